@@ -30,6 +30,13 @@ frame reduce measured on its own (`multi_gpu`).
 renderer, a 64x48 frame): rank 0 reports whether the reduced frame equals a one-process render bit
 for bit (tests/test_bench_cpu.py). It measures nothing.
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the
+line; its `roofline`, `cpu_baseline`, `psnr_vs_reference` and `reference_equivalent_work` are null.
+`--full` adds what takes runs of its own after the timed region: the frames rendered one at a time and
+the count pass behind `roofline`, the CPU leg and the converged PSNR against the reference render
+(each still has its own --no-... switch). `--dump-outputs DIR` writes the last timed step's frame
+accumulator to DIR/accum.npy (float32; a fixed seeded sample of its pixels where it exceeds 64 MB).
+
 Prints ONE JSON line on rank 0 (see DESIGN.md §6 for every field).
 """
 import argparse
@@ -105,6 +112,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--spp", type=int, default=0, help="override the config's spp")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the roofline "
+                         "(frames rendered one at a time, the count pass), the CPU baseline and the PSNR against "
+                         "the reference render")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the frame accumulator the last timed step produced to DIR/accum.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-psnr", action="store_true", help="skip the converged PSNR check vs the reference render")
     ap.add_argument("--no-count-pass", action="store_true",
@@ -155,7 +168,32 @@ def parse():
     ap.add_argument("--launch-streams", type=int, default=-1,
                     help="rmr_set_launch_streams for every renderer context (-1: the library default; 0 off; "
                          "N >= 2: consecutive trace launches overlap on N private streams)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.dry_run or args.predict):
+        ap.error("--dump-outputs: --dry-run and --predict have no timed frame to write")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each array (what a caller of the timed path receives) as DIR/<name>.npy, float32.
+    An array over the size limit is cut to a fixed sample of its leading-axes elements (pixels), drawn
+    with a constant seed, so two builds dump the same elements."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > budget:
+            rows = a.reshape(-1, a.shape[-1])
+            keep = budget // (4 * rows.shape[1])
+            idx = np.sort(np.random.default_rng(0x524D52).choice(rows.shape[0], size=keep, replace=False))
+            a = rows[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def scene_for_frame(cfg, frame):
@@ -687,6 +725,8 @@ def api_render_bench(args, cfg):
     elapsed = time.perf_counter() - t0
     st = r.stats()
     got = r.read_accum()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"accum": got})
     calls = len(rects) * spp * args.steps
     samples = float(cw * ch * len(rects)) * spp * args.steps
     # the same frame as one batched call (checked bit for bit, then timed the same number of times)
@@ -763,6 +803,8 @@ def api_group_bench(args, cfg):
     elapsed = time.perf_counter() - t0
     per = [g.stats(m) for m in range(g.size())]
     got = g.read_frame()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"accum": got})
     g.close()
     r = Renderer(0, W, H)
     load_into(r, cfg, scene)
@@ -911,6 +953,9 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     st = combined_stats(rs)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's frame (on rank 0 the reduced one), before anything renders again
+        dump_outputs(args.dump_outputs, {"accum": fr.last.cpu().numpy()})
     per_rank = None
     reduce_ms = None
     verify = None
@@ -949,8 +994,8 @@ def main():
 
     # overlapped frames: the per-launch event times include time the kernel waited behind the other
     # context's, so the roofline's per-launch figures come from `steps` more frames rendered one at a
-    # time (each synchronised before the next starts), outside the timed region
-    if n_ctx > 1:
+    # time (each synchronised before the next starts), outside the timed region (--full)
+    if args.full and n_ctx > 1:
         for r in rs:
             r.reset_stats()
         for _ in range(args.steps):
@@ -962,9 +1007,9 @@ def main():
     roof = None
     work_ref = None
     cp = None
-    if rank == 0 and not args.no_count_pass and st.jit_launches:
+    if args.full and rank == 0 and not args.no_count_pass and st.jit_launches:
         cp = count_pass(cfg, spp, local_rank)
-    if st.trace_launches > 0 and st.trace_ms > 0:
+    if args.full and st.trace_launches > 0 and st.trace_ms > 0:
         # rank 0's dominant kernel: its own map evals over its own launches. Executed flops per map
         # from the count pass (BVH / cache maps evaluate a few primitives, the Mandelbulb iterates a
         # point-dependent number of times); reference-equivalent: every primitive of the scene per
@@ -1019,11 +1064,11 @@ def main():
                             "rendered one at a time after the timed region" % (n_ctx, args.steps))
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, spp, args.cpu_seconds, cpu_threads())
 
     parity = None
-    if rank == 0 and not args.no_psnr:
+    if args.full and rank == 0 and not args.no_psnr:
         parity = psnr_vs_reference(args.config, cfg, local_rank)
 
     if rank == 0:

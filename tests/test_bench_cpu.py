@@ -42,6 +42,34 @@ def test_bench_rejects_mismatched_launcher():
     assert p.returncode != 0 and "--gpus 2" in p.stderr
 
 
+def test_dump_outputs_writes_float32_within_the_size_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs: a small array whole; one over the limit as the same seeded sample of its
+    pixels on every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    small = np.arange(6 * 5 * 4, dtype=np.float64).reshape(6, 5, 4)
+    big = np.arange(40 * 30 * 4, dtype=np.float32).reshape(40, 30, 4)
+    bench.dump_outputs(str(tmp_path / "a"), {"small": small})
+    bench.dump_outputs(str(tmp_path / "b"), {"accum": big})
+    bench.dump_outputs(str(tmp_path / "c"), {"accum": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small)
+    b, c = np.load(tmp_path / "b" / "accum.npy"), np.load(tmp_path / "c" / "accum.npy")
+    assert b.dtype == np.float32 and b.shape == (256, 4) and b.nbytes <= 4096
+    assert np.array_equal(b, c)
+    # whole pixels of the frame, in frame order, none twice
+    px = b[:, 0].astype(np.int64) // 4
+    assert np.array_equal(b, big.reshape(-1, 4)[px]) and (np.diff(px) > 0).all()
+
+
+def test_steps_must_be_positive():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0"],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
 def test_default_contexts_and_hardware_queues(monkeypatch):
     """bench.default_overlap: four overlapping contexts for a rank's frame share of <= 20 M samples
     when the process has 8 hardware queues (bench.py raises GPU_MAX_HW_QUEUES to 8 at import), two

@@ -66,10 +66,38 @@ def test_predict_partition_line():
 @pytest.mark.timeout(300)
 def test_default_line_overlaps_frames_and_times_launches_solo():
     """bench.py's default N = 1 line: two renderer contexts whose consecutive frames overlap (the
-    value), and the roofline's per-launch time from frames rendered one at a time afterwards."""
-    out = _run("--config", "c1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-psnr")
+    value), and with --full the roofline's per-launch time from frames rendered one at a time afterwards."""
+    out = _run("--config", "c1", "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-psnr")
     assert out["n_gpus"] == 1 and out["config"]["frame_streams"] == 4   # C1: four contexts (default_overlap)
     roof = out["roofline"]
     assert "one at a time" in roof["note"]
     assert 0 < roof["avg_launch_ms"] < 5 and roof["map_evals_per_launch"] > 0
     assert out["value"] > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_plain_line_is_lean_and_dumps_last_frame(tmp_path):
+    """A plain run times its steps and nothing else (the legs behind --full are null), and
+    --dump-outputs writes the last timed step's frame: bit for bit a one-context render of it."""
+    import numpy as np
+    from raymarchrenderer_amd import Renderer, abi, time_schedule
+    from raymarchrenderer_amd.multi_gpu import frame_tiles
+    out = _run("--gpus", "1", "--config", "c1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+    # value and ms_per_step describe the same timed steps (ms_per_step is rounded to 0.001 ms, value to 0.01)
+    rel = 0.0006 / out["ms_per_step"] + 0.01 / out["value"] + 1e-6
+    assert abs(out["value"] - 256 * 256 / out["ms_per_step"] / 1e3) <= rel * out["value"]
+    for k in ("roofline", "cpu_baseline", "psnr_vs_reference", "reference_equivalent_work"):
+        assert out[k] is None, k
+    got = np.load(tmp_path / "accum.npy")
+    assert got.dtype == np.float32 and got.shape == (256, 256, 4)
+    r = Renderer(0, 256, 256)   # C1: sphere1.scene 256x256, 1 spp, 1 bounce, 32x32 tiles (bench.CONFIGS)
+    try:
+        r.load_scene(os.path.join(ROOT, "scenes", "sphere1.scene"), "rm1")
+        r.set_params(abi.default_params(max_bounces=1))
+        r.render_tiles(time_schedule(1), frame_tiles(256, 256, 32), 32)
+        want = r.read_accum()
+    finally:
+        r.close()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
