@@ -1,5 +1,5 @@
 // grid.hpp — candidate grid of the nearest-primitive cache's full map() (rmr_trace.h map_grid_npc):
-// host construction, shared by the context upload (rmr_api.cpp build_grid) and the CPU-testable
+// host construction, shared by the scene acceleration (accel.cpp build_grid) and the CPU-testable
 // C-ABI hook rmr_candidate_grid.
 #pragma once
 #include <hip/hip_runtime.h>   // (vector types of rmr_internal.h)

@@ -21,7 +21,7 @@
 
 #include "../../include/rmr.h"
 #include "rmr_internal.h"
-#include "grid.hpp"
+#include "accel.hpp"
 #include "rmr_jit.hpp"
 #include "scene.hpp"
 
@@ -65,11 +65,11 @@ struct rmr_ctx {
     rmr::DPrim* d_dprims = nullptr;
     rmr::DMat* d_dmats = nullptr;
     rmr::BvhNode* d_bvh = nullptr;
-    // escape bound (rmr_trace.h ray_exit): <= kMaxEscBoxes boxes covering every primitive (lo.xyz,
-    // hi.xyz), uploaded inflated by esc_infl (which depends on the view and maxDist)
-    std::vector<float> esc_raw;
-    std::vector<rmr::BvhNode> bvh_host;   // host copy of the BVH (escape-box cut)
-    std::vector<int> bvh_order;           // leaf-order -> scene index
+    // what the host works out per scene (accel.hpp); after the upload without the grid's arrays
+    rmr::SceneAccel accel;
+    KParams scene_kp{};                   // the launch parameters that only a scene load changes (scene_params)
+    // escape bound (rmr_trace.h ray_exit): accel.esc_raw uploaded inflated by esc_infl_dev (which
+    // depends on the view and maxDist)
     float* d_esc = nullptr;
     double esc_infl_dev = -1.0;
     float4* d_env = nullptr;              // envTex (rmr_set_env_map)
@@ -77,17 +77,10 @@ struct rmr_ctx {
     uint32_t* d_screen = nullptr;         // rmr_display: staging of a host screen image
     size_t screen_cap = 0;
     int env_w = 0, env_h = 0;
-    int n_bvh = 0;
-    float bvh_margin = 1e-4f;
-    // candidate grid of the cache's full map() (build_grid; BVH scenes)
+    // candidate grid of the cache's full map() (accel.grid_on; BVH scenes)
     uint4* d_grid = nullptr;
     uint16_t* d_grid_list = nullptr;
-    bool grid_on = false;
-    bool grid_small_spheres = false;   // every primitive a cell can list is a sphere (rmr_jit.cpp)
-    float grid_lo[3] = {0, 0, 0}, grid_inv = 1.0f, grid_sbox[6] = {0, 0, 0, 0, 0, 0};
-    int grid_dim[3] = {0, 0, 0}, grid_n_large = 0;
-    int map_np = -1;  // map() specialisation: 4/8 unrolled, 0 loop, -1 general
-    bool has_prog = true;  // RM1 scene has materials needing the generic node interpreter
+    int npc_ksel = 0;   // RMR_NPC_KSEL (experiments): the cache's primitives per lane, 0 = by the kernel class
     // buffers
     float4* d_accum = nullptr;
     bool accum_external = false;
@@ -132,8 +125,7 @@ struct rmr_ctx {
     // the consecutive samples requested so far, launched together at the next call of any other entry
     // point (flush_calls); rmr_set_call_batching: -1 auto (on while the context owns its stream and its
     // accumulator), 0 off, 1 on
-    struct Deferred { int x0, y0, x1, y1; uint32_t s0; std::vector<float> times; };
-    std::vector<Deferred> deferred;
+    std::vector<rmr::DeferredCall> deferred;
     uint64_t deferred_units = 0;
     int call_batching = -1;
     unsigned long long* d_queue = nullptr;
@@ -246,172 +238,20 @@ void default_view(rmr_ctx* c) {
     c->view_set = true;
 }
 
-// Scenes of more than kMaxLoopPrims spheres/boxes use the exact-culling BVH map (map_bvh in
-// rmr_trace.h): median-split hierarchy over the primitives' boxes, leaves of <= 4, pre-order with
-// skip links; the primitives are stored in leaf order with their scene index (the id tie-break).
-constexpr size_t kMaxLoopPrims = 32;
-
-int upload_bvh(rmr_ctx* c);
-
-// Escape boxes: each primitive's box for scenes of <= kMaxEscBoxes primitives; for BVH scenes a cut
-// of the hierarchy (the always-visited large primitives individually, then the node with the most
-// primitives split until kMaxEscBoxes boxes). Their union covers every primitive.
-constexpr size_t kMaxEscBoxesDefault = 32;
-size_t max_esc_boxes() {   // env RMR_ESC_BOXES (experiments), read at scene upload
-    if (const char* e = RMR_ENV("RMR_ESC_BOXES")) return (size_t)std::max(1, std::min(64, std::atoi(e)));
-    return kMaxEscBoxesDefault;
-}
-// A Mandelbulb primitive (sd_mandelbulb) takes part when it iterates at least once with a bailout
-// >= 1.5: at |p - c| > bailout its loop stops at once with r = |p - c|, dr = 1, so its distance is
-// 0.5 log(r) r >= 0.30 — the box c +- bailout then bounds everything within 0.001 of it.
-bool escape_prim(const rmr_prim& q) {
-    if (q.type == RMR_PRIM_SPHERE || q.type == RMR_PRIM_BOX) return true;
-    return q.type == RMR_PRIM_MANDELBULB && q.r[1] >= 1.0f && q.r[2] >= 1.5f && std::isfinite(q.r[2]);
-}
-float escape_halfwidth(const rmr_prim& q, int k) {
-    if (q.type == RMR_PRIM_SPHERE) return std::fabs(q.r[0]);
-    if (q.type == RMR_PRIM_MANDELBULB) return q.r[2];
-    return std::fabs(q.r[k]);
-}
-void build_escape_boxes(rmr_ctx* c, bool simple) {
-    const CompiledScene& s = c->scene;
-    c->esc_raw.clear();
-    bool ok = !s.prims.empty();
-    for (const rmr_prim& q : s.prims) ok = ok && escape_prim(q);
-    const size_t kMaxEscBoxes = max_esc_boxes();
-    if (!ok || (!simple && s.prims.size() > kMaxEscBoxes)) return;
-    auto prim_box = [&](const rmr_prim& q, float* b) {
-        for (int k = 0; k < 3; k++) {
-            const float h = escape_halfwidth(q, k);
-            b[k] = q.c[k] - h;
-            b[3 + k] = q.c[k] + h;
-        }
-    };
-    float b[6];
-    if (c->map_np != -2 || s.prims.size() <= kMaxEscBoxes) {   // one box per primitive
-        for (const rmr_prim& q : s.prims) {
-            prim_box(q, b);
-            c->esc_raw.insert(c->esc_raw.end(), b, b + 6);
-        }
-        return;
-    }
-    // BVH scene: nodes are in pre-order (first child = next node, second child = that node's skip);
-    // leaves of the always-visited list have infinite bounds: use their primitives' own boxes
-    std::vector<int> cut;
-    for (size_t i = 0; i < c->bvh_host.size();) {
-        const rmr::BvhNode& nd = c->bvh_host[i];
-        if (nd.lo[0] <= -1e38f) {   // always-visited leaf of large primitives
-            for (int k = nd.first; k < nd.first + nd.count; k++) {
-                prim_box(s.prims[(size_t)(c->bvh_order[(size_t)k])], b);
-                c->esc_raw.insert(c->esc_raw.end(), b, b + 6);
-            }
-            i = (size_t)nd.skip;
-            continue;
-        }
-        cut.push_back((int)i);   // root of the remaining hierarchy
-        break;
-    }
-    while (!cut.empty() && c->esc_raw.size() / 6 + cut.size() < kMaxEscBoxes) {
-        // split the internal node of the cut with the largest box
-        int best = -1;
-        float bestv = -1.0f;
-        for (size_t q = 0; q < cut.size(); q++) {
-            const rmr::BvhNode& nd = c->bvh_host[(size_t)cut[q]];
-            if (nd.count != 0) continue;
-            const float v = (nd.hi[0] - nd.lo[0]) * (nd.hi[1] - nd.lo[1]) * (nd.hi[2] - nd.lo[2]);
-            if (v > bestv) { bestv = v; best = (int)q; }
-        }
-        if (best < 0) break;
-        const int i = cut[(size_t)best];
-        cut[(size_t)best] = i + 1;
-        cut.push_back(c->bvh_host[(size_t)(i + 1)].skip);
-    }
-    for (int i : cut) {
-        const rmr::BvhNode& nd = c->bvh_host[(size_t)i];
-        for (int k = 0; k < 3; k++) { b[k] = nd.lo[k]; b[3 + k] = nd.hi[k]; }
-        c->esc_raw.insert(c->esc_raw.end(), b, b + 6);
-    }
-}
-
-// Shading kinds of the RM1 materials: the single-node diffuse / emission materials run the fast
-// shading path, every other defined material its node program (has_prog). Shared by upload_scene and
-// rmr_jit_compile_scene, so both pick the same kernel class.
-std::vector<rmr::DMat> shading_kinds(const CompiledScene& s) {
-    std::vector<rmr::DMat> dm(std::max<size_t>(1, s.materials.size()));
-    for (size_t i = 0; i < s.materials.size(); i++) {
-        const rmr_material& m = s.materials[i];
-        rmr::DMat d{};
-        d.kind = m.defined ? rmr::MAT_PROGRAM : rmr::MAT_NONE;
-        if (m.defined && m.prog_end - m.prog_begin == 1 && m.inside_var < 0 && m.hit_var < 0) {
-            const rmr_op& op = s.ops[(size_t)m.prog_begin];
-            auto lit = [&](int ref, float* out) {
-                if (!RMR_OPND_IS_CONST(ref)) return false;
-                const int k = RMR_OPND_CONST_INDEX(ref);
-                for (int j = 0; j < 3; j++) out[j] = s.consts[3 * (size_t)k + j];
-                return true;
-            };
-            if (op.code == RMR_OP_M_DIFFUSE && m.color_var == op.out[0] && m.dir_var == op.out[1] &&
-                op.out[0] != op.out[1] && lit(op.in[0], d.c))
-                d.kind = rmr::MAT_DIFFUSE;
-            else if (op.code == RMR_OP_M_EMISSION && m.color_var == op.out[0] && m.dir_var < 0 &&
-                     lit(op.in[0], d.c) && lit(op.in[1], d.p)) {
-                d.kind = rmr::MAT_EMISSION;
-                // grayscale of p * vec3(1) without separateChannels (rmr_trace.h gray_ch, RM1:306-309):
-                // x * 1 is exact, so this is the kernel's ((p.x + p.y) + p.z) / (1 + 1 + 1)
-                const float sum = (d.p[0] + d.p[1]) + d.p[2];
-                d.gray1 = sum / 3.0f;
-            }
-        }
-        dm[i] = d;
-    }
-    return dm;
-}
-bool any_program(const std::vector<rmr::DMat>& dm) {
-    for (const auto& d : dm)
-        if (d.kind == rmr::MAT_PROGRAM) return true;
-    return false;
-}
-
 int free_slots(rmr_ctx* c);
 
-int upload_scene(rmr_ctx* c) {
-    const CompiledScene& s = c->scene;
-    int r;
-    if ((r = dev_upload(c, &c->d_prims, s.prims.data(), s.prims.size()))) return r;
-    if ((r = dev_upload(c, &c->d_ops, s.ops.data(), s.ops.size()))) return r;
-    if ((r = dev_upload(c, &c->d_consts, s.consts.data(), s.consts.size()))) return r;
-    if ((r = dev_upload(c, &c->d_mats, s.materials.data(), s.materials.size()))) return r;
-    if ((r = dev_upload(c, &c->d_spec, s.spectral.data(), s.spectral.size()))) return r;
-    if ((r = dev_upload(c, &c->d_rm2, &s.rm2, 1))) return r;
-    const std::vector<rmr::DMat> dm = shading_kinds(s);
-    c->has_prog = any_program(dm);
-    if ((r = dev_upload(c, &c->d_dmats, dm.data(), dm.size()))) return r;
-    // packed prims + map() specialisation
-    bool simple = true;
-    for (const auto& p : s.prims) simple = simple && (p.type == RMR_PRIM_SPHERE || p.type == RMR_PRIM_BOX);
-    const size_t n = s.prims.size();
-    c->map_np = !simple || n == 0 ? -1 : (n <= 4 ? 4 : (n <= 8 ? 8 : (n <= kMaxLoopPrims ? 0 : -2)));
-    if (c->map_np == -2) {
-        if ((r = upload_bvh(c))) return r;
-    } else {
-        std::vector<rmr::DPrim> dp(std::max<size_t>(n, 8));
-        for (size_t i = 0; i < dp.size(); i++) {
-            rmr::DPrim q{};
-            if (i < n) {
-                const rmr_prim& p = s.prims[i];
-                for (int k = 0; k < 3; k++) { q.c[k] = p.c[k]; q.r[k] = p.r[k]; }
-                q.type = p.type;
-                q.mat_id = p.mat_id;
-            }
-            dp[i] = q;
-        }
-        if ((r = dev_upload(c, &c->d_dprims, dp.data(), dp.size()))) return r;
-        c->n_bvh = 0;
-        c->grid_on = false;
-    }
-    build_escape_boxes(c, simple);
-    c->esc_infl_dev = -1.0;
-    if (const char* e = RMR_ENV("RMR_FULL_T"))   // (experiments; read per scene load)
+// The experiments' switches of the diagnostic library that take effect at a scene load (RMR_ENV is
+// nullptr in the release library, rmr_jit.hpp; rmr_create reads those of a context's settings).
+rmr::AccelOptions read_switches(rmr_ctx* c) {
+    rmr::AccelOptions o;
+    if (const char* e = RMR_ENV("RMR_ESC_BOXES")) o.max_esc_boxes = (size_t)std::max(1, std::min(64, std::atoi(e)));
+    if (const char* e = RMR_ENV("RMR_BVH_LEAF")) o.bvh_leaf = std::max(1, std::min(16, std::atoi(e)));
+    if (const char* e = RMR_ENV("RMR_GRID")) o.grid = std::atoi(e) != 0;
+    if (const char* e = RMR_ENV("RMR_GRID_CELLS")) o.grid_cells = std::max(1.0, std::atof(e));
+    if (const char* e = RMR_ENV("RMR_GRID_PAD")) o.grid_pad = std::max(0.0, std::atof(e));
+    c->npc_ksel = 0;
+    if (const char* e = RMR_ENV("RMR_NPC_KSEL")) c->npc_ksel = std::atoi(e) == 1 ? 1 : 2;
+    if (const char* e = RMR_ENV("RMR_FULL_T"))
         c->full_threshold = (c->full_threshold & ~0xff) | std::max(1, std::min(64, std::atoi(e)));
     if (const char* e = RMR_ENV("RMR_FULL_R"))
         c->full_threshold = (c->full_threshold & 0xff) | (std::max(0, std::min(255, std::atoi(e))) << 8);
@@ -419,10 +259,74 @@ int upload_scene(rmr_ctx* c) {
     c->diag_no_fold = false;
     if (const char* e = RMR_ENV("RMR_DIAG_NO_FOLD")) c->diag_no_fold = std::atoi(e) != 0;
     if (const char* e = RMR_ENV("RMR_SLOT_RESERVE")) c->slot_reserve = std::max(0, std::atoi(e));
-    if (const char* e = RMR_ENV("RMR_LAUNCH_STREAMS")) {   // (experiments; the slots go at the next launch)
+    if (const char* e = RMR_ENV("RMR_LAUNCH_STREAMS")) {   // (the slots go at the next launch)
         (void)free_slots(c);
         c->launch_streams = std::max(0, std::min(4, std::atoi(e)));
     }
+    return o;
+}
+
+// The launch parameters that only a scene load changes: the tables and what accel.hpp derived from them.
+KParams scene_params(const rmr_ctx* c) {
+    const CompiledScene& s = c->scene;
+    const rmr::SceneAccel& a = c->accel;
+    KParams P{};
+    P.prims = c->d_prims; P.ops = c->d_ops; P.consts = c->d_consts; P.mats = c->d_mats;
+    P.spec = c->d_spec; P.rm2 = c->d_rm2;
+    P.dprims = c->d_dprims; P.dmats = c->d_dmats;
+    P.bvh = c->d_bvh; P.n_nodes = (int)a.nodes.size(); P.bvh_margin = a.bvh_margin;
+    if (a.grid_on) {
+        P.grid = c->d_grid; P.grid_list = c->d_grid_list; P.grid_inv = a.grid.inv; P.grid_n_large = a.n_large;
+        for (int k = 0; k < 3; k++) {
+            P.grid_lo[k] = a.grid.lo[k];
+            P.grid_dim[k] = a.grid.dim[k];
+            P.grid_dimf[k] = (float)a.grid.dim[k];
+        }
+        for (int k = 0; k < 6; k++) P.grid_sbox[k] = a.grid.sbox[k];
+    }
+    P.n_prims = (int)s.prims.size();
+    P.am_r2 = a.am_r2;
+    P.npc_eps0 = a.npc_eps0;
+    P.cert_k = a.cert_k;
+    P.full_threshold = c->full_threshold;
+    P.n_mats = (int)(s.variant == RMR_VARIANT_RM3 ? s.spectral.size() : s.materials.size());
+    P.v2_begin = s.v2_begin; P.v2_end = s.v2_end;
+    P.spec_sky = s.spectral_sky;
+    for (int i = 0; i < 3; i++) { P.sky[i] = s.sky[i]; P.rm2_light[i] = s.rm2.light_pos[i]; }
+    P.rm2_light_power = s.rm2.light_power;
+    P.rm2_node_id = s.rm2.node_mat_id;
+    P.queue = c->d_queue;
+    P.counters = c->d_counters;
+    P.flops_static = (int32_t)s.flops_per_map();
+    P.transc_static = (int32_t)s.transc_per_map();
+    return P;
+}
+
+int upload_scene(rmr_ctx* c) {
+    const CompiledScene& s = c->scene;
+    const rmr::AccelOptions opt = read_switches(c);
+    c->accel = rmr::build_scene_accel(s, opt);
+    rmr::SceneAccel& a = c->accel;
+    int r;
+    if ((r = dev_upload(c, &c->d_prims, s.prims.data(), s.prims.size()))) return r;
+    if ((r = dev_upload(c, &c->d_ops, s.ops.data(), s.ops.size()))) return r;
+    if ((r = dev_upload(c, &c->d_consts, s.consts.data(), s.consts.size()))) return r;
+    if ((r = dev_upload(c, &c->d_mats, s.materials.data(), s.materials.size()))) return r;
+    if ((r = dev_upload(c, &c->d_spec, s.spectral.data(), s.spectral.size()))) return r;
+    if ((r = dev_upload(c, &c->d_rm2, &s.rm2, 1))) return r;
+    if ((r = dev_upload(c, &c->d_dmats, a.dmats.data(), a.dmats.size()))) return r;
+    if ((r = dev_upload(c, &c->d_dprims, a.dprims.data(), a.dprims.size()))) return r;
+    if (a.map_np == -2 && (r = dev_upload(c, &c->d_bvh, a.nodes.data(), a.nodes.size()))) return r;
+    if (a.grid_on) {
+        if ((r = dev_upload(c, &c->d_grid, a.grid_cells.data(), a.grid_cells.size()))) return r;
+        if ((r = dev_upload(c, &c->d_grid_list, a.grid.list.data(), a.grid.list.size()))) return r;
+    }
+    // (the grid's arrays live on the device from here: 16 MB of cell records)
+    a.grid_cells = {};
+    a.grid.cells = {};
+    a.grid.list = {};
+    c->esc_infl_dev = -1.0;
+    c->scene_kp = scene_params(c);
     c->scene_loaded = true;
     c->jit_ready = false;
     c->jit_failed = false;
@@ -436,7 +340,7 @@ int ensure_jit(rmr_ctx* c) {
     // animation: same structure as the last specialised scene, different numbers -> the primitives
     // that changed since the kernel's baked values become loads ("live"), the others stay literals:
     // one compile when the motion starts, then the same kernel every frame
-    const std::string struct_src = rmr::jit_source(c->scene, c->has_prog, false, c->cull);
+    const std::string struct_src = rmr::jit_source(c->scene, c->accel.has_prog, false, c->cull);
     const auto& prims = c->scene.prims;
     if (struct_src != c->jit_struct_src || c->jit_base.size() != prims.size()) {   // new layout
         c->jit_base = prims;
@@ -446,13 +350,10 @@ int ensure_jit(rmr_ctx* c) {
             if (std::memcmp(&prims[j], &c->jit_base[j], sizeof(rmr_prim)) != 0) c->jit_live[j] = 1;
     }
     c->jit_struct_src = struct_src;
-    // one cached primitive when the cache's full map() runs through the candidate grid (csg256: 21.5 ->
-    // 17.4 ms per 4 spp against two); two with the BVH full map
-    int npc_k = (c->map_np == -2 && c->grid_on) ? 1 : 2;
-    if (const char* e = RMR_ENV("RMR_NPC_KSEL")) npc_k = std::atoi(e) == 1 ? 1 : 2;   // (experiments)
-    const bool npc_spheres = c->map_np == -2 && c->grid_on && c->grid_small_spheres;
+    const rmr::CacheFacts cache = rmr::cache_kernel_facts(c->accel, c->accel.grid_on);
     rmr::JitFacts facts;
-    const std::string src = rmr::jit_source(c->scene, c->has_prog, true, c->cull, &c->jit_live, npc_k, npc_spheres, &facts);
+    const std::string src = rmr::jit_source(c->scene, c->accel.has_prog, true, c->cull, &c->jit_live,
+                                            c->npc_ksel ? c->npc_ksel : cache.npc_k, cache.npc_spheres, &facts);
     std::vector<char> code;
     std::string key, log;
     std::vector<std::string> opts;
@@ -497,208 +398,6 @@ int ensure_jit(rmr_ctx* c) {
     c->jit_loaded.push_back(k);
     c->jit = k;
     c->jit_ready = true;
-    return RMR_OK;
-}
-
-namespace {
-struct BvhItem {
-    float lo[3], hi[3], cen[3];
-    int idx;
-};
-int bvh_leaf_size() {   // primitives per BVH leaf (env RMR_BVH_LEAF: experiments), read at scene upload
-    if (const char* e = RMR_ENV("RMR_BVH_LEAF")) return std::max(1, std::min(16, std::atoi(e)));
-    return 8;   // csg256 4 spp: 2 / 3 / 4 / 6 / 8 / 12 / 16 -> 37.0 / 36.1 / 34.1 / 33.3 / 32.9 / 33.1 / 33.6 ms
-}
-void bvh_build(std::vector<BvhItem>& it, int l, int r, std::vector<rmr::BvhNode>& nodes, std::vector<int>& order) {
-    const int me = (int)nodes.size();
-    nodes.push_back(rmr::BvhNode{});
-    rmr::BvhNode nd{};
-    for (int k = 0; k < 3; k++) { nd.lo[k] = 3.0e38f; nd.hi[k] = -3.0e38f; }
-    float clo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, chi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-    for (int i = l; i < r; i++)
-        for (int k = 0; k < 3; k++) {
-            nd.lo[k] = std::min(nd.lo[k], it[i].lo[k]);
-            nd.hi[k] = std::max(nd.hi[k], it[i].hi[k]);
-            clo[k] = std::min(clo[k], it[i].cen[k]);
-            chi[k] = std::max(chi[k], it[i].cen[k]);
-        }
-    if (r - l <= bvh_leaf_size()) {
-        std::sort(it.begin() + l, it.begin() + r, [](const BvhItem& a, const BvhItem& b) { return a.idx < b.idx; });
-        nd.first = (int)order.size();
-        nd.count = r - l;
-        for (int i = l; i < r; i++) order.push_back(it[i].idx);
-    } else {
-        int ax = 0;
-        for (int k = 1; k < 3; k++)
-            if (chi[k] - clo[k] > chi[ax] - clo[ax]) ax = k;
-        const int mid = (l + r) / 2;
-        std::nth_element(it.begin() + l, it.begin() + mid, it.begin() + r,
-                         [ax](const BvhItem& a, const BvhItem& b) { return a.cen[ax] < b.cen[ax]; });
-        nd.first = -1;
-        nd.count = 0;
-        bvh_build(it, l, mid, nodes, order);
-        bvh_build(it, mid, r, nodes, order);
-    }
-    nd.skip = (int)nodes.size();
-    nodes[(size_t)me] = nd;
-}
-}  // namespace
-
-// Candidate grid over the small primitives (leaf order [n_large, n)) of a BVH scene, for the nearest-
-// primitive cache's full map() (rmr_trace.h map_grid_npc). Per cell C (inflated past the kernel's
-// rounding of the cell index): U = the smallest distance upper bound over C of any primitive (box and
-// sphere SDFs are convex: the maximum is at a corner); the list = the small primitives whose distance
-// lower bound over C is <= U + margin (margin = 4 x the float evaluation error bound of a distance
-// anywhere in the grid, so an unlisted primitive's float distance is strictly above the minimum's);
-// the cell's bound = the smallest lower bound of an unlisted one, minus that error bound. Exact
-// arithmetic in double; cells of more than 254 candidates keep the BVH (count 255).
-// Env (experiments): RMR_GRID=0 off, RMR_GRID_CELLS (target cell count), RMR_GRID_PAD (region pad).
-// The construction is host code (grid.cpp, build_candidate_grid); this uploads it.
-int build_grid(rmr_ctx* c, const std::vector<rmr::DPrim>& dp, int n_large, double E) {
-    c->grid_on = false;
-    if (const char* e = RMR_ENV("RMR_GRID")) if (std::atoi(e) == 0) return RMR_OK;
-    // 2^20 cells (round 3; csg256 1080p 8 spp, same process: 2^18 21.1, 2^19 20.2, 2^20 19.9 ms,
-    // flat beyond; 16 MB of cell records, ~0.4 s to build on 16 host threads)
-    double target = 1048576.0, pad = 0.5;
-    if (const char* e = RMR_ENV("RMR_GRID_CELLS")) target = std::max(1.0, std::atof(e));
-    if (const char* e = RMR_ENV("RMR_GRID_PAD")) pad = std::max(0.0, std::atof(e));
-    rmr::CandidateGrid g;
-    if (!rmr::build_candidate_grid(dp, n_large, E, target, pad, g)) return RMR_OK;
-    int r;
-    // device cells: the host record (offset | count, bound) plus the list's first four entries
-    // inline, so most full-map lanes read their candidates without a dependent list load
-    const size_t ncell = g.cells.size() / 2;
-    if (ncell >= ((size_t)1 << 31)) return RMR_OK;   // the kernel's cell index is 32-bit (map_grid_npc)
-    std::vector<uint4> cells4(ncell);
-    for (size_t i = 0; i < ncell; i++) {
-        const uint32_t x = g.cells[2 * i], off = x & 0xffffffu, cnt = x >> 24;
-        uint32_t e[4] = {0, 0, 0, 0};
-        for (uint32_t k = 0; k < 4 && cnt != 255u && k < cnt; k++) e[k] = g.list[off + k];
-        cells4[i] = make_uint4(x, g.cells[2 * i + 1], e[0] | (e[1] << 16), e[2] | (e[3] << 16));
-    }
-    if ((r = dev_upload(c, &c->d_grid, cells4.data(), cells4.size()))) return r;
-    if ((r = dev_upload(c, &c->d_grid_list, g.list.data(), g.list.size()))) return r;
-    for (int k = 0; k < 3; k++) { c->grid_lo[k] = g.lo[k]; c->grid_dim[k] = g.dim[k]; }
-    for (int k = 0; k < 6; k++) c->grid_sbox[k] = g.sbox[k];
-    c->grid_inv = g.inv;
-    c->grid_n_large = n_large;
-    c->grid_small_spheres = true;
-    for (size_t k = (size_t)n_large; k < dp.size(); k++)
-        c->grid_small_spheres = c->grid_small_spheres && (dp[k].type & 0xff) == RMR_PRIM_SPHERE;
-    c->grid_on = true;
-    return RMR_OK;
-}
-
-// Bounding boxes of a BVH scene's primitives, and which are "large": primitives much larger than the
-// typical one (ground planes, walls) would make every box above them cover the scene, so they go
-// first, in an always-visited leaf (infinite bounds), which also gives the running minimum a small
-// value early; the candidate grid lists only the others. Shared by upload_bvh and
-// rmr_jit_compile_scene (the cache kernel's RMR_NPC_SPHERES depends on the split).
-std::vector<BvhItem> bvh_items(const CompiledScene& s, std::vector<char>& is_large, float& extent) {
-    std::vector<BvhItem> items;
-    extent = 0.0f;
-    for (size_t i = 0; i < s.prims.size(); i++) {
-        const rmr_prim& p = s.prims[i];
-        BvhItem b{};
-        for (int k = 0; k < 3; k++) {
-            const float h = (p.type == RMR_PRIM_SPHERE) ? std::fabs(p.r[0]) : std::fabs(p.r[k]);
-            b.lo[k] = p.c[k] - h;
-            b.hi[k] = p.c[k] + h;
-            b.cen[k] = p.c[k];
-            extent = std::max(extent, std::fabs(p.c[k]) + h);
-        }
-        b.idx = (int)i;
-        items.push_back(b);
-    }
-    std::vector<float> ext;
-    for (const auto& b : items) ext.push_back(std::max({b.hi[0] - b.lo[0], b.hi[1] - b.lo[1], b.hi[2] - b.lo[2]}));
-    std::vector<float> sorted_ext = ext;
-    is_large.assign(items.size(), 0);
-    if (items.empty()) return items;
-    std::nth_element(sorted_ext.begin(), sorted_ext.begin() + sorted_ext.size() / 2, sorted_ext.end());
-    const float big = 8.0f * sorted_ext[sorted_ext.size() / 2];
-    for (size_t i = 0; i < items.size(); i++) is_large[i] = ext[i] > big;
-    return items;
-}
-
-int upload_bvh(rmr_ctx* c) {
-    const CompiledScene& s = c->scene;
-    std::vector<char> is_large;
-    float extent = 0.0f;
-    const std::vector<BvhItem> items = bvh_items(s, is_large, extent);
-    std::vector<BvhItem> small, large;
-    for (size_t i = 0; i < items.size(); i++) (is_large[i] ? large : small).push_back(items[i]);
-    std::vector<rmr::BvhNode> nodes;
-    std::vector<int> order;
-    if (!large.empty()) {
-        for (size_t at = 0; at < large.size(); at += 4) {  // leaves of <= 4, all always visited
-            rmr::BvhNode nd{};
-            for (int k = 0; k < 3; k++) { nd.lo[k] = -3.0e38f; nd.hi[k] = 3.0e38f; }
-            nd.first = (int)order.size();
-            nd.count = (int)std::min<size_t>(4, large.size() - at);
-            for (int i = 0; i < nd.count; i++) order.push_back(large[at + (size_t)i].idx);
-            nd.skip = (int)nodes.size() + 1;
-            nodes.push_back(nd);
-        }
-    }
-    if (!small.empty()) bvh_build(small, 0, (int)small.size(), nodes, order);
-    std::vector<rmr::DPrim> dp(order.size());
-    for (size_t k = 0; k < order.size(); k++) {
-        const rmr_prim& p = s.prims[(size_t)order[k]];
-        rmr::DPrim q{};
-        for (int i = 0; i < 3; i++) { q.c[i] = p.c[i]; q.r[i] = p.r[i]; }
-        q.type = p.type | (order[k] << 8);
-        q.mat_id = p.mat_id;
-        dp[k] = q;
-    }
-    int r;
-    if ((r = dev_upload(c, &c->d_dprims, dp.data(), dp.size()))) return r;
-    if ((r = dev_upload(c, &c->d_bvh, nodes.data(), nodes.size()))) return r;
-    c->bvh_host = nodes;
-    c->bvh_order = order;
-    c->n_bvh = (int)nodes.size();
-    c->bvh_margin = 1e-4f + extent * 0x1p-16f;
-    double E = 0.0;   // max |c|_inf + |r|_inf (as render_tiles' npc_eps0)
-    for (const rmr_prim& q : s.prims) {
-        const double rr = q.type == RMR_PRIM_SPHERE ? std::fabs(q.r[0])
-                                                    : std::max({std::fabs(q.r[0]), std::fabs(q.r[1]), std::fabs(q.r[2])});
-        E = std::max(E, std::max({std::fabs((double)q.c[0]), std::fabs((double)q.c[1]), std::fabs((double)q.c[2])}) + rr);
-    }
-    int n_large = 0;
-    for (const rmr::BvhNode& nd : nodes) {   // the always-visited leaves come first (leaf order 0 ..)
-        if (nd.lo[0] > -1e38f) break;
-        n_large += nd.count;
-    }
-    return build_grid(c, dp, n_large, E);
-}
-
-int validate_scene(rmr_ctx* c, const CompiledScene& s) {
-    for (const auto& p : s.prims) {
-        if (p.type < RMR_PRIM_SPHERE || p.type > RMR_PRIM_MANDELBULB) return fail(c, RMR_E_SCENE, "bad prim type");
-        if (p.type == RMR_PRIM_PROGRAM) {
-            if (p.prog_begin < 0 || p.prog_end > (int)s.ops.size() || p.prog_begin > p.prog_end)
-                return fail(c, RMR_E_SCENE, "prim program range out of bounds");
-            if (p.dist_var < 0 || p.dist_var >= RMR_MAX_VARS) return fail(c, RMR_E_SCENE, "bad dist_var");
-        }
-    }
-    const int nconst = (int)(s.consts.size() / 3);
-    for (const auto& o : s.ops) {
-        for (int i = 0; i < 7; i++) {
-            const int r = o.in[i];
-            if (r == RMR_OPND_NONE || r == RMR_OPND_P) continue;
-            if (RMR_OPND_IS_CONST(r)) {
-                if (RMR_OPND_CONST_INDEX(r) >= nconst) return fail(c, RMR_E_SCENE, "constant index out of range");
-            } else if (r < 0 || r >= RMR_MAX_VARS) {
-                return fail(c, RMR_E_SCENE, "var index out of range");
-            }
-        }
-        for (int i = 0; i < 4; i++)
-            if (o.out[i] >= RMR_MAX_VARS) return fail(c, RMR_E_SCENE, "var index out of range");
-    }
-    for (const auto& m : s.materials)
-        if (m.defined && (m.prog_begin < 0 || m.prog_end > (int)s.ops.size())) return fail(c, RMR_E_SCENE, "material program range");
-    if (s.variant == RMR_VARIANT_RM2 && (s.v2_begin < 0 || s.v2_end > (int)s.ops.size()))
-        return fail(c, RMR_E_SCENE, "v2 program range");
     return RMR_OK;
 }
 
@@ -876,96 +575,36 @@ int collect_timing(rmr_ctx* c) {
     return RMR_OK;
 }
 
-// The launch's escape bound (rmr_trace.h ray_exit): the escape boxes inflated by 0.002 + 2^-16 (|eye| +
-// 2E + 3 maxDist) >= 0.001 + 8 x the float error of a distance at any point a march reaches
-// (|p| <= |eye| + E + 3 maxDist) + the rounding of the slab parameters
+// The launch's escape bound (rmr_trace.h ray_exit, accel.hpp escape_inflation): on for scenes whose every
+// primitive takes part; the boxes go to the device again when the inflation changed.
 int escape_params(rmr_ctx* c, KParams& P) {
-    const CompiledScene& s = c->scene;
-    bool simple = !s.prims.empty();
-    double E = 0.0;
-    for (const rmr_prim& q : s.prims) {
-        simple = simple && escape_prim(q);
-        if (!escape_prim(q)) continue;
-        for (int k = 0; k < 3; k++) E = std::max(E, std::fabs((double)q.c[k]) + (double)escape_halfwidth(q, k));
-    }
-    double eye = 0.0;
-    for (int k = 0; k < 3; k++) eye = std::max(eye, std::fabs((double)c->view[k]));
-    const double infl = 0.002 + std::ldexp(eye + 2.0 * E + 3.0 * std::fabs((double)c->params.max_dist), -16);
+    const rmr::SceneAccel& a = c->accel;
+    const double infl = rmr::escape_inflation(c->view, a.esc_extent, c->params.max_dist);
     // (infl < 2^44: |eye|, E, maxDist < 2^60, the range ray_exit's FMA slab form is exact in)
-    P.esc_on = (c->cull & RMR_CULL_ESCAPE) && simple && infl < 0x1p44 && !c->esc_raw.empty() ? 1 : 0;
+    P.esc_on = (c->cull & RMR_CULL_ESCAPE) && a.esc_all && infl < 0x1p44 && !a.esc_raw.empty() ? 1 : 0;
     if (P.esc_on && infl != c->esc_infl_dev) {
-        std::vector<float> bx(c->esc_raw.size());
-        for (size_t i = 0; i < bx.size(); i++)   // outward in double, then to float
-            bx[i] = (float)((double)c->esc_raw[i] + ((i % 6) < 3 ? -infl : infl));
+        const std::vector<float> bx = rmr::inflate_escape_boxes(a.esc_raw, infl);
         int rr;
         if ((rr = dev_upload(c, &c->d_esc, bx.data(), bx.size()))) return rr;
         c->esc_infl_dev = infl;
     }
     P.esc_boxes = c->d_esc;
-    P.n_esc = (int)(c->esc_raw.size() / 6);
+    P.n_esc = (int)(a.esc_raw.size() / 6);
     return RMR_OK;
 }
 
-// Core: nspp samples over an 8x8 tile list, clipped to [x0,x1)x[y0,y1).
-int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, int x1, int y1,
-                 const float* times, uint32_t first_sample, uint32_t nspp) {
+// What a launch needs of the context's state (rmr_render gives the same errors at the call it defers).
+int launch_precheck(rmr_ctx* c) {
     if (!c->scene_loaded) return fail(c, RMR_E_STATE, "no scene loaded (call rmr_load_scene_json / rmr_load_builtin_scene)");
     if (c->params.use_env_tex && !c->d_env) return fail(c, RMR_E_STATE, "useEnvTex != 0 but no env map (rmr_set_env_map)");
-    if (tiles.empty() || nspp == 0) return RMR_OK;
-    if (!c->view_set) default_view(c);
-    int r;
-    const TileXY* d_tiles = nullptr;
-    if ((r = tile_list(c, tiles, &d_tiles))) return r;
-    const size_t plane = tiles.size() * 64;
-    size_t chunk = std::max<size_t>(1, c->samp_budget / (plane * sizeof(float4)));
-    chunk = std::min<size_t>(chunk, nspp);
-    // the trace kernel indexes units with 32 bits (atomic work counter included): < 2^31 per launch
-    chunk = std::max<size_t>(1, std::min<size_t>(chunk, ((size_t)1 << 31) / plane));
-    // slots for launches whose planes fit the budget shared between the slots (larger ones, C4's 34-GB
-    // 4K 256-spp frame, run on the context's stream: one plane buffer of them is enough)
-    const bool slotted = c->launch_streams >= 2 && plane * chunk * sizeof(float4) <= c->samp_budget / (size_t)c->launch_streams;
-    if (slotted && c->slots.size() != (size_t)c->launch_streams) {
-        if ((r = free_slots(c)) || (r = make_slots(c))) return r;
-    }
-    const float* d_times = nullptr;
+    return RMR_OK;
+}
 
-    const CompiledScene& s = c->scene;
-    KParams P{};
-    P.prims = c->d_prims; P.ops = c->d_ops; P.consts = c->d_consts; P.mats = c->d_mats;
-    P.spec = c->d_spec; P.rm2 = c->d_rm2;
-    P.dprims = c->d_dprims; P.dmats = c->d_dmats;
-    P.bvh = c->d_bvh; P.n_nodes = c->n_bvh; P.bvh_margin = c->bvh_margin;
-    if (c->grid_on && c->map_np == -2) {
-        P.grid = c->d_grid; P.grid_list = c->d_grid_list; P.grid_inv = c->grid_inv; P.grid_n_large = c->grid_n_large;
-        for (int k = 0; k < 3; k++) {
-            P.grid_lo[k] = c->grid_lo[k];
-            P.grid_dim[k] = c->grid_dim[k];
-            P.grid_dimf[k] = (float)c->grid_dim[k];
-        }
-        for (int k = 0; k < 6; k++) P.grid_sbox[k] = c->grid_sbox[k];
-    }
-    P.n_prims = (int)s.prims.size();
-    P.am_r2 = 2.0f * rmr::max_sphere_radius(s);
-    {
-        float E = 0.0f;   // max |c|_inf + |r|_inf: scale of the float error of a box/sphere distance
-        for (const rmr_prim& q : s.prims) {
-            const float rr = q.type == RMR_PRIM_SPHERE ? std::fabs(q.r[0])
-                                                       : std::max({std::fabs(q.r[0]), std::fabs(q.r[1]), std::fabs(q.r[2])});
-            E = std::max(E, std::max({std::fabs(q.c[0]), std::fabs(q.c[1]), std::fabs(q.c[2])}) + rr);
-        }
-        P.npc_eps0 = E * 0x1p-17f + 0x1p-60f;
-        // rmr_trace.h am_normal_cert: (0.002 + 2R) 2^-20 + 2^-39 + 4 eps + 2 delta with eps the npc_eps
-        // bound at |p|_inf <= E + 0.005 (a hit's probes), in double, widened by 2^-20 for the kernel
-        // fma's rounding and rounded up to float
-        const double eps = ((double)E + 0.005) * 0x1p-17 + (double)P.npc_eps0;
-        const double k0 = (0.002 + (double)P.am_r2) * 0x1p-20 + 0x1p-39 + 4.0 * eps + 2.0 * 0.0010001;
-        P.cert_k = std::nextafter((float)(k0 * (1.0 + 0x1p-20)), INFINITY);
-    }
-    P.full_threshold = c->full_threshold;
-    {
-        int rr;
-        if ((rr = escape_params(c, P))) return rr;
-    }
+// The view, the render parameters, the env map and the buffers on top of the scene's parameters.
+int view_params(rmr_ctx* c, KParams& P) {
+    P = c->scene_kp;
+    int r;
+    if ((r = escape_params(c, P))) return r;
     {
         // primary rays' first march step from the eye (rmr_trace.h eye_map): the march point
         // fma(dir, 0, eye) is the eye itself for every finite direction unless an eye coordinate is
@@ -975,14 +614,8 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
             neg0 = neg0 || (c->view[k] == 0.0f && std::signbit(c->view[k])) || !std::isfinite(c->view[k]);
         P.eye_step = (c->cull & RMR_CULL_EYE) && !neg0 ? 1 : 0;
     }
-    P.n_mats = (int)(s.variant == RMR_VARIANT_RM3 ? s.spectral.size() : s.materials.size());
-    P.v2_begin = s.v2_begin; P.v2_end = s.v2_end;
-    P.spec_sky = s.spectral_sky;
     P.env = c->d_env; P.env_w = c->env_w; P.env_h = c->env_h;
     P.use_env = (c->params.use_env_tex != 0 && c->d_env) ? 1 : 0;
-    for (int i = 0; i < 3; i++) { P.sky[i] = s.sky[i]; P.rm2_light[i] = s.rm2.light_pos[i]; }
-    P.rm2_light_power = s.rm2.light_power;
-    P.rm2_node_id = s.rm2.node_mat_id;
     P.max_dist = c->params.max_dist; P.step_mult = c->params.step_multiply;
     P.max_steps = c->params.max_steps; P.max_bounces = c->params.max_bounces;
     P.separate_channels = c->params.separate_channels;
@@ -999,23 +632,83 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
     P.env_wf[0] = (float)c->env_w; P.env_wf[1] = (float)c->env_h;
     P.env_wf[2] = (float)(c->env_w - 1); P.env_wf[3] = (float)(c->env_h - 1);
     P.eye_xy = P.eye[0] + P.eye[1];
+    P.accum = c->d_accum;
+    P.shade_threshold = c->shade_threshold;
+    P.refill_threshold = refill_for(c->refill_threshold, c->shade_threshold);
+    return RMR_OK;
+}
+
+// One trace launch and its fold, queued: the trace on the slot's stream (or the context's), the fold on the
+// context's stream after it.
+int submit_launch(rmr_ctx* c, const KParams& P, rmr_ctx::Slot* S, bool use_jit, int grid) {
+    const hipStream_t ts = S ? S->s : c->stream;   // the trace's stream
+    bool& qdirty = S ? S->queue_dirty : c->queue_dirty;
+    if (qdirty) HIPCHK(c, hipMemsetAsync(P.queue, 0, rmr::kQueueBytes, ts));
+    qdirty = true;   // until the fold that zeroes it is queued
+    EventPair ev = get_events(c);
+    HIPCHK(c, hipEventRecord(ev.a, ts));
+    hipError_t le;
+    if (use_jit) {
+        void* args[] = {const_cast<KParams*>(&P)};
+        le = hipModuleLaunchKernel(c->jit.fn, (unsigned)grid, 1, 1, (unsigned)c->jit.block, 1, 1, 0, ts, args, nullptr);
+        if (le == hipSuccess) c->stats.jit_launches++;
+    } else {
+        le = rmr::launch_trace(P, c->scene.variant, c->accel.map_np, c->accel.has_prog, c->kernel_mode == 0, grid, ts);
+    }
+    if (le == hipSuccess) le = hipEventRecord(ev.b, ts);
+    if (le == hipSuccess && c->launch_streams >= 2) {
+        if (!c->trace_end) le = hipEventCreateWithFlags(&c->trace_end, hipEventDisableTiming);
+        if (le == hipSuccess) le = hipEventRecord(c->trace_end, ts);
+    }
+    if (S) {
+        // the context's stream waits for the trace before its fold (and before anything after it)
+        if (le == hipSuccess) le = hipEventRecord(S->done, ts);
+        if (le == hipSuccess) le = hipStreamWaitEvent(c->stream, S->done, 0);
+        if (le != hipSuccess) (void)hipStreamSynchronize(ts);   // nothing of this slot left running
+    }
+    if (le != hipSuccess) return fail(c, RMR_E_HIP, std::string("trace launch: ") + hipGetErrorString(le));
+    // (RMR_DIAG_NO_FOLD: what the fold costs the frame, a timing experiment with a wrong accumulator;
+    // the next launch then zeroes the queue with a memset)
+    if (!c->diag_no_fold) {
+        HIPCHK(c, rmr::launch_fold(P, c->stream));
+        qdirty = false;
+    }
+    if (S) {
+        HIPCHK(c, hipEventRecord(S->freed, c->stream));
+        S->in_use = true;
+    }
+    HIPCHK(c, hipEventRecord(ev.c, c->stream));
+    c->pending.push_back(ev);
+    c->stats.trace_launches++;
+    c->stats.samples += P.n_units;  // upper bound
+    return RMR_OK;
+}
+
+// Core: nspp samples over an 8x8 tile list, clipped to [x0,x1)x[y0,y1).
+int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, int x1, int y1,
+                 const float* times, uint32_t first_sample, uint32_t nspp) {
+    int r;
+    if ((r = launch_precheck(c))) return r;
+    if (tiles.empty() || nspp == 0) return RMR_OK;
+    if (!c->view_set) default_view(c);
+    const TileXY* d_tiles = nullptr;
+    if ((r = tile_list(c, tiles, &d_tiles))) return r;
+    const size_t plane = tiles.size() * 64;
+    const rmr::SamplePlan sp = rmr::plan_samples(plane, nspp, c->samp_budget, c->launch_streams);
+    const size_t chunk = sp.per_launch;
+    if (sp.slotted && c->slots.size() != (size_t)c->launch_streams) {
+        if ((r = free_slots(c)) || (r = make_slots(c))) return r;
+    }
+    KParams P;
+    if ((r = view_params(c, P))) return r;
     P.x0 = x0; P.y0 = y0; P.x1 = x1; P.y1 = y1;
     P.tiles = d_tiles;
     P.n_tiles = (int)tiles.size();
-    P.samp = c->d_samp;
-    P.accum = c->d_accum;
-    P.queue = c->d_queue;
-    P.counters = c->d_counters;
-    P.flops_static = (int32_t)s.flops_per_map();
-    P.transc_static = (int32_t)s.transc_per_map();
-    P.shade_threshold = c->shade_threshold;
-    P.refill_threshold = refill_for(c->refill_threshold, c->shade_threshold);
 
     // hipRTC specialisation for large launches (always when jit_mode == 1)
     bool use_jit = false;
     if (c->kernel_mode == 0 && c->jit_mode != 0 && !(c->jit_mode == 2 && c->jit_failed)) {
-        const uint64_t units = (uint64_t)std::min<size_t>(chunk, nspp) * plane;
-        if (c->jit_mode == 1 || units >= c->jit_min_units) {
+        if (c->jit_mode == 1 || (uint64_t)chunk * plane >= c->jit_min_units) {
             const int jr = ensure_jit(c);
             if (jr == RMR_OK) use_jit = true;
             else if (c->jit_mode == 1) return jr;
@@ -1024,7 +717,7 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
     int bpc = c->grid_per_cu;
     if (bpc <= 0) {
         if (use_jit) bpc = c->jit.blocks_per_cu;
-        else if (rmr::trace_occupancy(s.variant, c->map_np, c->has_prog, &bpc) != 0 || bpc <= 0) bpc = 4;
+        else if (rmr::trace_occupancy(c->scene.variant, c->accel.map_np, c->accel.has_prog, &bpc) != 0 || bpc <= 0) bpc = 4;
     }
     const int full_grid = c->n_cu * bpc;
     for (uint32_t k0 = 0; k0 < nspp; k0 += (uint32_t)chunk) {
@@ -1032,7 +725,7 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
         // a slot only while the previous trace is still running (something to overlap); otherwise the
         // context's stream, with no stream hop (one launch per frame, then a sync: r06t_slot_ab.log)
         rmr_ctx::Slot* S = nullptr;
-        if (slotted && c->trace_end && hipEventQuery(c->trace_end) == hipErrorNotReady) {
+        if (sp.slotted && c->trace_end && hipEventQuery(c->trace_end) == hipErrorNotReady) {
             if ((r = slot_prepare(c, plane * n, &S))) return r;
             P.samp = S->samp;
             P.queue = S->queue;
@@ -1041,7 +734,7 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
             P.samp = c->d_samp;
             P.queue = c->d_queue;
         }
-        d_times = nullptr;
+        const float* d_times = nullptr;
         if (n > 1 && (r = stage_times(c, times + k0, n, &d_times, S ? S->s : c->stream))) return r;
         c->last_samp = P.samp;
         P.nspp = n;
@@ -1049,89 +742,25 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
         P.times = d_times;
         P.time1 = times[k0];   // the seed when this launch has one sample (unit_pixel)
         P.n_units = (uint64_t)n * plane;
-        // a persistent grid no larger than the launch's work: one work chunk per wave at most (a
-        // 256x256 1-spp launch (C1) on the full grid: 0.47 ms, almost all of it waves that find no
-        // work; the per-path kernel takes one wave per 64 units as it is). Waves per block and units
-        // per chunk of the kernel that runs.
-        // A launch with less work than one chunk per wave of the grid (a tile of one sample: the
-        // reference's Graphics::Render call) takes smaller claims instead, down to small_chunk units,
-        // so its paths spread over more CUs rather than running after one another in a few waves.
-        // 480x270 tiles of one sample, same process (r06m_small_chunk.log), 64 against 128 units:
-        // Cornell-5 -21%, RM3 -7%, Mandelbulb -18%; 32 / 16 slower again. Single-bounce paths are too
-        // short for it (C1's 256x256 frame +6%): those launches keep the kernel's chunk.
-        int grid = full_grid;
-        P.chunk_units = 0;
-        if (c->kernel_mode == 0 && c->grid_per_cu <= 0) {
-            const uint64_t wpb = (uint64_t)((use_jit ? c->jit.block : 256) / 64), kchunk = use_jit ? c->jit.chunk : 128;
-            // slotted launches leave workgroups free for the previous launch's fold, which waits behind
-            // the next trace's persistent workgroups otherwise (and the slot's reuse behind that fold)
-            const int reserve = (S && c->grid_reserve == 0) ? c->slot_reserve : c->grid_reserve;
-            const uint64_t avail = (uint64_t)std::max(1, full_grid - reserve);
-            uint64_t ck = kchunk;
-            if (c->small_chunk > 0 && P.max_bounces >= 2 && P.n_units < avail * wpb * kchunk)
-                ck = std::min(kchunk, std::max<uint64_t>((uint64_t)c->small_chunk, (P.n_units + avail * wpb - 1) / (avail * wpb)));
-            if (ck < kchunk) P.chunk_units = (uint32_t)ck;
-            const uint64_t want = (P.n_units + wpb * ck - 1) / (wpb * ck);
-            grid = (int)std::max<uint64_t>(1, std::min<uint64_t>(avail, want));
-        }
+        // slotted launches leave workgroups free for the previous launch's fold, which waits behind
+        // the next trace's persistent workgroups otherwise (and the slot's reuse behind that fold)
+        const int reserve = (S && c->grid_reserve == 0) ? c->slot_reserve : c->grid_reserve;
+        const rmr::GridPlan gp = rmr::plan_grid(P.n_units, full_grid, reserve, (use_jit ? c->jit.block : 256) / 64,
+                                                use_jit ? c->jit.chunk : 128, c->small_chunk, P.max_bounces,
+                                                c->grid_per_cu, c->kernel_mode);
+        P.chunk_units = gp.chunk_units;
         // tuned shading batch size of the kernel that runs (measured: C2 +2% at 20; the Mandelbulb
         // and the cached BVH map -1..2%)
         if (c->shade_auto) {
             P.shade_threshold = use_jit ? c->jit.shade_t : 16;
             P.refill_threshold = refill_for(c->refill_threshold, P.shade_threshold);
         }
-        const hipStream_t ts = S ? S->s : c->stream;   // the trace's stream
-        bool& qdirty = S ? S->queue_dirty : c->queue_dirty;
-        if (qdirty) HIPCHK(c, hipMemsetAsync(P.queue, 0, rmr::kQueueBytes, ts));
-        qdirty = true;   // until the fold that zeroes it is queued
-        EventPair ev = get_events(c);
-        HIPCHK(c, hipEventRecord(ev.a, ts));
-        hipError_t le;
-        if (use_jit) {
-            void* args[] = {&P};
-            le = hipModuleLaunchKernel(c->jit.fn, (unsigned)grid, 1, 1, (unsigned)c->jit.block, 1, 1, 0, ts, args, nullptr);
-            if (le == hipSuccess) c->stats.jit_launches++;
-        } else {
-            le = rmr::launch_trace(P, s.variant, c->map_np, c->has_prog, c->kernel_mode == 0, grid, ts);
-        }
-        if (le == hipSuccess) le = hipEventRecord(ev.b, ts);
-        if (le == hipSuccess && c->launch_streams >= 2) {
-            if (!c->trace_end) le = hipEventCreateWithFlags(&c->trace_end, hipEventDisableTiming);
-            if (le == hipSuccess) le = hipEventRecord(c->trace_end, ts);
-        }
-        if (S) {
-            // the context's stream waits for the trace before its fold (and before anything after it)
-            if (le == hipSuccess) le = hipEventRecord(S->done, ts);
-            if (le == hipSuccess) le = hipStreamWaitEvent(c->stream, S->done, 0);
-            if (le != hipSuccess) (void)hipStreamSynchronize(ts);   // nothing of this slot left running
-        }
-        if (le != hipSuccess) return fail(c, RMR_E_HIP, std::string("trace launch: ") + hipGetErrorString(le));
-        // (RMR_DIAG_NO_FOLD: what the fold costs the frame, a timing experiment with a wrong accumulator;
-        // the next launch then zeroes the queue with a memset)
-        if (!c->diag_no_fold) {
-            HIPCHK(c, rmr::launch_fold(P, c->stream));
-            qdirty = false;
-        }
-        if (S) {
-            HIPCHK(c, hipEventRecord(S->freed, c->stream));
-            S->in_use = true;
-        }
-        HIPCHK(c, hipEventRecord(ev.c, c->stream));
-        c->pending.push_back(ev);
-        c->stats.trace_launches++;
-        c->stats.samples += (uint64_t)n * plane;  // upper bound; exact count below
+        if ((r = submit_launch(c, P, S, use_jit, gp.grid))) return r;
     }
     return RMR_OK;
 }
 
-std::vector<TileXY> rect_tiles(int x0, int y0, int x1, int y1) {
-    std::vector<TileXY> t;
-    for (int y = y0; y < y1; y += 8)
-        for (int x = x0; x < x1; x += 8) t.push_back(TileXY{x, y});
-    return t;
-}
-
-int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+using rmr::rect_tiles;
 
 bool batching_on(const rmr_ctx* c) {
     return c->call_batching > 0 || (c->call_batching < 0 && c->own_stream && !c->accum_external);
@@ -1141,45 +770,15 @@ bool batching_on(const rmr_ctx* c) {
 constexpr uint64_t kDeferredUnitsMax = (uint64_t)1 << 28;
 constexpr size_t kDeferredRectsMax = 4096;
 
-// Launch the deferred one-sample calls. Rects holding the same samples (same first index, same seeds)
-// whose union is a rectangle go out as one launch over that rectangle (the reference's 4x4 grid, fixed
-// or progressive: the whole grid in one launch); any other rect goes out as a launch of its own (a
-// launch clips to one rect: a tile of a rect whose edge is off the 8-pixel grid reaches into its
-// neighbour). Bitwise equal to the calls made one by one: each pixel gets the same samples with the same
-// seeds in the same order, and the held rects are disjoint (rmr_render flushes before an overlapping
-// call).
+// Launch the deferred one-sample calls, grouped by accel.hpp group_deferred.
 int flush_calls(rmr_ctx* c) {
     if (c->deferred.empty()) return RMR_OK;
-    std::vector<rmr_ctx::Deferred> d;
+    std::vector<rmr::DeferredCall> d;
     d.swap(c->deferred);
     c->deferred_units = 0;
-    std::vector<char> done(d.size(), 0);
-    for (size_t i = 0; i < d.size(); i++) {
-        if (done[i]) continue;
-        std::vector<size_t> grp;
-        int bx0 = d[i].x0, by0 = d[i].y0, bx1 = d[i].x1, by1 = d[i].y1;
-        uint64_t area = 0;
-        for (size_t j = i; j < d.size(); j++) {
-            if (done[j] || d[j].s0 != d[i].s0 || d[j].times.size() != d[i].times.size() ||
-                std::memcmp(d[j].times.data(), d[i].times.data(), d[i].times.size() * sizeof(float)) != 0)
-                continue;
-            grp.push_back(j);
-            done[j] = 1;
-            bx0 = std::min(bx0, d[j].x0); by0 = std::min(by0, d[j].y0);
-            bx1 = std::max(bx1, d[j].x1); by1 = std::max(by1, d[j].y1);
-            area += (uint64_t)(d[j].x1 - d[j].x0) * (uint64_t)(d[j].y1 - d[j].y0);
-        }
-        const uint32_t n = (uint32_t)d[i].times.size();
-        if (area == (uint64_t)(bx1 - bx0) * (uint64_t)(by1 - by0)) {   // disjoint rects filling their box
-            const int r = render_tiles(c, rect_tiles(bx0, by0, bx1, by1), bx0, by0, bx1, by1, d[i].times.data(), d[i].s0, n);
-            if (r) return r;
-            continue;
-        }
-        for (size_t j : grp) {
-            const int r = render_tiles(c, rect_tiles(d[j].x0, d[j].y0, d[j].x1, d[j].y1), d[j].x0, d[j].y0, d[j].x1,
-                                       d[j].y1, d[j].times.data(), d[j].s0, n);
-            if (r) return r;
-        }
+    for (const rmr::CallLaunch& l : rmr::group_deferred(d)) {
+        const int r = render_tiles(c, rect_tiles(l.x0, l.y0, l.x1, l.y1), l.x0, l.y0, l.x1, l.y1, l.times, l.s0, l.n);
+        if (r) return r;
     }
     return RMR_OK;
 }
@@ -1350,8 +949,7 @@ int rmr_load_scene_json(rmr_ctx* c, int variant, const char* json, size_t len) {
     RMR_FLUSH(c);
     try {
         CompiledScene s = rmr::compile_scene(std::string(json, len), variant);
-        int r = validate_scene(c, s);
-        if (r) return r;
+        if (const char* bad = rmr::validate_scene(s)) return fail(c, RMR_E_SCENE, bad);
         c->scene = std::move(s);
     } catch (const rmr::SceneError& e) {
         return fail(c, RMR_E_SCENE, e.what());
@@ -1371,8 +969,7 @@ int rmr_load_scene_tables(rmr_ctx* c, const rmr_scene* s) {
         return fail(c, RMR_E_INVALID, "table sizes out of range");
     CompiledScene cs;
     cs.from_tables(*s);
-    int r = validate_scene(c, cs);
-    if (r) return r;
+    if (const char* bad = rmr::validate_scene(cs)) return fail(c, RMR_E_SCENE, bad);
     c->scene = std::move(cs);
     HIPCHK(c, hipSetDevice(c->device));
     return upload_scene(c);
@@ -1413,17 +1010,15 @@ int rmr_reload(rmr_ctx* c) {
 int rmr_render(rmr_ctx* c, float time, float min_x, float min_y, float max_x, float max_y, uint32_t current_sample) {
     if (!c) return RMR_E_INVALID;
     // pix >= bounds.xy && pix < bounds.zw for integer pix (RM1:572) <=> pix in [ceil(min), ceil(max))
-    const int x0 = clampi((int)std::ceil(min_x), 0, c->W), y0 = clampi((int)std::ceil(min_y), 0, c->H);
-    const int x1 = clampi((int)std::ceil(max_x), 0, c->W), y1 = clampi((int)std::ceil(max_y), 0, c->H);
-    if (x1 <= x0 || y1 <= y0) return RMR_OK;
+    int x0 = (int)std::ceil(min_x), y0 = (int)std::ceil(min_y), x1 = (int)std::ceil(max_x), y1 = (int)std::ceil(max_y);
+    if (!rmr::clamp_rect(c->W, c->H, x0, y0, x1, y1)) return RMR_OK;
     if (!batching_on(c)) {
         RMR_FLUSH(c);
         return render_tiles(c, rect_tiles(x0, y0, x1, y1), x0, y0, x1, y1, &time, current_sample, 1);
     }
     // deferred (rmr_set_call_batching): the errors the launch would give now come at the call
-    if (!c->scene_loaded) return fail(c, RMR_E_STATE, "no scene loaded (call rmr_load_scene_json / rmr_load_builtin_scene)");
-    if (c->params.use_env_tex && !c->d_env) return fail(c, RMR_E_STATE, "useEnvTex != 0 but no env map (rmr_set_env_map)");
-    rmr_ctx::Deferred* same = nullptr;
+    if (const int r = launch_precheck(c)) return r;
+    rmr::DeferredCall* same = nullptr;
     bool overlap = false;
     for (auto& e : c->deferred) {
         if (e.x0 == x0 && e.y0 == y0 && e.x1 == x1 && e.y1 == y1) same = &e;
@@ -1435,7 +1030,7 @@ int rmr_render(rmr_ctx* c, float time, float min_x, float min_y, float max_x, fl
         same = nullptr;
     }
     if (same) same->times.push_back(time);
-    else c->deferred.push_back(rmr_ctx::Deferred{x0, y0, x1, y1, current_sample, std::vector<float>(1, time)});
+    else c->deferred.push_back(rmr::DeferredCall{x0, y0, x1, y1, current_sample, std::vector<float>(1, time)});
     c->deferred_units += (uint64_t)((x1 - x0 + 7) / 8) * ((y1 - y0 + 7) / 8) * 64;
     if (c->deferred_units >= kDeferredUnitsMax) RMR_FLUSH(c);
     return RMR_OK;
@@ -1462,9 +1057,7 @@ int rmr_get_launch_streams(const rmr_ctx* c) { return c ? c->launch_streams : -1
 int rmr_render_spp(rmr_ctx* c, const float* times, int x0, int y0, int x1, int y1, uint32_t first_sample, uint32_t nspp) {
     if (!c || (!times && nspp)) return RMR_E_INVALID;
     RMR_FLUSH(c);
-    x0 = clampi(x0, 0, c->W); x1 = clampi(x1, 0, c->W);
-    y0 = clampi(y0, 0, c->H); y1 = clampi(y1, 0, c->H);
-    if (x1 <= x0 || y1 <= y0) return RMR_OK;
+    if (!rmr::clamp_rect(c->W, c->H, x0, y0, x1, y1)) return RMR_OK;
     return render_tiles(c, rect_tiles(x0, y0, x1, y1), x0, y0, x1, y1, times, first_sample, nspp);
 }
 
@@ -1484,13 +1077,7 @@ int rmr_render_tiles(rmr_ctx* c, const float* times, const int32_t* tiles_xy, in
     std::sort(seen.begin(), seen.end());
     if (std::adjacent_find(seen.begin(), seen.end()) != seen.end())
         return fail(c, RMR_E_INVALID, "duplicate tile in rmr_render_tiles");
-    std::vector<TileXY> t;
-    t.reserve((size_t)n_tiles * (tile_size / 8) * (tile_size / 8));
-    for (int i = 0; i < n_tiles; i++) {
-        const int bx = tiles_xy[2 * i] * tile_size, by = tiles_xy[2 * i + 1] * tile_size;
-        for (int y = by; y < std::min(by + tile_size, c->H); y += 8)
-            for (int x = bx; x < std::min(bx + tile_size, c->W); x += 8) t.push_back(TileXY{x, y});
-    }
+    const std::vector<TileXY> t = rmr::expand_tiles(tiles_xy, n_tiles, tile_size, c->W, c->H);
     if (t.empty()) return RMR_OK;
     return render_tiles(c, t, 0, 0, c->W, c->H, times, first_sample, nspp);
 }
@@ -1790,27 +1377,17 @@ int rmr_jit_compile_scene(int variant, const char* json, size_t len, char* log, 
     std::string lg;
     try {
         CompiledScene s = (json && len) ? rmr::compile_scene(std::string(json, len), variant) : rmr::builtin_scene(variant);
-        // the kernel class as a context picks it: node-program materials by upload_scene's rule
-        // (shading_kinds), the cache's primitives per lane and the sphere-only candidates as
-        // ensure_jit for BVH scenes, whose full map() runs through the candidate grid (assumed built,
-        // as it is unless the grid would exceed 2^31 cells)
-        const bool prog = any_program(shading_kinds(s));
-        bool simple = true;
-        for (const auto& q : s.prims) simple = simple && (q.type == RMR_PRIM_SPHERE || q.type == RMR_PRIM_BOX);
-        const bool bvh = simple && s.prims.size() > (size_t)kMaxLoopPrims;
-        bool npc_spheres = bvh;
-        if (bvh) {
-            std::vector<char> is_large;
-            float extent = 0.0f;
-            (void)bvh_items(s, is_large, extent);
-            for (size_t i = 0; i < s.prims.size(); i++)
-                npc_spheres = npc_spheres && (is_large[i] || s.prims[i].type == RMR_PRIM_SPHERE);
-        }
+        // the kernel class as a context picks it (ensure_jit), with the candidate grid of a BVH scene
+        // taken as built (as it is unless it would exceed 2^31 cells) rather than built here
+        rmr::AccelOptions opt;
+        opt.grid = false;
+        const rmr::SceneAccel a = rmr::build_scene_accel(s, opt);
+        const rmr::CacheFacts cache = rmr::cache_kernel_facts(a, true);
         std::vector<char> code;
         std::string key;
         const bool ok = rmr::jit_compile(
-            rmr::jit_source(s, prog, true, RMR_CULL_ESCAPE | RMR_CULL_NPC | RMR_CULL_APPROX | RMR_CULL_EYE, nullptr,
-                            bvh ? 1 : 2, npc_spheres),
+            rmr::jit_source(s, a.has_prog, true, RMR_CULL_ESCAPE | RMR_CULL_NPC | RMR_CULL_APPROX | RMR_CULL_EYE, nullptr,
+                            cache.npc_k, cache.npc_spheres),
             code, key, lg);
         if (log && loglen) std::snprintf(log, loglen, "%s", ok ? key.c_str() : lg.c_str());
         return ok ? RMR_OK : RMR_E_HIP;
@@ -1856,9 +1433,7 @@ int rmr_set_grid_reserve(rmr_ctx* c, int blocks) {
 int rmr_trace_samples(rmr_ctx* c, const float* times, int x0, int y0, int x1, int y1, uint32_t nspp, float* out) {
     if (!c || !times || !out) return RMR_E_INVALID;
     RMR_FLUSH(c);
-    x0 = clampi(x0, 0, c->W); x1 = clampi(x1, 0, c->W);
-    y0 = clampi(y0, 0, c->H); y1 = clampi(y1, 0, c->H);
-    if (x1 <= x0 || y1 <= y0 || nspp == 0) return RMR_OK;
+    if (!rmr::clamp_rect(c->W, c->H, x0, y0, x1, y1) || nspp == 0) return RMR_OK;
     std::vector<TileXY> tiles = rect_tiles(x0, y0, x1, y1);
     const size_t saved_budget = c->samp_budget;
     const size_t plane = tiles.size() * 64;

@@ -17,9 +17,10 @@
 
 // Environment switches (RMR_GRID, RMR_JIT_OPTS, RMR_JIT_BAKE, ...: A/B experiments, tools/) exist only
 // in the diagnostic build librmr_diag.so (`make diag`, -DRMR_DIAG=1). The release librmr.so reads no
-// environment variable but RMR_JIT_CACHE (and HOME for its default): a drop-in renderer's results and
-// kernels do not depend on an inherited environment. RMR_ENV("X") is nullptr there, and the name
-// does not reach the binary.
+// environment variable but RMR_JIT_CACHE (and HOME for its default) and GPU_MAX_HW_QUEUES (rmr_create:
+// the number of launch slots): a drop-in renderer's results and kernels do not depend on an inherited
+// environment. RMR_ENV("X") is nullptr there, and the name does not reach the binary. Only rmr_api.cpp
+// and rmr_jit.cpp, the two files built twice, use RMR_ENV; other units take the switches as arguments.
 #ifndef RMR_DIAG
 #define RMR_DIAG 0
 #endif

@@ -18,7 +18,7 @@ SPHERE, BOX = 1.0, 2.0
 
 
 def _prims(scene):
-    """Leaf-order rows (the large ground box first, as rmr_api.cpp upload_bvh orders it)."""
+    """Leaf-order rows (the large ground box first, as accel.cpp build_bvh orders it)."""
     with open(os.path.join(SCENES, scene)) as f:
         sc = json.load(f)
     rows = []
