@@ -263,7 +263,11 @@ int rmr_jit_compile_scene(int variant, const char* json, size_t len, char* log, 
 int rmr_set_tuning(rmr_ctx* ctx, int shade_threshold, int grid_per_cu, long long samp_budget_bytes);
 /* (shade_threshold bits 8..15, when non-zero, set the refill threshold separately: idle lanes a
  * wave collects before it fetches new units; default (and when zero) = half the shading
- * threshold, at least 2.) */
+ * threshold, at least 2. Bits 0..7 zero leave the batch size as it is. With bit 23 set the value
+ * also carries the settings of the kernels with lane slots — a second path per lane waiting in LDS,
+ * RM1's certified sphere/box kernels: bits 16..22 the finished marches a wave collects before it
+ * parks them (0: the kernel class's default; 127: the schedule off), bits 24..30 the waiting events
+ * per shading batch (0: the class's default); with bits 0..15 zero it sets nothing else.) */
 /* Persistent-grid reserve: the trace launch leaves `blocks` workgroups of its occupancy grid
  * unlaunched (default 0; the grid stays >= 1 workgroup). For two contexts that alternate frames on
  * one GPU (multi_gpu.FrameRenderer): a persistent trace kernel holds every slot it gets until its

@@ -315,6 +315,17 @@ static void check_plan(std::mt19937_64& rng) {
     check_grid((uint64_t)plane4k * 256, 2048, 0, 4, 128, 64, 16, 0, 0);
     g = plan_grid((uint64_t)plane4k * 256, 2048, 0, 4, 128, 64, 16, 0, 0);
     CHECK(g.grid == 2048 && g.chunk_units == 0);
+    // the lane-slot kernels: 6 workgroups per CU (their LDS; rmr_api.cpp takes the count from the loaded
+    // code object's occupancy) and 64-unit chunks, so 256 CUs give the same 1,536-block grid
+    check_grid((uint64_t)1920 * 1080 * 64, 256 * 6, 0, 4, 64, 64, 4, 0, 0);
+    g = plan_grid((uint64_t)1920 * 1080 * 64, 256 * 6, 0, 4, 64, 64, 4, 0, 0);   // C2: the whole grid, whole chunks
+    CHECK(g.grid == 1536 && g.chunk_units == 0);
+    g = plan_grid(130560, 256 * 6, 0, 4, 64, 64, 16, 0, 0);   // 480x270 x 1 spp: one 64-unit chunk per wave
+    CHECK(g.grid == 510 && g.chunk_units == 0);
+    g = plan_grid(64 * 64 * 4, 256 * 6, 1 << 20, 4, 64, 64, 4, 0, 0);   // the grid reserved down to one block
+    CHECK(g.grid == 1 && g.chunk_units == 0);
+    g = plan_grid(64, 256 * 6, 0, 4, 64, 64, 4, 0, 0);   // one tile: a single claim
+    CHECK(g.grid == 1 && g.chunk_units == 0);
     // tiles
     std::vector<TileXY> t = rect_tiles(3, 5, 20, 14);
     CHECK(t.size() == 6 && t[0].x == 3 && t[0].y == 5 && t[2].x == 19 && t[3].x == 3 && t[3].y == 13);

@@ -140,6 +140,12 @@ struct rmr_ctx {
     // Cornell-5 -0.4%, RM3 -1.2%, default -2% against 2; Mandelbulb T = 8: 4 best); 0 = the shading
     // threshold; refills are cheap with the LDS chunk rays
     int refill_threshold = -1;
+    // lane-slot kernels (rmr_trace.h RMR_LANE_SLOTS): -1 the kernel class's default, 0 off, 1 on where
+    // the class can run it; park / batch thresholds (0: the class's, rmr_jit.hpp JitFacts). Their
+    // refill threshold follows the park threshold as the others' follows the shading threshold
+    int lane_slots = -1;
+    int park_threshold = 0, slot_threshold = 0;
+    int jit_slots = -1;         // the request `jit` was specialised with (slots_request)
     // nearest-primitive cache: 40 lanes per full map() batch, or once waiting lanes >= cache-served ones
     // (R = 8; csg256 with the candidate grid: 15.7 -> 14.8 ms per 4 spp against R = 2)
     int full_threshold = 40 | (8 << 8);
@@ -334,9 +340,20 @@ int upload_scene(rmr_ctx* c) {
     return RMR_OK;
 }
 
+// The lane-slot request of a launch with the context's parameters: the schedule covers paths with one
+// channel pass and the constant sky (an event's record has no channel and a miss is shaded where it is
+// found), and packs the bounce count above bit 9 of a word; other launches run the class's kernel without it.
+int slots_request(const rmr_ctx* c) {
+    if (c->params.separate_channels != 0 || c->params.use_env_tex != 0 || c->params.max_bounces >= (1 << 21)) return 0;
+    return c->lane_slots;
+}
+
 // Compile (or fetch from the cache) and load the specialised trace kernel of the loaded scene.
 int ensure_jit(rmr_ctx* c) {
-    if (c->jit_ready) return RMR_OK;
+    const int slots = slots_request(c);
+    if (c->jit_ready && c->jit_slots == slots) return RMR_OK;
+    c->jit_ready = false;
+    c->jit_slots = slots;
     // animation: same structure as the last specialised scene, different numbers -> the primitives
     // that changed since the kernel's baked values become loads ("live"), the others stay literals:
     // one compile when the motion starts, then the same kernel every frame
@@ -353,7 +370,7 @@ int ensure_jit(rmr_ctx* c) {
     const rmr::CacheFacts cache = rmr::cache_kernel_facts(c->accel, c->accel.grid_on);
     rmr::JitFacts facts;
     const std::string src = rmr::jit_source(c->scene, c->accel.has_prog, true, c->cull, &c->jit_live,
-                                            c->npc_ksel ? c->npc_ksel : cache.npc_k, cache.npc_spheres, &facts);
+                                            c->npc_ksel ? c->npc_ksel : cache.npc_k, cache.npc_spheres, &facts, slots);
     std::vector<char> code;
     std::string key, log;
     std::vector<std::string> opts;
@@ -395,6 +412,9 @@ int ensure_jit(rmr_ctx* c) {
     // certified sphere/box kernels at 7 waves 20 (Cornell-5 1080p 64 spp: 47.17 -> 46.63 ms; 18: 46.77,
     // 14: 47.92)
     k.shade_t = facts.shade_t();
+    k.slots = facts.slots;
+    k.park_t = facts.park_t();
+    k.slot_t = facts.slot_t();
     c->jit_loaded.push_back(k);
     c->jit = k;
     c->jit_ready = true;
@@ -755,6 +775,11 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
             P.shade_threshold = use_jit ? c->jit.shade_t : 16;
             P.refill_threshold = refill_for(c->refill_threshold, P.shade_threshold);
         }
+        if (use_jit && c->jit.slots) {
+            const int park = c->park_threshold > 0 ? c->park_threshold : c->jit.park_t;
+            P.shade_threshold = park | ((c->slot_threshold > 0 ? c->slot_threshold : c->jit.slot_t) << 8);
+            P.refill_threshold = refill_for(c->refill_threshold, park);
+        }
         if ((r = submit_launch(c, P, S, use_jit, gp.grid))) return r;
     }
     return RMR_OK;
@@ -844,6 +869,9 @@ int rmr_create(rmr_ctx** out, int device) {
         c->shade_auto = false;
     }
     if (const char* e = RMR_ENV("RMR_REFILL_T")) c->refill_threshold = std::max(0, std::atoi(e));
+    if (const char* e = RMR_ENV("RMR_LANE_SLOTS")) c->lane_slots = std::atoi(e) != 0;
+    if (const char* e = RMR_ENV("RMR_PARK_T")) c->park_threshold = std::max(0, std::min(64, std::atoi(e)));
+    if (const char* e = RMR_ENV("RMR_SLOT_T")) c->slot_threshold = std::max(0, std::min(64, std::atoi(e)));
     if (const char* e = RMR_ENV("RMR_ESC")) if (std::atoi(e) == 0) c->cull &= ~RMR_CULL_ESCAPE;
     if (const char* e = RMR_ENV("RMR_NPC")) if (std::atoi(e) == 0) c->cull &= ~RMR_CULL_NPC;
     if (const char* e = RMR_ENV("RMR_JIT_APPROX")) if (std::atoi(e) == 0) c->cull &= ~RMR_CULL_APPROX;
@@ -1412,10 +1440,21 @@ int rmr_set_tuning(rmr_ctx* c, int shade_threshold, int grid_per_cu, long long s
     if (!c) return RMR_E_INVALID;
     RMR_FLUSH(c);
     if (shade_threshold > 0) {
-        c->shade_threshold = std::max(1, std::min(64, shade_threshold & 0xff));
-        c->shade_auto = false;
+        if (shade_threshold & 0xff) {
+            c->shade_threshold = std::max(1, std::min(64, shade_threshold & 0xff));
+            c->shade_auto = false;
+        }
         const int tr = (shade_threshold >> 8) & 0xff;
-        c->refill_threshold = tr ? std::min(64, tr) : -1;   // unset: half the shading threshold
+        if ((shade_threshold & 0xffff) || !(shade_threshold & (1 << 23)))
+            c->refill_threshold = tr ? std::min(64, tr) : -1;   // unset: half the shading threshold
+        // lane-slot kernels, when bit 23 is set: bits 16..22 the park threshold (127: the schedule off),
+        // 24..30 the batch threshold (0: the kernel class's)
+        if (shade_threshold & (1 << 23)) {
+            const int park = (shade_threshold >> 16) & 0x7f;
+            c->lane_slots = park == 127 ? 0 : -1;
+            c->park_threshold = park == 127 ? 0 : std::min(64, park);
+            c->slot_threshold = std::min(64, (shade_threshold >> 24) & 0x7f);
+        }
     }
     if (grid_per_cu >= 0) c->grid_per_cu = grid_per_cu;
     if (samp_budget_bytes > 0) c->samp_budget = (size_t)samp_budget_bytes;

@@ -41,6 +41,8 @@ struct JitKernel {
     int block = 256;            // workgroup size
     int chunk = 128;            // units a wave takes from the work queue at a time (rmr_trace.h
                                 // RMR_CHUNK; the nearest-primitive cache kernels: RMR_CHUNK_CACHE)
+    bool slots = false;         // the lane-slot schedule (rmr_trace.h RMR_LANE_SLOTS)
+    int park_t = 0, slot_t = 0; // its default thresholds (JitFacts)
 };
 
 // What jit_source decided about the kernel class (the launch settings follow from these, not from
@@ -49,7 +51,14 @@ struct JitKernel {
 struct JitFacts {
     int variant = 0;
     bool cache = false, general = false, prog = false, cert = false;
-    int chunk() const { return cache ? 64 : 128; }   // rmr_trace.h RMR_CHUNK_CACHE / RMR_CHUNK
+    // the lane-slot schedule (rmr_trace.h RMR_LANE_SLOTS): the class can run it (RM1's certified
+    // sphere/box kernels) / this source has it on
+    bool slots_ok = false, slots = false;
+    int chunk() const { return (cache || slots) ? 64 : 128; }   // rmr_trace.h RMR_CHUNK_CACHE / RMR_CHUNK_SLOTS / RMR_CHUNK
+    // lane slots: finished marches per park step, slot events per shading batch (Cornell-5 1080p 64 spp:
+    // flat over 8-10 / 28-40, +10% and more outside 6-12 / 24-48)
+    int park_t() const { return 8; }
+    int slot_t() const { return 32; }
     // default shading batch: general maps without material programs, whose map() dwarfs the shading
     // (the Mandelbulb): 10 (C3: 8 / 12 within 0.6%, 6 / 16 +3%, profiles/r05_c3_shade_ab.log); node-program materials, the cache kernels and the certified
     // sphere/box kernels (their batches run the certified probes): 20; otherwise 16 (rmr_api.cpp)
@@ -71,9 +80,10 @@ struct JitFacts {
 // npc_spheres: every primitive the candidate grid lists is a sphere (RMR_NPC_SPHERES: the full
 // map's candidates take the sphere distance, the same value as the general form for a sphere).
 // facts (optional): the kernel class, for the launch settings.
+// slots: the lane-slot schedule where the class can run it: 1 on, 0 off, -1 the class's default.
 std::string jit_source(const CompiledScene& s, bool prog, bool bake = true, int cull = 7,
                        const std::vector<char>* live = nullptr, int npc_k = 2, bool npc_spheres = false,
-                       JitFacts* facts = nullptr);
+                       JitFacts* facts = nullptr, int slots = -1);
 // Compile `src` for gfx950 (no GPU needed). Code-object cache: in-process, then the directory
 // $RMR_JIT_CACHE (default $HOME/.cache/rmr-jit). Returns false with the compiler log in `log`.
 // opts: further compiler options, part of the key (the instrumented build of rmr_set_instrument:

@@ -1389,8 +1389,12 @@ RMR_D bool trace_prologue(const KParams& P, Lane& L, V3 dir, float te_pre = __bu
 }
 
 // unit -> (sample k, pixel); false if the pixel is outside the launch's clip rect
+// (OPQ, lane-slot kernels: the divisor behind an empty asm, so that the division's reciprocal is
+// computed where it is used, per chunk, instead of living in a VGPR for the whole launch)
+template <bool OPQ = false>
 RMR_D bool unit_pixel(const KParams& P, uint32_t u, int& px, int& py, float& time) {
-    const uint32_t per_k = (uint32_t)P.n_tiles * 64u;
+    uint32_t per_k = (uint32_t)P.n_tiles * 64u;
+    if constexpr (OPQ) __asm__ volatile("" : "+s"(per_k));
     const uint32_t k = u / per_k;
     const uint32_t rem = u - k * per_k;
     const int tile = (int)(rem >> 6), lane = (int)(rem & 63u);
@@ -1544,12 +1548,12 @@ RMR_D void begin_trace(const KParams& P, Lane& L, uint32_t u, bool fresh) {
 // rand() calls) and (gid.x + time, gid.y + time, time, escape bound of the primary ray or NaN
 // outside the clip rect).
 struct ChunkRay { float4 a, b; };
-template <bool HO>
+template <bool HO, bool OPQ = false>
 RMR_D ChunkRay chunk_ray(const KParams& P, uint32_t u) {
     int px, py;
     float time, rc = 0.0f;
     ChunkRay r;
-    const bool in_rect = unit_pixel(P, u, px, py, time);
+    const bool in_rect = unit_pixel<OPQ>(P, u, px, py, time);
     V3 dir = v3s(0.0f);
     float te = __builtin_nanf("");
     if (in_rect) {
@@ -1598,7 +1602,8 @@ RMR_D void begin_unit(const KParams& P, Lane& L, uint32_t u, float4 a, float4 b)
 // p (cache kernels with one cached primitive): the march point, for the same certificate from the
 // cache's bound — a hit whose six probes all stay within the cached primitive's validity (each probe
 // would be served by the cache, F_w(probe) < cs - delta - eps) parks in PH_HIT with ctr = -1 too
-template <bool HO, bool CACHE = false>
+// PACKW (lane-slot kernels): the certified primitive rides in the hit's ctr = -1 - w, no L.cw
+template <bool HO, bool CACHE = false, bool PACKW = false>
 RMR_D void march_update(const KParams& P, Lane& L, V2 m, int w = 0, bool cert = false, V3 p = V3{0.0f, 0.0f, 0.0f}) {
     if constexpr (HO && !CACHE) {   // (cache kernels: A/B neutral-negative)
         // HO kernels (no shadow rays): the same state transitions as below as per-lane selects
@@ -1614,9 +1619,9 @@ RMR_D void march_update(const KParams& P, Lane& L, V2 m, int w = 0, bool cert = 
         L.t = tf;   // (o stays the ray origin: the shading batch writes the point, init_probe)
         L.e = v3(probe ? 0.001f : L.e.x, probe ? 0.0f : L.e.y, probe ? 0.0f : L.e.z);
         L.mid = hit ? m.y : (miss ? -1.0f : L.mid);
-        L.ctr = hit ? (cert ? -1 : 0) : cn;
+        L.ctr = hit ? (cert ? (PACKW ? -1 - w : -1) : 0) : cn;
         L.phase = hit ? (cert ? PH_HIT : PH_NORMAL) : (miss ? PH_MISS : L.phase);
-        L.cw = cert ? w : L.cw;
+        if constexpr (!PACKW) L.cw = cert ? w : L.cw;
         return;
     }
     const bool shadow = (L.phase == PH_SHADOW);
@@ -1725,13 +1730,15 @@ RMR_D void normal_update(Lane& L, float m) {
 // sd_sphere at points without NaN — and each owner gathers its six values back with ds_bpermute:
 // nrm = (m0 - m1, m2 - m3, m4 - m5), normalised in shade() as every normal.
 // Runs with every lane of the wave active (bpermute reads the owners' registers).
+// (AT, lane-slot kernels: L is a waiting path's event from its LDS slot, whose o is the hit point already)
+template <bool AT = false>
 RMR_D void cert_normals(const KParams& P, Lane& L, bool mine, uint64_t cm, int* tab, const float4* dtab) {
     const int lane = (int)__lane_id();
     const int n = __popcll(cm);
     const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u));
     if (mine) tab[rank] = lane;
     __builtin_amdgcn_wave_barrier();
-    const V3 hp = vfma(L.d, L.t, L.o);   // the hit point (HO: written at the shading batch, same bits)
+    const V3 hp = AT ? L.o : vfma(L.d, L.t, L.o);   // the hit point (HO: written at the shading batch, same bits)
     const int total = 6 * n;
     float v[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     for (int g0 = 0; g0 < total; g0 += 64) {   // wave-uniform
@@ -2195,6 +2202,89 @@ RMR_D void cold_get(float (*s)[256], int t, Lane& L) {
     L.bounces = cb >> 8;
 }
 
+// Lane slots (RMR_LANE_SLOTS, trace_main): a lane's second path waits in a lane-private LDS slot, one
+// word per lane per field as cold_put's (conflict-free), either as an event awaiting its shading batch
+// or as the next ray ready to march. The fields a path keeps through both states share their words:
+//   word   event (slot_put_event)                ray (slot_put_ray)
+//   0-2    hit point fma(d, t, o)                origin
+//   3-5    getNormal differences (uncertified)   direction
+//   6-8    throughput                            throughput
+//   9      rc (RNG chain)                        rc
+//   10-12  gxt, gyt, unit                        (kept)
+//   13     bounces << 9 | cw << 1 | certified   bounces
+//   14     -                                     escape bound
+//   15     material id                           -
+//   16     the unit of the path the lane marches in registers (read where its sample is stored or
+//          its event parked: a register less in the map loop and across the batch)
+// RM1 without separateChannels and without node-program materials only (chan = -1; inside = false:
+// rm1_after_material's ni stays 0; no RM2 / RM3 fields), inline maps (cw < 256).
+constexpr int kSlotWords = 17;
+RMR_D void slot_put_event(float (*s)[256], int t, const Lane& L, V3 hp) {
+    s[0][t] = hp.x; s[1][t] = hp.y; s[2][t] = hp.z;
+    if (L.ctr >= 0) { s[3][t] = L.nrm.x; s[4][t] = L.nrm.y; s[5][t] = L.nrm.z; }
+    s[6][t] = L.color.x; s[7][t] = L.color.y; s[8][t] = L.color.z;
+    s[9][t] = L.rc;
+    s[10][t] = L.gxt; s[11][t] = L.gyt;
+    s[12][t] = s[16][t];
+    // (ctr = -1 - cw of a certified hit, march_update PACKW; 6 after an uncertified hit's probes)
+    s[13][t] = __int_as_float((L.bounces << 9) | (L.ctr < 0 ? (((-1 - L.ctr) & 0xff) << 1) | 1 : 0));
+    s[15][t] = L.mid;
+}
+// the event as a lane in PH_HIT before its shading (o = the hit point, as the in-register batch sets it)
+RMR_D void slot_get_event(float (*s)[256], int t, Lane& E) {
+    E.o = v3(s[0][t], s[1][t], s[2][t]);
+    E.nrm = v3(s[3][t], s[4][t], s[5][t]);
+    E.color = v3(s[6][t], s[7][t], s[8][t]);
+    E.rc = s[9][t];
+    E.gxt = s[10][t]; E.gyt = s[11][t];
+    E.unit = __float_as_uint(s[12][t]);
+    const int pk = __float_as_int(s[13][t]);
+    E.bounces = pk >> 9;
+    E.cw = (pk >> 1) & 0xff;
+    E.inside = false;
+    E.ctr = (pk & 1) ? -1 : 6;
+    E.mid = s[15][t];
+}
+RMR_D void slot_put_ray(float (*s)[256], int t, const Lane& E) {
+    s[0][t] = E.o.x; s[1][t] = E.o.y; s[2][t] = E.o.z;
+    s[3][t] = E.d.x; s[4][t] = E.d.y; s[5][t] = E.d.z;
+    s[6][t] = E.color.x; s[7][t] = E.color.y; s[8][t] = E.color.z;
+    s[9][t] = E.rc;
+    s[13][t] = __int_as_float(E.bounces);
+    s[14][t] = E.texit;
+}
+struct SlotRay {
+    V3 o, d, color;
+    float rc, gxt, gyt, texit;
+    uint32_t unit;
+    int pk;
+};
+RMR_D SlotRay slot_read_ray(float (*s)[256], int t) {
+    SlotRay r;
+    r.o = v3(s[0][t], s[1][t], s[2][t]);
+    r.d = v3(s[3][t], s[4][t], s[5][t]);
+    r.color = v3(s[6][t], s[7][t], s[8][t]);
+    r.rc = s[9][t];
+    r.gxt = s[10][t]; r.gyt = s[11][t];
+    r.unit = __float_as_uint(s[12][t]);
+    r.pk = __float_as_int(s[13][t]);
+    r.texit = s[14][t];
+    return r;
+}
+// the lane starts the ray's march (start_march_te's running state: the ray was stored because it runs)
+RMR_D void slot_start_ray(float (*s)[256], int t, Lane& L, const SlotRay& r) {
+    s[16][t] = __uint_as_float(r.unit);
+    L.o = r.o; L.d = r.d; L.color = r.color;
+    L.rc = r.rc; L.gxt = r.gxt; L.gyt = r.gyt;
+    L.bounces = r.pk;
+    L.inside = false;
+    L.texit = r.texit;
+    L.chan = -1;
+    L.t = 0.0f;
+    L.ctr = 0;
+    L.phase = PH_MARCH;
+}
+
 // The lane id where trace_main needs it (the work-queue fetch, counter flushes): recomputed at each
 // use (two VALU) instead of a hoisted value the allocator keeps across the loop — at 8 waves / SIMD it
 // spilled that register to scratch (the stepped Mandelbulb kernel)
@@ -2306,6 +2396,16 @@ static_assert(RMR_QUEUE_PARTS >= 1 && RMR_QUEUE_PARTS <= 64 && RMR_QUEUE_PARTS *
 #ifndef RMR_CHUNK_CACHE
 #define RMR_CHUNK_CACHE 64   // the same for the nearest-primitive cache kernels (6 blocks per CU: 24 KiB of LDS each)
 #endif
+// Lane slots (the hipRTC source of RM1's certified sphere/box kernels asks for them, rmr_jit.cpp): each
+// lane owns a second path in LDS (slot_* above). A finished march whose event needs no shading work (a
+// miss, a hit that ends its path) stores its sample at once; a hit that goes on waits in the slot for
+// a full-width shading batch while the lane marches another path — the slot's ready ray, or a fresh unit.
+#ifndef RMR_LANE_SLOTS
+#define RMR_LANE_SLOTS 0
+#endif
+#ifndef RMR_CHUNK_SLOTS
+#define RMR_CHUNK_SLOTS 64   // units per work claim of the lane-slot kernels (8 KiB of chunk rays + 17 KiB of slots)
+#endif
 typedef uint32_t WCount;
 template <int VAR, class MAP, bool PERSIST, bool PROG, class MATS = TableMats>
 RMR_D void trace_main(const KParams& P) {
@@ -2329,7 +2429,11 @@ RMR_D void trace_main(const KParams& P) {
     // per-wave event counters, 32-bit (wave-uniform: SGPRs; 64-bit ones cost the cache kernels
     // scratch round trips), flushed to the 64-bit global counters before any can pass 2^31
     WCount maps = 0, iters = 0, shades = 0, fulls = 0, shaded = 0, bmaps = 0;
-    constexpr uint32_t CHUNK = MAP::kCache ? RMR_CHUNK_CACHE : RMR_CHUNK;
+    // lane slots: RM1 HO kernels with the certifying inline map, persistent (launched without
+    // separateChannels and without an env map only: the host picks the code object, rmr_api.cpp)
+    constexpr bool SLOTS = RMR_LANE_SLOTS && PERSIST && VAR == RMR_VARIANT_RM1 && CERT && MAP::kCert && !MAP::kCache &&
+                           !MAP::kStepped;
+    constexpr uint32_t CHUNK = MAP::kCache ? RMR_CHUNK_CACHE : (SLOTS ? RMR_CHUNK_SLOTS : RMR_CHUNK);
     const uint32_t n_units = (uint32_t)P.n_units;   // < 2^32 per launch (host chunking)
     // units per claim: the LDS ray buffer's CHUNK, or fewer for a small launch (the host's chunk_units)
     const uint32_t CK = P.chunk_units - 1u < CHUNK ? P.chunk_units : CHUNK;
@@ -2357,6 +2461,11 @@ RMR_D void trace_main(const KParams& P) {
         exhausted = true;
     }
     const int T = P.shade_threshold, TR = P.refill_threshold;
+    // lane slots: finished marches before the park step runs, slot events before a shading batch
+    // (in the shading threshold's place: bits 0-7 and 8-15)
+    const int PK = T & 0xff, T2 = (T >> 8) & 0xff;
+    int sst = 0;             // the lane's slot: 0 empty, 1 an event awaiting shading, 2 a ray ready to march
+    uint32_t nev = 0;        // slots holding an event (wave-uniform)
     // eye_map: every primary ray (a fresh unit, or a separateChannels restart) starts its march at
     // t = 0 from the eye, whose march point fma(dir, 0, eye) is the eye itself for a finite direction
     // (the host clears P.eye_step where an eye coordinate is -0 or not finite). Its map() is therefore
@@ -2387,6 +2496,7 @@ RMR_D void trace_main(const KParams& P) {
     // cache kernels: the lane's shading-only state during the inner march loop (cold_put / cold_get)
     constexpr bool kStash = MAP::kCache && HO;
     __shared__ float s_cold[kStash ? kColdWords : 1][kStash ? 256 : 1];
+    __shared__ float s_slot[SLOTS ? kSlotWords : 1][SLOTS ? 256 : 1];   // lane slots: [word][wave][lane]
     // the cached primitives' table in LDS (per-lane reads of the cache path)
     __shared__ float4 s_dp[MAP::kCache ? 2 * RMR_NPC_LDS_MAX : 1];
     // the stepped Mandelbulb kernel (8 waves / SIMD, 20 KiB of LDS per block): the RNG state (seeds
@@ -2426,6 +2536,18 @@ RMR_D void trace_main(const KParams& P) {
         RMR_STAMP(c0);
         bool fresh = false;
         uint32_t fu = 0;
+        if constexpr (SLOTS) {   // an idle lane marches its slot's ready ray before any fresh unit
+            const bool tk = L.phase == PH_IDLE && sst == 2;
+            if (__ballot(tk)) {
+                if (tk) {
+                    {
+                        const int st = (wv << 6) + (int)lane_now();
+                        slot_start_ray(s_slot, st, L, slot_read_ray(s_slot, st));
+                    }
+                    sst = 0;
+                }
+            }
+        }
         if (PERSIST && !exhausted) {
             uint64_t idle = __ballot(L.phase == PH_IDLE);
             uint64_t act0 = __ballot(is_active(L.phase));
@@ -2493,7 +2615,7 @@ RMR_D void trace_main(const KParams& P) {
                     if (!exhausted) {  // the chunk's primary rays, all 64 lanes at once
                         chunk_base = base;
                         for (uint32_t sl = lane_now(); sl < CK; sl += 64) {
-                            if (base + sl < rend) s_ray[wv][sl] = chunk_ray<HO>(P, base + sl);
+                            if (base + sl < rend) s_ray[wv][sl] = chunk_ray<HO, SLOTS>(P, base + sl);
                         }
                         __builtin_amdgcn_wave_barrier();
 #ifdef RMR_PROFILE
@@ -2515,7 +2637,7 @@ RMR_D void trace_main(const KParams& P) {
                 }
             }
         }
-        const bool restart = (L.phase == PH_RESTART);
+        const bool restart = !SLOTS && (L.phase == PH_RESTART);   // (lane slots: one channel pass, no restarts)
         if (PERSIST) {
             if (__ballot(fresh)) {
                 if (fresh) {
@@ -2527,6 +2649,10 @@ RMR_D void trace_main(const KParams& P) {
                         s_rng[2][wv][ln] = cr.a.w;
                     }
                     begin_unit<VAR, HO>(P, L, fu, cr.a, cr.b);
+                    if constexpr (SLOTS) {
+                        L.chan = -1;   // (launched without separateChannels: a constant)
+                        s_slot[16][(wv << 6) + (int)lane_now()] = __uint_as_float(fu);
+                    }
                 }
             }
             if (__ballot(restart)) {
@@ -2711,6 +2837,8 @@ RMR_D void trace_main(const KParams& P) {
             uint64_t am = amask;
             // the loop's own counts (scalar registers; the wave counters were carried in VGPRs here)
             uint32_t lmaps = 0, liters = 0;
+            // lane slots: PK more finished marches than the lanes that wait in registers for their slot
+            const int TL = SLOTS ? __popcll(__ballot(is_shade(L.phase))) + PK : T;
             for (;;) {
                 if (is_active(L.phase)) {
                     const V3 p = RMR_MARCH_POINT(L);
@@ -2721,7 +2849,7 @@ RMR_D void trace_main(const KParams& P) {
                         bool cert;
                         const V2 m = MAP::eval_c(P, p, w, cert);
                         if (L.phase == PH_NORMAL) normal_update(L, m.x);
-                        else march_update<HO>(P, L, m, w, cert);
+                        else march_update<HO, false, SLOTS>(P, L, m, w, cert);
                     } else {
                         const V2 m = MAP::eval(P, p);
                         if (L.phase == PH_NORMAL) normal_update(L, m.x);
@@ -2732,15 +2860,119 @@ RMR_D void trace_main(const KParams& P) {
                 liters++;
                 const uint64_t sm = __ballot(is_shade(L.phase));
                 am = __ballot(is_active(L.phase));
-                if (!am || __popcll(sm) >= T) break;
+                if (!am || __popcll(sm) >= TL) break;
             }
             maps += (WCount)__builtin_amdgcn_readfirstlane(lmaps);
             iters += (WCount)__builtin_amdgcn_readfirstlane(liters);
         }
         RMR_STAMP(c2);
+        if constexpr (SLOTS) {
+            for (;;) {
+                // (the lane's slot index from lane_now: a value kept across the loop would cost a register)
+                const int st = (wv << 6) + (int)lane_now();
+                // ---- park step: the lanes whose march ended ----
+                const bool sh = is_shade(L.phase);
+                if (__ballot(sh)) {
+                    // events without shading work store their sample at once, with shade()'s own
+                    // expressions (chan < 0, no env map): a miss (color x sky); a hit that ends its path
+                    // — any material but a diffuse one (emission: color x c x gray1; none: color x 0), or
+                    // a diffuse hit at the last bounce, whose new direction only finish_trace would
+                    // follow (color x c on either branch). Such hits never enter cert_normals.
+                    bool cheap = false;
+                    if (sh) {
+                        V3 nc = v3s(0.0f);
+                        if (L.phase == PH_MISS) {
+                            const float g = 1.0f;
+                            nc = sky_color(P, L.d) * g;
+                            cheap = true;
+                        } else {
+                            const int id = (int)L.mid;
+                            int kind = MAT_NONE;
+                            DMat dm{};
+                            if (id >= 0 && id < P.n_mats) {
+                                dm = P.dmats[id];
+                                kind = dm.kind;
+                            }
+                            if (kind == MAT_DIFFUSE) nc = v3(dm.c[0], dm.c[1], dm.c[2]);
+                            else if (kind == MAT_EMISSION) nc = v3(dm.c[0], dm.c[1], dm.c[2]) * dm.gray1;
+                            cheap = kind != MAT_DIFFUSE || !(L.bounces < P.max_bounces);
+                        }
+                        if (cheap) {
+                            const V3 res = L.color * nc;
+                            store_sample(P.samp + __float_as_uint(s_slot[16][st]), make_float4(res.x, res.y, res.z, 1.0f));
+                            L.phase = PH_IDLE;
+                            L.e = v3s(-0.0f);
+                        }
+                    }
+                    shaded += (WCount)__popcll(__ballot(cheap));
+                    // a hit that goes on: its record to the lane's slot — if a ready ray waits there the
+                    // lane takes it (swap), else it goes idle for the refill; with an event already in
+                    // the slot the lane waits in registers for the batch below
+                    const bool park = sh && !cheap && sst != 1;
+                    if (__ballot(park)) {
+                        if (park) {
+                            const bool swap = sst == 2;
+                            SlotRay r{};
+                            if (swap) r = slot_read_ray(s_slot, st);
+                            slot_put_event(s_slot, st, L, vfma(L.d, L.t, L.o));
+                            L.phase = PH_IDLE;
+                            if (swap) slot_start_ray(s_slot, st, L, r);
+                            L.e = v3s(-0.0f);
+                            sst = 1;
+                        }
+                        nev += (uint32_t)__popcll(__ballot(park));
+                    }
+                }
+                // ---- batch: every slot event shaded at once; the marching state stays in registers ----
+                if (!(nev && ((int)nev >= T2 || __ballot(is_active(L.phase)) == 0))) break;
+                shades++;
+                shaded += (WCount)nev;
+                nev = 0;
+                const bool ev = sst == 1;
+                Lane E;
+                slot_get_event(s_slot, st, E);
+                E.d = v3s(0.0f);
+                E.t = 0.0f;
+                E.hit = E.o;
+                E.chan = -1;
+                E.time = 0.0f;
+                E.fin = v3s(0.0f);
+                E.wl = 0u;
+                E.power = 0.0f;
+                E.cw2 = 0;
+                E.cs = -__builtin_inff();
+                E.cta = 0.0f;
+                E.texit = 0.0f;
+                E.e = v3s(-0.0f);
+                E.phase = ev ? PH_HIT : PH_IDLE;
+                {
+                    const bool mine = ev && E.ctr < 0;
+                    const uint64_t cm = __ballot(mine);
+                    if (cm) cert_normals<true>(P, E, mine, cm, s_tab[wv], RMR_DTAB);
+                    maps += (WCount)(6 * __popcll(cm));
+                    bmaps += (WCount)(6 * __popcll(cm));
+#ifdef RMR_COUNT_FLOPS
+                    const uint64_t bm = __ballot(mine && (__float_as_int(((const float4*)(P.dprims + E.cw))[1].z) & 0xff) == RMR_PRIM_BOX);
+                    RMR_COUNT(P.counters, (uint64_t)__popcll(bm), 6 * (22 + 2), 6);
+                    RMR_COUNT(P.counters, (uint64_t)__popcll(cm & ~bm), 6 * (10 + 2), 6);
+#endif
+                }
+                if (ev) {
+                    // (a next ray that meets no escape box is shaded as its miss in the same call)
+                    shade<VAR, PROG, MATS, CERT>(P, E);
+                    sst = 0;
+                    if (E.phase == PH_MARCH) {
+                        slot_put_ray(s_slot, st, E);
+                        sst = 2;
+                    }
+                }
+                // lanes that waited in registers park now (their slots are empty or hold a ready ray)
+                if (__ballot(is_shade(L.phase)) == 0) break;
+            }
+        }
         const uint64_t smask = __ballot(is_shade(L.phase));
         const uint64_t amask2 = __ballot(is_active(L.phase));
-        if (smask && (__popcll(smask) >= T || amask2 == 0)) {
+        if (!SLOTS && smask && (__popcll(smask) >= T || amask2 == 0)) {
             shades++;
             shaded += (WCount)__popcll(smask);
             if constexpr (CERT) {   // the certified hits' getNormal probes, spread over the wave
@@ -2781,7 +3013,7 @@ RMR_D void trace_main(const KParams& P) {
         cyc[2] += c3 - c2;
 #endif
         const uint64_t live = __ballot(L.phase != PH_IDLE);
-        const bool last = live == 0 && exhausted;
+        const bool last = live == 0 && exhausted && (!SLOTS || __ballot(sst != 0) == 0);
         // (an inner loop adds at most 64 x its iterations to `maps`; a flush every 2^30 keeps every
         // 32-bit counter far from wrapping between two checks)
         if (last || ((maps | shaded) >> 30) != 0) {

@@ -162,8 +162,15 @@ class Renderer:
     def set_kernel(self, k):
         self._chk(self._L.rmr_set_kernel(self._ctx, int(k)))
 
-    def set_tuning(self, shade_threshold=0, grid_per_cu=-1, samp_budget=0):
-        self._chk(self._L.rmr_set_tuning(self._ctx, int(shade_threshold), int(grid_per_cu), int(samp_budget)))
+    def set_tuning(self, shade_threshold=0, grid_per_cu=-1, samp_budget=0, park=None, slot_batch=None, lane_slots=None):
+        """rmr_set_tuning. park / slot_batch / lane_slots: the lane-slot kernels' thresholds (0: the
+        kernel class's) and the schedule's switch, carried in shade_threshold's upper bits (rmr.h);
+        giving any of them sets all three (the others to their defaults)."""
+        st = int(shade_threshold)
+        if not (park is None and slot_batch is None and lane_slots is None):
+            p = 127 if lane_slots is False else min(64, int(park or 0))
+            st |= 1 << 23 | p << 16 | min(64, int(slot_batch or 0)) << 24
+        self._chk(self._L.rmr_set_tuning(self._ctx, st, int(grid_per_cu), int(samp_budget)))
 
     def set_grid_reserve(self, blocks):
         """Workgroups the persistent trace launch leaves free (rmr_set_grid_reserve; scheduling only)."""

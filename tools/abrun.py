@@ -10,6 +10,7 @@ VARIANT = [LABEL=]SPEC[;SPEC...], SPEC one of
     env:K=V         any other RMR_* switch read at scene load / specialisation time (repeatable)
     cull:N          rmr_set_culling flags
     shade:T         rmr_set_tuning shading threshold (T + 256 R: refill threshold R)
+    slots:off | slots:P,T2   lane-slot kernels: the schedule off, or its park / batch thresholds
 e.g.  python tools/abrun.py --cases c2,c4 base="lib:tools/librmr_base.so" new="lib:raymarchrenderer_amd/librmr_diag.so"
       python tools/abrun.py --cases glass,default w6="opts:-DRMR_PROG_WAVES=6" w7="opts:-DRMR_PROG_WAVES=7" def=""
 
@@ -65,7 +66,10 @@ def parse_variant(text):
         elif kind == "cull":
             v["cull"] = int(val)
         elif kind == "shade":
-            v["shade"] = int(val)
+            v["shade"] = (v["shade"] or 0) | int(val)
+        elif kind == "slots":   # rmr_set_tuning's upper bits (rmr.h)
+            p, _, t2 = val.partition(",")
+            v["shade"] = (v["shade"] or 0) | 1 << 23 | ((127 << 16) if val == "off" else (int(p) << 16 | int(t2 or 0) << 24))
         else:
             raise SystemExit("unknown variant spec %r" % item)
     return v
