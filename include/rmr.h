@@ -197,6 +197,68 @@ int rmr_set_kernel(rmr_ctx* ctx, int kernel);
  * CLAMP_TO_EDGE. */
 int rmr_set_env_map(rmr_ctx* ctx, const uint8_t* rgba8, int w, int h);
 
+/* ---- first-hit guides and the preview denoiser ------------------------------------------- */
+/* No counterpart in the reference (its only output is the noisy running mean): the per-pixel geometry
+ * of the first hit, and an edge-avoiding a-trous filter over the accumulator guided by it, for a
+ * usable image after a few samples. Additive: nothing here changes a render's result. All of it runs
+ * on the context's stream after the work queued before it, flushes held rmr_render calls first like
+ * every other entry point, and works with a caller stream and a bound accumulator. The five W x H
+ * float4 buffers (three guide planes, two filter images) are allocated at first use (RMR_E_NOMEM if
+ * that fails) and freed by rmr_reload / rmr_destroy; a context that never calls these allocates none.
+ *
+ * Guide planes: W x H float4, row 0 = top, laid out like the accumulator. Each pixel's ray is main()'s
+ * corner-ray interpolation at the pixel centre (u = px / W + 0.5 / W, v = py / H + 0.5 / H; no rand()),
+ * marched with march(eye, dir, +1) under the context's max_dist / max_steps / step_multiply. A pixel
+ * is a hit iff t < max_dist (a hit march() returns at t >= max_dist is a miss, as in trace()).
+ *   RMR_GUIDE_RAY     (dir.xyz, 0)
+ *   RMR_GUIDE_HIT     (pos.xyz, t), pos = fma(dir, t, eye), for hits and misses alike
+ *   RMR_GUIDE_NORMAL  hit: (getNormal(pos).xyz, material id); miss: (0, 0, 0, -1) */
+#define RMR_GUIDE_RAY 0
+#define RMR_GUIDE_HIT 1
+#define RMR_GUIDE_NORMAL 2
+/* Render the guides of the integer rect [x0,x1) x [y0,y1) (clamped to the image); writes only inside
+ * the rect. The guides become valid when one call covers the whole image; rmr_set_view, a scene load,
+ * rmr_set_params and rmr_reload invalidate them. RMR_E_STATE without a scene. */
+int rmr_render_guides(rmr_ctx* ctx, int x0, int y0, int x1, int y1);
+/* One plane to the host (synchronises): what the rmr_render_guides calls so far wrote, zeros elsewhere.
+ * RMR_E_STATE before the first rmr_render_guides since rmr_create / rmr_reload. */
+int rmr_read_guide(rmr_ctx* ctx, int plane, float* rgba, size_t bytes);
+/* Device pointer of a plane (allocates the planes if need be; NULL for a bad plane or on failure). */
+void* rmr_guide_device_ptr(rmr_ctx* ctx, int plane);
+
+/* Filter parameters. Pass i = 0 .. iterations-1 is the 5x5 B3-spline kernel (1/16, 1/4, 3/8, 1/4, 1/16)^2
+ * with taps 2^i pixels apart; a tap q of a centre p weighs, besides the kernel,
+ *   [id_q == id_p] * max(0, n_p.n_q)^(2^normal_pow2) * exp(-|n_p.(x_q - x_p)| / (sigma_z 2^i max(t_p, FLT_MIN)))
+ *   * (sigma_c > 0 ? exp(-|c_q - c_p|^2 / (sigma_c 2^-i)^2) : 1),
+ * the centre tap 1 exactly, a tap off the image or not live 0. A pixel is live iff its guide id >= 0,
+ * its accumulator alpha != 0 and its current rgb is finite; a pixel that is not live (sky, not yet
+ * rendered, NaN) passes through every pass bit for bit. Alpha is never changed. */
+typedef struct rmr_denoise_params {
+    int32_t iterations;  /* 5     0..8; 0 copies the accumulator                                  */
+    int32_t normal_pow2; /* 5     0..7: squarings of the normal term (exponent 2^normal_pow2)      */
+    float   sigma_z;     /* 0.02  finite, > 0: plane distance, relative to the centre's t and step */
+    float   sigma_c;     /* 0     finite, >= 0: colour distance; 0 = term off                      */
+} rmr_denoise_params;
+void rmr_default_denoise_params(rmr_denoise_params* p);
+/* Filter the accumulator into the context's denoised image (the accumulator is never written).
+ * p NULL = the defaults; values outside the ranges above are RMR_E_INVALID. Renders full-image guides
+ * first when they are not valid. The denoised image stays valid until a render call, rmr_write_accum /
+ * rmr_load_accum, rmr_bind_accum, rmr_reload or anything that invalidates the guides. */
+int rmr_denoise(rmr_ctx* ctx, const rmr_denoise_params* p);
+/* The denoised image as RGBA32F (synchronises); RMR_E_STATE without a valid one. */
+int rmr_read_denoised(rmr_ctx* ctx, float* rgba, size_t bytes);
+/* Its device pointer (W x H float4; the next rmr_denoise may return another); NULL without a valid one. */
+void* rmr_denoised_device_ptr(rmr_ctx* ctx);
+/* What rmr_save_bmp / rmr_display / rmr_display_device read: the accumulator (default) or the denoised
+ * image; with RMR_OUTPUT_DENOISED and no valid denoised image those calls return RMR_E_STATE. */
+#define RMR_OUTPUT_ACCUM 0
+#define RMR_OUTPUT_DENOISED 1
+int rmr_set_output_source(rmr_ctx* ctx, int source);
+/* Float image file from a host RGBA32F buffer (no context needed, like rmr_encode_bmp): a colour PFM
+ * ("PF", RGB float32, scale -1.0 = little-endian, rows bottom to top; alpha is dropped). With
+ * rmr_read_guide / rmr_read_accum / rmr_read_denoised the float output path for planes and HDR images. */
+int rmr_encode_pfm(const float* rgba, int w, int h, const char* path);
+
 /* ---- display ---------------------------------------------------------------------------- */
 /* Graphics::Display(centre, zoom, min, max) (Graphics.cpp:356-390 with createFQ 227-258 and
  * FullQuad.vs / FullQuad.fs), headless: draws the accumulator into a screen_w x screen_h RGBA8 image
@@ -278,7 +340,9 @@ int rmr_set_grid_reserve(rmr_ctx* ctx, int blocks);
 /* Test hook: per-sample radiance (before the running mean) of the integer rect, written as
  * out[k][y-y0][x-x0][4]; sample k is seeded with times[k]. The accumulator is left unchanged. */
 int rmr_trace_samples(rmr_ctx* ctx, const float* times, int x0, int y0, int x1, int y1, uint32_t nspp, float* out);
-/* sizeof of the ABI structs (prim, op, material, spectral, rm2_consts, scene, params, stats). */
+/* sizeof of the ABI structs (prim, op, material, spectral, rm2_consts, scene, params, stats): writes
+ * the first min(n, 8) and returns 8. With n >= 9 it also writes out[8] = sizeof(rmr_denoise_params);
+ * the returned count stays 8 for callers that compare it with their own list of those eight. */
 int rmr_abi_sizes(int32_t* out, int n);
 
 #ifdef __cplusplus

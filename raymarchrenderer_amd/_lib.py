@@ -26,6 +26,8 @@ EXPORTS = [
     "rmr_set_kernel", "rmr_set_tuning", "rmr_set_grid_reserve", "rmr_trace_samples", "rmr_abi_sizes", "rmr_set_jit", "rmr_set_instrument", "rmr_jit_compile_scene", "rmr_set_env_map",
     "rmr_scene_compile", "rmr_scene_view", "rmr_scene_free", "rmr_display", "rmr_display_device",
     "rmr_srgb_thresholds", "rmr_candidate_grid", "rmr_set_call_batching", "rmr_set_launch_streams", "rmr_get_launch_streams",
+    "rmr_default_denoise_params", "rmr_render_guides", "rmr_read_guide", "rmr_guide_device_ptr", "rmr_denoise",
+    "rmr_read_denoised", "rmr_denoised_device_ptr", "rmr_set_output_source", "rmr_encode_pfm",
 ]
 
 
@@ -122,8 +124,19 @@ def lib(diag=None):
         "rmr_candidate_grid": (C.c_int, [fp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                          C.POINTER(C.c_int32), fp, C.POINTER(C.c_uint32), C.c_size_t,
                                          C.POINTER(C.c_uint16), C.c_size_t]),
-        # diagnostic library only (rmr_api.cpp RMR_DIAG): ray_exit at given rays
+        "rmr_default_denoise_params": (None, [C.POINTER(abi.DenoiseParams)]),
+        "rmr_render_guides": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "rmr_read_guide": (C.c_int, [vp, C.c_int, fp, C.c_size_t]),
+        "rmr_guide_device_ptr": (vp, [vp, C.c_int]),
+        "rmr_denoise": (C.c_int, [vp, C.POINTER(abi.DenoiseParams)]),
+        "rmr_read_denoised": (C.c_int, [vp, fp, C.c_size_t]),
+        "rmr_denoised_device_ptr": (vp, [vp]),
+        "rmr_set_output_source": (C.c_int, [vp, C.c_int]),
+        "rmr_encode_pfm": (C.c_int, [fp, C.c_int, C.c_int, C.c_char_p]),
+        # diagnostic library only (rmr_api.cpp RMR_DIAG): ray_exit at given rays; the a-trous passes
+        # that run the LDS-tiled form
         "rmr_diag_ray_exit": (C.c_int, [vp, fp, C.c_int, fp, fp, C.c_int, ip]),
+        "rmr_diag_denoise_tiled": (C.c_int, [vp, C.c_int]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(L, name):   # (an older build given by path may lack a newer entry point)

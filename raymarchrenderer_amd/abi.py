@@ -106,6 +106,29 @@ class Stats(C.Structure):
                 ("trace_ms", C.c_double), ("fold_ms", C.c_double), ("flops_per_map", C.c_double),
                 ("map_iters", C.c_uint64), ("shade_batches", C.c_uint64), ("jit_launches", C.c_uint64)]
 
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("normal_pow2", C.c_int32), ("sigma_z", C.c_float),
+                ("sigma_c", C.c_float)]
+
+
+def default_denoise_params(**kw):
+    """rmr_default_denoise_params' values (rmr.h), with overrides."""
+    p = DenoiseParams(5, 5, 0.02, 0.0)
+    for k, v in kw.items():
+        if k not in ("iterations", "normal_pow2", "sigma_z", "sigma_c"):
+            raise TypeError("unknown denoise parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+# guide planes and output sources (rmr.h)
+GUIDE_RAY = 0
+GUIDE_HIT = 1
+GUIDE_NORMAL = 2
+GUIDE_PLANES = {"ray": GUIDE_RAY, "hit": GUIDE_HIT, "normal": GUIDE_NORMAL}
+OUTPUT_ACCUM = 0
+OUTPUT_DENOISED = 1
 # rmr_set_culling flags (rmr.h)
 CULL_ESCAPE = 1
 CULL_NPC = 2

@@ -2,10 +2,12 @@
 //   * rmr_camera_view: Camera::calculateRays (Camera.cpp:25-102) + the setView argument swap
 //     (Camera.cpp:101 -> Graphics.cpp:827-835);
 //   * rmr_encode_bmp: Graphics::SaveImage's output encoding (Graphics.cpp:754-799) and the BMP
-//     writer of SOIL's stb_image_write (24-bit, BGR, bottom-up, alpha composited on (255,0,255)).
+//     writer of SOIL's stb_image_write (24-bit, BGR, bottom-up, alpha composited on (255,0,255));
+//   * rmr_encode_pfm: the float output path for guide planes and HDR images.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "../../include/rmr.h"
@@ -119,4 +121,25 @@ extern "C" int rmr_encode_bmp(const float* rgba, int w, int h, const char* path)
         std::fwrite(row.data(), 1, row.size(), f);
     }
     return std::fclose(f) == 0 ? RMR_OK : RMR_E_IO;
+}
+
+// Colour PFM: "PF\n<w> <h>\n-1.0\n", then RGB float32 little-endian, rows bottom to top (rmr.h).
+extern "C" int rmr_encode_pfm(const float* rgba, int w, int h, const char* path) {
+    if (!rgba || w <= 0 || h <= 0 || !path) return RMR_E_INVALID;
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return RMR_E_IO;
+    bool ok = std::fprintf(f, "PF\n%d %d\n-1.0\n", w, h) > 0;
+    std::vector<uint8_t> row((size_t)w * 12);
+    for (int y = h - 1; y >= 0 && ok; y--) {
+        for (int x = 0; x < w; x++)
+            for (int k = 0; k < 3; k++) {
+                uint32_t b;
+                std::memcpy(&b, &rgba[((size_t)y * w + x) * 4 + k], 4);
+                uint8_t* o = &row[((size_t)x * 3 + k) * 4];
+                for (int j = 0; j < 4; j++) o[j] = (uint8_t)(b >> (8 * j));   // little-endian on any host
+            }
+        ok = std::fwrite(row.data(), 1, row.size(), f) == row.size();
+    }
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? RMR_OK : RMR_E_IO;
 }

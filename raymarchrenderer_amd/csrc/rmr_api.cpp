@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -33,6 +34,8 @@ hipError_t launch_display(const float4* accum, int img_w, int img_h, float cx, f
                           float min_y, float max_x, float max_y, int scr_w, int scr_h, uint32_t* rgba8,
                           const float* thr, hipStream_t s);
 int trace_occupancy(int variant, int np, bool prog, int* blocks_per_cu);
+hipError_t launch_guides(const KParams& P, int np, float4* ray, float4* hit, float4* nrm, hipStream_t s);
+hipError_t launch_atrous(const DenoisePass& A, bool tiled, hipStream_t s);
 }  // namespace rmr
 
 using rmr::CompiledScene;
@@ -42,6 +45,8 @@ using rmr::TileXY;
 struct EventPair { hipEvent_t a, b, c; };
 
 constexpr int kSlotGridReserve = 32;   // workgroups a slotted launch leaves free for the previous fold
+// a-trous passes that run the LDS-tiled form (bit i: step 2^i); DESIGN.md §4.7 has the measurements
+constexpr int kDenoiseTiledSteps = 3;
 
 struct rmr_ctx {
     int device = 0;
@@ -86,6 +91,14 @@ struct rmr_ctx {
     bool accum_external = false;
     float4* d_samp = nullptr;
     size_t samp_cap = 0;
+    // first-hit guides and the preview denoiser (rmr_render_guides / rmr_denoise): three guide planes and
+    // two filter images of W x H float4, allocated at first use, freed at rmr_reload / rmr_destroy
+    float4* d_guide[3] = {nullptr, nullptr, nullptr};
+    float4* d_dn[2] = {nullptr, nullptr};
+    bool guides_valid = false;            // one rmr_render_guides covered the image with the current view / scene / params
+    int dn_result = -1;                   // d_dn[] index of the valid denoised image, -1: none
+    int output_source = RMR_OUTPUT_ACCUM; // what rmr_save_bmp / rmr_display* read
+    int dn_tiled_steps = kDenoiseTiledSteps;   // bit i: pass i (step 2^i, i < 2) runs the LDS-tiled form
     // Launch slots (rmr_set_launch_streams): trace launches go round-robin to private streams, each with
     // its own sample planes and work queue, so a launch's drain (its last long paths on a nearly idle
     // chip) overlaps the next launch's start. Every fold stays on the context's stream, after its trace's
@@ -246,6 +259,14 @@ void default_view(rmr_ctx* c) {
 
 int free_slots(rmr_ctx* c);
 
+// Release the guide planes and the filter images (the caller has synced the context's stream).
+void free_guides(rmr_ctx* c) {
+    for (float4*& b : c->d_guide) { if (b) (void)hipFree(b); b = nullptr; }
+    for (float4*& b : c->d_dn) { if (b) (void)hipFree(b); b = nullptr; }
+    c->guides_valid = false;
+    c->dn_result = -1;
+}
+
 // The experiments' switches of the diagnostic library that take effect at a scene load (RMR_ENV is
 // nullptr in the release library, rmr_jit.hpp; rmr_create reads those of a context's settings).
 rmr::AccelOptions read_switches(rmr_ctx* c) {
@@ -333,6 +354,8 @@ int upload_scene(rmr_ctx* c) {
     a.grid.list = {};
     c->esc_infl_dev = -1.0;
     c->scene_kp = scene_params(c);
+    c->guides_valid = false;   // (every scene load comes through here)
+    c->dn_result = -1;
     c->scene_loaded = true;
     c->jit_ready = false;
     c->jit_failed = false;
@@ -710,6 +733,7 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
     int r;
     if ((r = launch_precheck(c))) return r;
     if (tiles.empty() || nspp == 0) return RMR_OK;
+    c->dn_result = -1;   // the accumulator changes: the denoised image is of the old one
     if (!c->view_set) default_view(c);
     const TileXY* d_tiles = nullptr;
     if ((r = tile_list(c, tiles, &d_tiles))) return r;
@@ -786,6 +810,18 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
 }
 
 using rmr::rect_tiles;
+
+// The image rmr_save_bmp / rmr_display* read (rmr_set_output_source).
+int output_image(rmr_ctx* c, const char* who, const float4** out) {
+    if (c->output_source == RMR_OUTPUT_DENOISED) {
+        if (c->dn_result < 0)
+            return fail(c, RMR_E_STATE, std::string(who) + ": output source is the denoised image, but none is valid (call rmr_denoise)");
+        *out = c->d_dn[c->dn_result];
+    } else {
+        *out = c->d_accum;
+    }
+    return RMR_OK;
+}
 
 bool batching_on(const rmr_ctx* c) {
     return c->call_batching > 0 || (c->call_batching < 0 && c->own_stream && !c->accum_external);
@@ -902,6 +938,7 @@ void rmr_destroy(rmr_ctx* c) {
         if (b) (void)hipFree(b);
     for (auto& e : c->tile_cache) (void)hipFree(e.dev);
     if (c->h_times) (void)hipHostFree(c->h_times);
+    free_guides(c);
     if (c->d_accum && !c->accum_external) (void)hipFree(c->d_accum);
     for (auto& k : c->jit_loaded)
         if (k.module) (void)hipModuleUnload(k.module);
@@ -951,6 +988,8 @@ int rmr_set_params(rmr_ctx* c, const rmr_params* p) {
     RMR_FLUSH(c);
     if (p->max_steps < 0 || p->max_bounces < 0 || !(p->max_dist > 0.0f)) return fail(c, RMR_E_INVALID, "bad params");
     c->params = *p;
+    c->guides_valid = false;
+    c->dn_result = -1;
     return RMR_OK;
 }
 
@@ -969,6 +1008,8 @@ int rmr_set_view(rmr_ctx* c, const float eye[3], const float r00[3], const float
         c->view[9 + i] = r10[i]; c->view[12 + i] = r11[i];
     }
     c->view_set = true;
+    c->guides_valid = false;
+    c->dn_result = -1;
     return RMR_OK;
 }
 
@@ -1023,6 +1064,7 @@ int rmr_reload(rmr_ctx* c) {
     if (c->accum_external && (c->pend_W != c->W || c->pend_H != c->H))
         return fail(c, RMR_E_STATE, "bound accumulator cannot be resized");
     const bool resize = (c->pend_W != c->W || c->pend_H != c->H);
+    free_guides(c);   // (the stream is idle)
     c->W = c->pend_W;
     c->H = c->pend_H;
     if (resize) {
@@ -1046,6 +1088,7 @@ int rmr_render(rmr_ctx* c, float time, float min_x, float min_y, float max_x, fl
     }
     // deferred (rmr_set_call_batching): the errors the launch would give now come at the call
     if (const int r = launch_precheck(c)) return r;
+    c->dn_result = -1;
     rmr::DeferredCall* same = nullptr;
     bool overlap = false;
     for (auto& e : c->deferred) {
@@ -1125,6 +1168,7 @@ int rmr_write_accum(rmr_ctx* c, const float* rgba, size_t bytes) {
     RMR_FLUSH(c);
     const size_t need = (size_t)c->W * c->H * sizeof(float4);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
+    c->dn_result = -1;
     HIPCHK(c, hipMemcpyAsync(c->d_accum, rgba, need, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RMR_OK;
@@ -1147,6 +1191,7 @@ int rmr_bind_accum(rmr_ctx* c, void* ptr, size_t bytes) {
     // (an external buffer is only swapped: launches already queued keep the pointer they captured)
     c->d_accum = (float4*)ptr;
     c->accum_external = true;
+    c->dn_result = -1;
     return RMR_OK;
 }
 
@@ -1154,8 +1199,11 @@ int rmr_save_bmp(rmr_ctx* c, const char* path) {
     if (!c || !path) return RMR_E_INVALID;
     RMR_FLUSH(c);
     std::vector<float> host((size_t)c->W * c->H * 4);
-    int r = rmr_read_accum(c, host.data(), host.size() * sizeof(float));
+    const float4* src = nullptr;
+    int r = output_image(c, "rmr_save_bmp", &src);
     if (r) return r;
+    HIPCHK(c, hipMemcpyAsync(host.data(), src, host.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     r = rmr_encode_bmp(host.data(), c->W, c->H, path);
     if (r) return fail(c, r, std::string("cannot write ") + path);
     return RMR_OK;
@@ -1321,7 +1369,9 @@ int display_common(rmr_ctx* c, float cx, float cy, float zoom, float min_x, floa
         int r = dev_upload(c, &c->d_srgb_thr, t, 256);
         if (r) return r;
     }
-    HIPCHK(c, rmr::launch_display(c->d_accum, c->W, c->H, cx, cy, zoom, min_x, min_y, max_x, max_y, sw, sh, dev,
+    const float4* src = nullptr;
+    if (const int r = output_image(c, "rmr_display", &src)) return r;
+    HIPCHK(c, rmr::launch_display(src, c->W, c->H, cx, cy, zoom, min_x, min_y, max_x, max_y, sw, sh, dev,
                                   c->d_srgb_thr, c->stream));
     return RMR_OK;
 }
@@ -1500,7 +1550,159 @@ int rmr_trace_samples(rmr_ctx* c, const float* times, int x0, int y0, int x1, in
     return rmr_write_accum(c, keep.data(), keep.size() * sizeof(float));
 }
 
+// ---- first-hit guides and the preview denoiser (rmr_guides.hip, rmr_denoise.hip) ------------------
+namespace {
+// The five W x H float4 buffers, at first use. The guide planes start as zeros (a read before a
+// full-image pass shows zeros outside the rects rendered so far).
+int ensure_guides(rmr_ctx* c) {
+    if (c->d_guide[0]) return RMR_OK;
+    const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
+    float4* b[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 5; i++) {
+        if (hipMalloc((void**)&b[i], bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            for (int k = 0; k < i; k++) (void)hipFree(b[k]);
+            return fail(c, RMR_E_NOMEM, "cannot allocate the guide planes and filter images (5 x W x H x 16 bytes)");
+        }
+    }
+    for (int i = 0; i < 3; i++) c->d_guide[i] = b[i];
+    c->d_dn[0] = b[3];
+    c->d_dn[1] = b[4];
+    c->guides_valid = false;
+    c->dn_result = -1;
+    for (int i = 0; i < 3; i++) HIPCHK(c, hipMemsetAsync(c->d_guide[i], 0, bytes, c->stream));
+    return RMR_OK;
+}
+
+// The guide pass over a rect already clamped to the image and non-empty.
+int render_guides(rmr_ctx* c, int x0, int y0, int x1, int y1) {
+    int r;
+    if (!c->scene_loaded) return fail(c, RMR_E_STATE, "no scene loaded (call rmr_load_scene_json / rmr_load_builtin_scene)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((r = ensure_guides(c))) return r;
+    if (!c->view_set) default_view(c);
+    KParams P;
+    if ((r = view_params(c, P))) return r;
+    P.x0 = x0; P.y0 = y0; P.x1 = x1; P.y1 = y1;
+    HIPCHK(c, rmr::launch_guides(P, c->accel.map_np, c->d_guide[RMR_GUIDE_RAY], c->d_guide[RMR_GUIDE_HIT],
+                                 c->d_guide[RMR_GUIDE_NORMAL], c->stream));
+    if (x0 == 0 && y0 == 0 && x1 == c->W && y1 == c->H) c->guides_valid = true;
+    return RMR_OK;
+}
+
+bool denoise_params_ok(const rmr_denoise_params& p) {
+    return p.iterations >= 0 && p.iterations <= 8 && p.normal_pow2 >= 0 && p.normal_pow2 <= 7 &&
+           std::isfinite(p.sigma_z) && p.sigma_z > 0.0f && std::isfinite(p.sigma_c) && p.sigma_c >= 0.0f;
+}
+}  // namespace
+
+void rmr_default_denoise_params(rmr_denoise_params* p) {
+    if (!p) return;
+    p->iterations = 5;
+    p->normal_pow2 = 5;
+    p->sigma_z = 0.02f;
+    p->sigma_c = 0.0f;
+}
+
+int rmr_render_guides(rmr_ctx* c, int x0, int y0, int x1, int y1) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!c->scene_loaded) return fail(c, RMR_E_STATE, "no scene loaded (call rmr_load_scene_json / rmr_load_builtin_scene)");
+    if (!rmr::clamp_rect(c->W, c->H, x0, y0, x1, y1)) return RMR_OK;
+    return render_guides(c, x0, y0, x1, y1);
+}
+
+int rmr_read_guide(rmr_ctx* c, int plane, float* rgba, size_t bytes) {
+    if (!c || !rgba) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (plane < RMR_GUIDE_RAY || plane > RMR_GUIDE_NORMAL) return fail(c, RMR_E_INVALID, "bad guide plane");
+    const size_t need = (size_t)c->W * c->H * sizeof(float4);
+    if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
+    if (!c->d_guide[plane]) return fail(c, RMR_E_STATE, "no guides rendered (call rmr_render_guides)");
+    HIPCHK(c, hipMemcpyAsync(rgba, c->d_guide[plane], need, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+void* rmr_guide_device_ptr(rmr_ctx* c, int plane) {
+    if (!c || plane < RMR_GUIDE_RAY || plane > RMR_GUIDE_NORMAL) return nullptr;
+    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
+    if (hipSetDevice(c->device) != hipSuccess || ensure_guides(c) != RMR_OK) return nullptr;
+    return (void*)c->d_guide[plane];
+}
+
+int rmr_denoise(rmr_ctx* c, const rmr_denoise_params* p) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_denoise_params q;
+    rmr_default_denoise_params(&q);
+    if (p) q = *p;
+    if (!denoise_params_ok(q))
+        return fail(c, RMR_E_INVALID, "bad denoise params (iterations 0..8, normal_pow2 0..7, sigma_z finite > 0, sigma_c finite >= 0)");
+    int r;
+    c->dn_result = -1;
+    if (!c->guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
+    if (q.iterations == 0) {
+        HIPCHK(c, hipMemcpyAsync(c->d_dn[0], c->d_accum, bytes, hipMemcpyDeviceToDevice, c->stream));
+        c->dn_result = 0;
+        return RMR_OK;
+    }
+    rmr::DenoisePass A{};
+    A.hit = c->d_guide[RMR_GUIDE_HIT];
+    A.nrm = c->d_guide[RMR_GUIDE_NORMAL];
+    A.W = c->W;
+    A.H = c->H;
+    A.normal_pow2 = q.normal_pow2;
+    for (int i = 0; i < q.iterations; i++) {
+        A.in = i == 0 ? c->d_accum : c->d_dn[(i - 1) & 1];
+        A.out = c->d_dn[i & 1];
+        A.step = 1 << i;
+        A.sigma_z_step = q.sigma_z * (float)A.step;
+        const double sc = (double)q.sigma_c / (double)A.step;   // sigma_c 2^-i
+        // (kept finite: a zero colour distance then weighs exp(-0) = 1 whatever sigma_c is)
+        A.inv_sigma_c2 = q.sigma_c > 0.0f ? (float)std::min(1.0 / (sc * sc), (double)FLT_MAX) : 0.0f;
+        HIPCHK(c, rmr::launch_atrous(A, i < 2 && ((c->dn_tiled_steps >> i) & 1), c->stream));
+    }
+    c->dn_result = (q.iterations - 1) & 1;
+    return RMR_OK;
+}
+
+int rmr_read_denoised(rmr_ctx* c, float* rgba, size_t bytes) {
+    if (!c || !rgba) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    const size_t need = (size_t)c->W * c->H * sizeof(float4);
+    if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
+    if (c->dn_result < 0) return fail(c, RMR_E_STATE, "no valid denoised image (call rmr_denoise)");
+    HIPCHK(c, hipMemcpyAsync(rgba, c->d_dn[c->dn_result], need, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+void* rmr_denoised_device_ptr(rmr_ctx* c) {
+    if (!c) return nullptr;
+    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
+    return c->dn_result < 0 ? nullptr : (void*)c->d_dn[c->dn_result];
+}
+
+int rmr_set_output_source(rmr_ctx* c, int source) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (source != RMR_OUTPUT_ACCUM && source != RMR_OUTPUT_DENOISED) return fail(c, RMR_E_INVALID, "bad output source");
+    c->output_source = source;
+    return RMR_OK;
+}
+
 #if RMR_DIAG
+// Diagnostic library only (not in include/rmr.h; tools/denoise_time.py): which a-trous passes run the
+// LDS-tiled form, bit i = the pass of step 2^i (i < 2); the results are the same either way.
+int rmr_diag_denoise_tiled(rmr_ctx* c, int mask) {
+    if (!c || mask < 0 || mask > 3) return RMR_E_INVALID;
+    c->dn_tiled_steps = mask;
+    return RMR_OK;
+}
+
 // Diagnostic library only (not in include/rmr.h): the escape bound ray_exit at n given rays (rays:
 // o.xyz, d.xyz per ray) with the context's scene, view and maxDist, as a launch would use it; out[i]
 // = the bound (+inf: none). boxes (optional, 6 floats per box, up to max_boxes) receives the inflated
@@ -1540,6 +1742,7 @@ int rmr_abi_sizes(int32_t* out, int n) {
                          (int32_t)sizeof(rmr_params), (int32_t)sizeof(rmr_stats)};
     const int m = (int)(sizeof s / sizeof s[0]);
     for (int i = 0; i < n && i < m; i++) out[i] = s[i];
+    if (n >= 9) out[8] = (int32_t)sizeof(rmr_denoise_params);   // (beyond the returned count, see rmr.h)
     return m;
 }
 

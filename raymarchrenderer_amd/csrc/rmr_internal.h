@@ -135,4 +135,18 @@ struct KParams {
     int32_t refill_threshold;   // idle lanes before a wave fetches new units
 };
 
+// One pass of the a-trous preview filter (rmr_denoise.hip): in -> out (W x H float4 each, never the
+// same buffer) guided by the first-hit planes of rmr_guides.hip.
+struct DenoisePass {
+    const float4* in;
+    float4* out;
+    const float4* hit;          // (pos.xyz, t)
+    const float4* nrm;          // (normal.xyz, id); id < 0: no hit
+    int32_t W, H;
+    int32_t step;               // 2^i: pixels between taps
+    int32_t normal_pow2;        // squarings of max(0, n_p . n_q)
+    float sigma_z_step;         // sigma_z * step
+    float inv_sigma_c2;         // 1 / (sigma_c 2^-i)^2; 0: no colour term
+};
+
 }  // namespace rmr

@@ -172,6 +172,27 @@ void Graphics::setEnvMap(const unsigned char* rgba8, int w, int h) {
     if (g_group) check(rmr_group_set_env_map(g_group, rgba8, w, h), "setEnvMap");
     else check(rmr_set_env_map(g_ctx, rgba8, w, h), "setEnvMap");
 }
+namespace {
+// the denoiser works on one context's accumulator; a device group's frame lives in its reduce buffer
+bool no_group(const char* what) {
+    if (!g_group) return true;
+    g_status = RMR_E_UNSUPPORTED;
+    g_error = std::string(what) + ": not available in device-group mode (setDevices); single-context mode only";
+    std::cerr << "Graphics::" << g_error << std::endl;
+    return false;
+}
+}  // namespace
+void Graphics::Denoise(int iterations) {
+    if (!need_ctx("Denoise") || !no_group("Denoise")) return;
+    rmr_denoise_params p;
+    rmr_default_denoise_params(&p);
+    p.iterations = iterations;
+    check(rmr_denoise(g_ctx, &p), "Denoise");
+}
+void Graphics::setOutputSource(int source) {
+    if (!need_ctx("setOutputSource") || !no_group("setOutputSource")) return;
+    check(rmr_set_output_source(g_ctx, source), "setOutputSource");
+}
 void Graphics::Sync() {
     if (!need_ctx("Sync")) return;
     if (g_group) check(rmr_group_sync(g_group), "Sync");

@@ -61,6 +61,13 @@ public:
     // envTex of skyColor (Graphics.cpp:287 loads it from data/textures/veranda_1k.hdr): RGBA8, row
     // 0 = up; used when the params' use_env_tex is set. nullptr removes it.
     static void setEnvMap(const unsigned char* rgba8, int w, int h);
+    // Preview denoiser (rmr_denoise with `iterations` passes, the other parameters at their
+    // defaults) and what SaveImage writes afterwards: RMR_OUTPUT_ACCUM (default) or
+    // RMR_OUTPUT_DENOISED (rmr_set_output_source). Single-context mode only: with setDevices both
+    // fail with RMR_E_UNSUPPORTED and a message (rank 0 can denoise the reduced frame through
+    // rmr_write_accum / a bound accumulator).
+    static void Denoise(int iterations = 5);
+    static void setOutputSource(int source);
     static void Sync();
     static bool saveCheckpoint(const std::string& path, unsigned samplesDone);
     static bool loadCheckpoint(const std::string& path, unsigned* samplesDone);

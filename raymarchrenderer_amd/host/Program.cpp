@@ -57,6 +57,8 @@ struct Options {
     bool per_sample = false, interactive = false, quiet = false;
     bool print_tiles = false, print_view = false;  // host-only diagnostics (no GPU needed)
     rmr_params params;
+    int denoise = -1;               // --denoise [N]: a-trous iterations, -1 = no denoise
+    std::string aov;                // --aov PREFIX: guide planes as PREFIX_*.pfm
     bool have_camera = false;
     double cam[6] = {0, 4, -6, 0, -3, 6};
 };
@@ -234,6 +236,39 @@ RenderResult render(const Options& o, unsigned first_pass) {
     return r;
 }
 
+// --aov PREFIX: the first-hit guide planes as float images (rmr_encode_pfm): PREFIX_normal.pfm,
+// PREFIX_position.pfm, PREFIX_ray.pfm (the planes' xyz) and PREFIX_depth_id.pfm (R = t, G = id, B = 0)
+bool write_aovs(const Options& o) {
+    rmr_ctx* c = Graphics::context();
+    const int W = (int)Graphics::getImageSize().x, H = (int)Graphics::getImageSize().y;
+    auto fail = [&](const std::string& what) {
+        std::cerr << "--aov: " << what << ": " << rmr_last_error(c) << std::endl;
+        return false;
+    };
+    if (rmr_render_guides(c, 0, 0, W, H) != RMR_OK) return fail("rmr_render_guides");
+    const size_t n = (size_t)W * H * 4;
+    std::vector<float> ray(n), hit(n), nrm(n), di(n, 0.0f);
+    if (rmr_read_guide(c, RMR_GUIDE_RAY, ray.data(), n * sizeof(float)) != RMR_OK ||
+        rmr_read_guide(c, RMR_GUIDE_HIT, hit.data(), n * sizeof(float)) != RMR_OK ||
+        rmr_read_guide(c, RMR_GUIDE_NORMAL, nrm.data(), n * sizeof(float)) != RMR_OK)
+        return fail("rmr_read_guide");
+    for (size_t i = 0; i < (size_t)W * H; i++) {
+        di[4 * i] = hit[4 * i + 3];
+        di[4 * i + 1] = nrm[4 * i + 3];
+    }
+    const struct { const char* name; const std::vector<float>* img; } files[] = {
+        {"_normal.pfm", &nrm}, {"_position.pfm", &hit}, {"_ray.pfm", &ray}, {"_depth_id.pfm", &di}};
+    for (const auto& f : files) {
+        const std::string path = o.aov + f.name;
+        if (rmr_encode_pfm(f.img->data(), W, H, path.c_str()) != RMR_OK) {
+            std::cerr << "--aov: cannot write " << path << std::endl;
+            return false;
+        }
+        if (!o.quiet) std::cout << "Saved plane as: " << path << std::endl;
+    }
+    return true;
+}
+
 void report(const Options& o, const RenderResult& r) {
     std::cout << "Render Time: " << r.seconds << std::endl;  // Program.cpp:297
     if (!o.quiet && r.seconds > 0)
@@ -326,6 +361,10 @@ void usage() {
         "  --frame F           seed schedule frame: time = 1000 F + 0.016 s\n"
         "  --per-sample        one Graphics::Render launch per sample per tile (reference pattern)\n"
         "  --out FILE.bmp      (default output/<timestamp>.bmp)\n"
+        "  --denoise [N]       after the render, filter the image with N a-trous iterations (0..8, default 5)\n"
+        "                      and write --out from the denoised image\n"
+        "  --aov PREFIX        first-hit planes as float PFM: PREFIX_normal.pfm, PREFIX_position.pfm,\n"
+        "                      PREFIX_ray.pfm, PREFIX_depth_id.pfm (R = t, G = material id or -1, B = 0)\n"
         "  --checkpoint FILE   write the float accumulator at the end; --resume FILE continue from one\n"
         "  --device N  --interactive (CLI.cpp commands on stdin)  --scene-dir DIR  --quiet\n"
         "  --gpus N | --devices a,b,..  the frame tile-partitioned over those GPUs (one process, RCCL reduce)");
@@ -366,6 +405,16 @@ bool parse(int argc, char** argv, Options& o) {
         } else if (a == "--frame") o.frame = std::atoi(next("--frame"));
         else if (a == "--per-sample") o.per_sample = true;
         else if (a == "--out") o.out = next("--out");
+        else if (a == "--denoise") {   // the count is optional: taken when the next argument is a number
+            o.denoise = 5;
+            if (i + 1 < argc && argv[i + 1][0] != '\0' && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1])) {
+                o.denoise = std::atoi(argv[++i]);
+                if (o.denoise > 8 || std::strlen(argv[i]) > 2) return false;
+            }
+        } else if (a == "--aov") {
+            o.aov = next("--aov");
+            if (o.aov.empty()) return false;
+        }
         else if (a == "--checkpoint") o.checkpoint = next("--checkpoint");
         else if (a == "--resume") o.resume = next("--resume");
         else if (a == "--device") o.device = std::atoi(next("--device"));
@@ -428,8 +477,8 @@ int main(int argc, char** argv) {
     Screen::setScreenSize(Vector2(1280, 720));  // Program.cpp:89
     Graphics::setDevice(o.device);
     if (!o.devices.empty()) {
-        if (!o.checkpoint.empty() || !o.resume.empty() || o.interactive) {
-            std::fprintf(stderr, "--gpus / --devices: no checkpoint, resume or interactive mode\n");
+        if (!o.checkpoint.empty() || !o.resume.empty() || o.interactive || o.denoise >= 0 || !o.aov.empty()) {
+            std::fprintf(stderr, "--gpus / --devices: no checkpoint, resume, interactive mode, --denoise or --aov\n");
             return 2;
         }
         Graphics::setDevices(o.devices);
@@ -454,8 +503,14 @@ int main(int argc, char** argv) {
     const RenderResult r = render(o, 0);
     if (Graphics::lastStatus() != RMR_OK) return 1;
     report(o, r);
+    if (o.denoise >= 0) {
+        Graphics::Denoise(o.denoise);
+        if (Graphics::lastStatus() != RMR_OK) return 1;
+        Graphics::setOutputSource(RMR_OUTPUT_DENOISED);
+    }
     save(o);
-    const int rc = Graphics::lastStatus() == RMR_OK ? 0 : 1;
+    int rc = Graphics::lastStatus() == RMR_OK ? 0 : 1;
+    if (rc == 0 && !o.aov.empty() && !write_aovs(o)) rc = 1;
     Graphics::Shutdown();
     return rc;
 }

@@ -317,6 +317,72 @@ class Renderer:
                                                    float(vmin[0]), float(vmin[1]), float(vmax[0]), float(vmax[1]),
                                                    int(screen_w), int(screen_h), C.c_void_p(dev_ptr), int(nbytes)))
 
+    # -- first-hit guides and the preview denoiser --
+    def render_guides(self, rect=None):
+        """rmr_render_guides: the first-hit guide planes of the integer rect (the whole image without
+        one). The guides are valid once a call covers the whole image."""
+        if rect is None:
+            w, h = self.image_size()
+            rect = (0, 0, w, h)
+        x0, y0, x1, y1 = (int(v) for v in rect)
+        self._chk(self._L.rmr_render_guides(self._ctx, x0, y0, x1, y1))
+
+    def read_guide(self, plane):
+        """One guide plane as an (H, W, 4) float32 array; plane: abi.GUIDE_* or 'ray' / 'hit' / 'normal'."""
+        if isinstance(plane, str):
+            if plane not in abi.GUIDE_PLANES:
+                raise ValueError("read_guide: unknown plane %r (ray, hit, normal)" % plane)
+            plane = abi.GUIDE_PLANES[plane]
+        w, h = self.image_size()
+        out = np.zeros((h, w, 4), np.float32)
+        self._chk(self._L.rmr_read_guide(self._ctx, int(plane), _fp(out), out.nbytes))
+        return out
+
+    def read_guides(self):
+        """The three guide planes: {'ray': (dir, 0), 'hit': (pos, t), 'normal': (normal, id) or
+        (0, 0, 0, -1) for a miss}, each (H, W, 4) float32."""
+        return {name: self.read_guide(plane) for name, plane in abi.GUIDE_PLANES.items()}
+
+    def guide_device_ptr(self, plane):
+        if isinstance(plane, str):
+            if plane not in abi.GUIDE_PLANES:
+                raise ValueError("guide_device_ptr: unknown plane %r (ray, hit, normal)" % plane)
+            plane = abi.GUIDE_PLANES[plane]
+        return self._L.rmr_guide_device_ptr(self._ctx, int(plane))
+
+    def denoise(self, params=None, **kw):
+        """rmr_denoise: filter the accumulator (left unchanged) and return the denoised image (H, W, 4).
+        Keywords: iterations (5; 0..8), normal_pow2 (5; 0..7), sigma_z (0.02; > 0), sigma_c (0 = off)."""
+        if params is not None and not isinstance(params, abi.DenoiseParams):
+            raise TypeError("denoise: params must be an abi.DenoiseParams")
+        p = abi.default_denoise_params() if params is None else abi.DenoiseParams.from_buffer_copy(params)
+        for k, v in kw.items():
+            if k not in ("iterations", "normal_pow2", "sigma_z", "sigma_c"):
+                raise TypeError("denoise: unknown parameter %r" % k)
+            setattr(p, k, v)
+        self._chk(self._L.rmr_denoise(self._ctx, C.byref(p)))
+        return self.read_denoised()
+
+    def read_denoised(self):
+        w, h = self.image_size()
+        out = np.zeros((h, w, 4), np.float32)
+        self._chk(self._L.rmr_read_denoised(self._ctx, _fp(out), out.nbytes))
+        return out
+
+    def denoised_device_ptr(self):
+        """Device pointer of the valid denoised image (W x H float4), None without one."""
+        return self._L.rmr_denoised_device_ptr(self._ctx)
+
+    def set_output_source(self, source):
+        """What save_bmp / display / display_device read: abi.OUTPUT_ACCUM (default) or
+        abi.OUTPUT_DENOISED (also 'accum' / 'denoised')."""
+        if isinstance(source, str):
+            names = {"accum": abi.OUTPUT_ACCUM, "denoised": abi.OUTPUT_DENOISED}
+            if source not in names:
+                raise ValueError("set_output_source: unknown source %r (accum, denoised)" % source)
+            source = names[source]
+        self._chk(self._L.rmr_set_output_source(self._ctx, int(source)))
+
     def stats(self):
         s = abi.Stats()
         self._chk(self._L.rmr_get_stats(self._ctx, C.byref(s)))
@@ -360,6 +426,18 @@ def encode_bmp(rgba, path):
     rc = lib().rmr_encode_bmp(_fp(a), w, h, path.encode())
     if rc != abi.RMR_OK:
         raise RMRError(rc, "rmr_encode_bmp(%s)" % path)
+
+
+def encode_pfm(rgba, path):
+    """rmr_encode_pfm: a host RGBA32F image (h, w, 4) as a colour PFM (RGB float32, little-endian,
+    rows bottom to top; alpha dropped). No GPU needed."""
+    a = np.ascontiguousarray(rgba, np.float32)
+    if a.ndim != 3 or a.shape[2] != 4 or a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError("encode_pfm: rgba must be a non-empty (h, w, 4) image, got shape %s" % (a.shape,))
+    h, w = a.shape[:2]
+    rc = lib().rmr_encode_pfm(_fp(a), w, h, path.encode())
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_encode_pfm(%s)" % path)
 
 
 # ------------------------------------------------------------------------------------------
