@@ -643,6 +643,16 @@ int launch_precheck(rmr_ctx* c) {
     return RMR_OK;
 }
 
+// KParams::am_dmax (rmr_trace.h am_far): the largest float strictly below maxDist - (2^-20 (maxDist + 2 R)
+// + 2^-39), twice the approximate minimum's error bound at maxDist, computed in double and rounded
+// down; -inf (every lane takes the exact fold) where that is not positive or maxDist is not finite.
+float am_direct_bound(float max_dist, float am_r2) {
+    if (!std::isfinite(max_dist) || !std::isfinite(am_r2)) return -INFINITY;
+    const double b = (double)max_dist - (((double)max_dist + (double)am_r2) * 0x1p-20 + 0x1p-39);
+    const float f = std::nextafter((float)b, -INFINITY);
+    return f > 0.0f ? f : -INFINITY;
+}
+
 // The view, the render parameters, the env map and the buffers on top of the scene's parameters.
 int view_params(rmr_ctx* c, KParams& P) {
     P = c->scene_kp;
@@ -660,6 +670,7 @@ int view_params(rmr_ctx* c, KParams& P) {
     P.env = c->d_env; P.env_w = c->env_w; P.env_h = c->env_h;
     P.use_env = (c->params.use_env_tex != 0 && c->d_env) ? 1 : 0;
     P.max_dist = c->params.max_dist; P.step_mult = c->params.step_multiply;
+    P.am_dmax = am_direct_bound(P.max_dist, P.am_r2);
     P.max_steps = c->params.max_steps; P.max_bounces = c->params.max_bounces;
     P.separate_channels = c->params.separate_channels;
     for (int i = 0; i < 3; i++) {

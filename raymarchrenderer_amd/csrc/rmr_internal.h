@@ -66,6 +66,10 @@ struct KParams {
     const DMat* dmats;          // per-id shading kind (RM1)
     const BvhNode* bvh;         // NP = -2: node array (n_nodes), prims in dprims in leaf order
     int32_t n_nodes;
+    // approximate minimum below which the exact one is < max_dist (rmr_trace.h am_far); in the four bytes
+    // that pad n_nodes to the next pointer, so that no other field moves (a field added further down
+    // changed the kernels' scalar-load grouping and SGPR spills: RM3 +25 instructions)
+    float am_dmax;
     // candidate grid of the nearest-primitive cache's full map() (rmr_trace.h map_grid_npc; null =
     // none): per cell x = list offset | count << 24 (count 255: no list, take the BVH), y = float bits
     // of a lower bound of every non-listed primitive's float distance in the cell, z / w = the list's

@@ -578,7 +578,28 @@ RMR_D bool am_unique(const AMin& m, float R2) {   // R2 = 2 R
 // exact result of a unique fold: opU((maxDist, -1), d_w, id_w); d_w = sqrt_cr(len2) + k is the same
 // expression as sd_box (k + length) and sd_sphere (length - r == length + (-r)). sqrt_cr_big: the
 // tiny range is excluded by am_unique (those lanes take the exact fold).
+//
+// RMR_AM_DIRECT: the result is (d_w, id_w) itself, without the opU against (maxDist, -1). opU
+// changes that pair only when d_w > maxDist (d_w == maxDist takes both; a NaN d_w cannot occur: len2 is
+// >= 0 and k finite once am_unique holds), so a lane whose d_w may reach maxDist takes the exact fold
+// instead (am_far joins the generated fallback test). With err(a) = 2^-21 (|a| + R) + 2^-40 the
+// approximate minimum's error bound (above), d_w <= a + err(a), and the host's bound
+//   am_dmax = RD(maxDist - (2^-20 (maxDist + 2 R) + 2^-39))        (rmr_api.cpp am_direct_bound)
+// gives for every a < am_dmax: a >= 0: a + err(a) < am_dmax + 2^-21 (maxDist + R) + 2^-40 < maxDist; a < 0:
+// a + err(a) <= 2^-21 R + 2^-40 < maxDist, as am_dmax > 0 says (else the host passes -inf: every lane
+// takes the exact fold). One compare per map() instead of opU's two compares, two selects and a move.
+// A NaN a fails a < am_dmax and lands in the fallback.
+// The hipRTC source of RM1's approximate-map kernels asks for it (rmr_jit.cpp: Cornell-5 -2.1%; RM2 and
+// RM3 measured neutral to +1% with it and keep the opU).
+#ifndef RMR_AM_DIRECT
+#define RMR_AM_DIRECT 0   // (0: the opU against (maxDist, -1) in every map())
+#endif
+RMR_D bool am_far(const KParams& P, const AMin& m) {
+    if (RMR_AM_DIRECT) return !(m.a < P.am_dmax);
+    return false;
+}
 RMR_D V2 am_result(const KParams& P, const AMin& m) {
+    if (RMR_AM_DIRECT) return v2(sqrt_cr_big(m.l2) + m.k, m.id);
     V2 d = v2(P.max_dist, -1.0f);
     opu(d, sqrt_cr_big(m.l2) + m.k, m.id);
     return d;
@@ -594,6 +615,7 @@ RMR_D float am_pack(float id, int j) { return __int_as_float(__float_as_int(id) 
 RMR_D float am_id_of(float packed) { return __int_as_float(__float_as_int(packed) & ~0xff); }
 RMR_D int am_w_of(float packed) { return __float_as_int(packed) & 0xff; }
 RMR_D V2 am_result_packed(const KParams& P, const AMin& m) {
+    if (RMR_AM_DIRECT) return v2(sqrt_cr_big(m.l2) + m.k, am_id_of(m.id));   // (see am_result)
     V2 d = v2(P.max_dist, -1.0f);
     opu(d, sqrt_cr_big(m.l2) + m.k, am_id_of(m.id));
     return d;
@@ -1547,9 +1569,21 @@ RMR_D void begin_trace(const KParams& P, Lane& L, uint32_t u, bool fresh) {
 // by the few lanes each refill starts) and kept in LDS: (dir.xyz, randChange after the 3 jitter
 // rand() calls) and (gid.x + time, gid.y + time, time, escape bound of the primary ray or NaN
 // outside the clip rect).
+//
+// EYEC (lane-slot kernels, RMR_EYE_CHUNK): the primary ray's first march step rides with the chunk's
+// rays. The eye's map() is one value per launch (trace_main eye_map), and where its outcome is "march
+// on" the step's t1 = fma(map(eye).x, stepMultiply, 0) > 0 is wave-uniform; what march_update would
+// make of a fresh lane (t = 0, ctr = 0, outside) is then either (t, ctr) = (t1, 1), or its miss
+// (t = maxDist, mid = -1) when t1 passes the ray's own escape bound. b.z carries the ray's first t in
+// the place of the sample's time (RM2's seed, which no RM1 lane reads): t1, or 0 for a direction that is
+// not finite (its march point at t = 0 is not the eye: the lane starts as it always did, with the
+// map() of its own point) and for every ray when t1 = 0 (no uniform "march on": trace_main keeps the
+// per-refill step). A ray whose t1 passes its bound gets the bound -1: start_march_te then parks it as
+// the miss at once, the state march_update's miss has but for ctr (0 instead of 1) and texit, which
+// nothing reads after a miss: the park step stores color x sky from L.color and L.d alone.
 struct ChunkRay { float4 a, b; };
-template <bool HO, bool OPQ = false>
-RMR_D ChunkRay chunk_ray(const KParams& P, uint32_t u) {
+template <bool HO, bool OPQ = false, bool EYEC = false>
+RMR_D ChunkRay chunk_ray(const KParams& P, uint32_t u, float t1 = 0.0f) {
     int px, py;
     float time, rc = 0.0f;
     ChunkRay r;
@@ -1562,10 +1596,16 @@ RMR_D ChunkRay chunk_ray(const KParams& P, uint32_t u) {
     }
     r.a = make_float4(dir.x, dir.y, dir.z, rc);
     r.b = make_float4((float)px + time, (float)py + time, time, te);
+    if constexpr (EYEC) {
+        const float dsum = (dir.x + dir.y) + dir.z;   // NaN for a NaN / infinite direction
+        const float t0 = (dsum - dsum == 0.0f) ? t1 : 0.0f;
+        r.b.z = t0;
+        r.b.w = (t0 > te) ? -1.0f : te;   // (a NaN te, outside the clip rect, stays)
+    }
     return r;
 }
 // begin_trace for a fresh unit whose primary ray is in LDS
-template <int VAR, bool HO>
+template <int VAR, bool HO, bool EYEC = false>
 RMR_D void begin_unit(const KParams& P, Lane& L, uint32_t u, float4 a, float4 b) {
     if (!(b.w == b.w)) {   // outside the clip rect
         L.phase = PH_IDLE;
@@ -1575,14 +1615,21 @@ RMR_D void begin_unit(const KParams& P, Lane& L, uint32_t u, float4 a, float4 b)
     L.cw2 = 0;
     L.cs = -__builtin_inff();
     L.unit = u;
-    L.time = b.z;
+    L.time = EYEC ? 0.0f : b.z;
     L.gxt = b.x;
     L.gyt = b.y;
     L.rc = a.w;
     L.chan = (VAR != RMR_VARIANT_RM3 && P.separate_channels != 0) ? 0 : -1;
     const V3 dir = v3(a.x, a.y, a.z);
     for (;;) {  // a zero-bounce trace finishes at once (and may start the next channel)
-        if (trace_prologue<VAR, HO>(P, L, dir, b.w)) return;   // the escape bound from chunk_ray
+        if (trace_prologue<VAR, HO>(P, L, dir, b.w)) {   // the escape bound from chunk_ray
+            if constexpr (EYEC) {   // the first step (chunk_ray): b.z = its t, 0 = none taken
+                const bool run = L.phase == PH_MARCH;
+                L.t = run ? b.z : L.t;
+                L.ctr = (run && b.z > 0.0f) ? 1 : 0;
+            }
+            return;
+        }
         if (finish_trace<VAR, HO>(P, L)) {
             L.phase = PH_DONE;
             return;
@@ -1603,7 +1650,10 @@ RMR_D void begin_unit(const KParams& P, Lane& L, uint32_t u, float4 a, float4 b)
 // cache's bound — a hit whose six probes all stay within the cached primitive's validity (each probe
 // would be served by the cache, F_w(probe) < cs - delta - eps) parks in PH_HIT with ctr = -1 too
 // PACKW (lane-slot kernels): the certified primitive rides in the hit's ctr = -1 - w, no L.cw
-template <bool HO, bool CACHE = false, bool PACKW = false>
+// BP (batch probes, RMR_BATCH_PROBES): an uncertified hit parks in PH_HIT as well, with ctr = 0 (a
+// certified one has ctr < 0); its six probes run in the shading batch (probe_normals), so the lane
+// never enters PH_NORMAL and carries no probe offset e
+template <bool HO, bool CACHE = false, bool PACKW = false, bool BP = false>
 RMR_D void march_update(const KParams& P, Lane& L, V2 m, int w = 0, bool cert = false, V3 p = V3{0.0f, 0.0f, 0.0f}) {
     if constexpr (HO && !CACHE) {   // (cache kernels: A/B neutral-negative)
         // HO kernels (no shadow rays): the same state transitions as below as per-lane selects
@@ -1617,10 +1667,10 @@ RMR_D void march_update(const KParams& P, Lane& L, V2 m, int w = 0, bool cert = 
         const float tf = hit0 ? L.t : (miss ? P.max_dist : tn);
         const bool probe = hit && !cert;
         L.t = tf;   // (o stays the ray origin: the shading batch writes the point, init_probe)
-        L.e = v3(probe ? 0.001f : L.e.x, probe ? 0.0f : L.e.y, probe ? 0.0f : L.e.z);
+        if constexpr (!BP) L.e = v3(probe ? 0.001f : L.e.x, probe ? 0.0f : L.e.y, probe ? 0.0f : L.e.z);
         L.mid = hit ? m.y : (miss ? -1.0f : L.mid);
         L.ctr = hit ? (cert ? (PACKW ? -1 - w : -1) : 0) : cn;
-        L.phase = hit ? (cert ? PH_HIT : PH_NORMAL) : (miss ? PH_MISS : L.phase);
+        L.phase = hit ? ((BP || cert) ? PH_HIT : PH_NORMAL) : (miss ? PH_MISS : L.phase);
         if constexpr (!PACKW) L.cw = cert ? w : L.cw;
         return;
     }
@@ -1731,8 +1781,12 @@ RMR_D void normal_update(Lane& L, float m) {
 // nrm = (m0 - m1, m2 - m3, m4 - m5), normalised in shade() as every normal.
 // Runs with every lane of the wave active (bpermute reads the owners' registers).
 // (AT, lane-slot kernels: L is a waiting path's event from its LDS slot, whose o is the hit point already)
-template <bool AT = false>
-RMR_D void cert_normals(const KParams& P, Lane& L, bool mine, uint64_t cm, int* tab, const float4* dtab) {
+//
+// spread_probes is that flattening for any probe evaluation: value(own, act, q) returns map(q).x for the
+// probe q of the owner in lane `own` (act: this lane has a probe in this pass), and may fetch more of the
+// owner's registers with ds_bpermute; it is called once per pass with every lane active.
+template <bool AT, class VALUE>
+RMR_D void spread_probes(Lane& L, bool mine, uint64_t cm, int* tab, VALUE value) {
     const int lane = (int)__lane_id();
     const int n = __popcll(cm);
     const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u));
@@ -1750,15 +1804,11 @@ RMR_D void cert_normals(const KParams& P, Lane& L, bool mine, uint64_t cm, int* 
         const float hx = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * own, __float_as_int(hp.x)));
         const float hy = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * own, __float_as_int(hp.y)));
         const float hz = __int_as_float(__builtin_amdgcn_ds_bpermute(4 * own, __float_as_int(hp.z)));
-        const int w = __builtin_amdgcn_ds_bpermute(4 * own, L.cw);
         // e_c: (+h,+0,+0) (-h,-0,-0) (+0,+h,+0) (-0,-h,-0) (+0,+0,+h) (-0,-0,-h)
         const float sg = (c & 1) ? -1.0f : 1.0f;
         const int ax = c >> 1;
         const V3 e = v3(sg * (ax == 0 ? 0.001f : 0.0f), sg * (ax == 1 ? 0.001f : 0.0f), sg * (ax == 2 ? 0.001f : 0.0f));
-        float mid;
-        int j;
-        const float F = prim_dist_tab(dtab + kTabStep * (act ? w : 0), v3(hx, hy, hz) + e, mid, j);
-        const float val = (P.max_dist >= F) ? F : P.max_dist;   // opu(d = (maxDist, -1), F, .).x
+        const float val = value(own, act, v3(hx, hy, hz) + e);
 #pragma unroll
         for (int k = 0; k < 6; k++) {   // owners collect the values of this pass
             const int gk = 6 * rank + k;
@@ -1768,6 +1818,33 @@ RMR_D void cert_normals(const KParams& P, Lane& L, bool mine, uint64_t cm, int* 
     }
     __builtin_amdgcn_wave_barrier();   // (tab is rewritten by the next batch)
     if (mine) L.nrm = v3(v[0] - v[1], v[2] - v[3], v[4] - v[5]);
+}
+template <bool AT = false>
+RMR_D void cert_normals(const KParams& P, Lane& L, bool mine, uint64_t cm, int* tab, const float4* dtab) {
+    spread_probes<AT>(L, mine, cm, tab, [&](int own, bool act, V3 q) {
+        const int w = __builtin_amdgcn_ds_bpermute(4 * own, L.cw);
+        float mid;
+        int j;
+        const float F = prim_dist_tab(dtab + kTabStep * (act ? w : 0), q, mid, j);
+        return (P.max_dist >= F) ? F : P.max_dist;   // opu(d = (maxDist, -1), F, .).x
+    });
+}
+// getNormal of the uncertified hits (batch probes, RMR_BATCH_PROBES; march_update BP: PH_HIT with
+// ctr = 0), by the same flattening after cert_normals: probe c of the uncertified lane of rank r is the
+// whole map, MAP::eval(P, hp + e_c).x, on lane (6 r + c) mod 64, instead of six map-loop iterations of
+// the hit's own lane. Why each value keeps the bits the in-loop probe had:
+//  * the in-loop probe point is march_point = fma(d, t, o) + e with t the hit's t, and e cycled by
+//    normal_update through exactly the six e_c above (signed zeros included); here hp is fma(d, t, o)
+//    as well — the park step stores that expression (slot_put_event), the in-register batch forms it —
+//    and ds_bpermute moves the three words unchanged, so hp + e_c is the same addition of the same bits;
+//  * the in-loop value is eval_c(P, p, w, cert).x, and MAP::eval is eval_c with w and cert dropped: the
+//    same function of the point, and no lane of a wave reads another's state in it;
+//  * the owner forms (m0 - m1, m2 - m3, m4 - m5), normal_update's three subtractions (its shift
+//    register only moves the differences), normalised in shade() as every normal.
+// A helper lane without a probe in its pass evaluates the first owner's probe and nobody reads it.
+template <bool AT, class MAP>
+RMR_D void probe_normals(const KParams& P, Lane& L, bool mine, uint64_t um, int* tab) {
+    spread_probes<AT>(L, mine, um, tab, [&](int, bool, V3 q) { return MAP::eval(P, q).x; });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2207,7 +2284,8 @@ RMR_D void cold_get(float (*s)[256], int t, Lane& L) {
 // or as the next ray ready to march. The fields a path keeps through both states share their words:
 //   word   event (slot_put_event)                ray (slot_put_ray)
 //   0-2    hit point fma(d, t, o)                origin
-//   3-5    getNormal differences (uncertified)   direction
+//   3-5    getNormal differences (uncertified    direction
+//          hits probed in the map loop)
 //   6-8    throughput                            throughput
 //   9      rc (RNG chain)                        rc
 //   10-12  gxt, gyt, unit                        (kept)
@@ -2219,31 +2297,48 @@ RMR_D void cold_get(float (*s)[256], int t, Lane& L) {
 // RM1 without separateChannels and without node-program materials only (chan = -1; inside = false:
 // rm1_after_material's ni stays 0; no RM2 / RM3 fields), inline maps (cw < 256).
 constexpr int kSlotWords = 17;
+// (BP, batch probes: an uncertified hit has no normal yet either, ctr = 0; words 3-5 stay unused)
+template <bool BP = false>
 RMR_D void slot_put_event(float (*s)[256], int t, const Lane& L, V3 hp) {
     s[0][t] = hp.x; s[1][t] = hp.y; s[2][t] = hp.z;
-    if (L.ctr >= 0) { s[3][t] = L.nrm.x; s[4][t] = L.nrm.y; s[5][t] = L.nrm.z; }
+    if constexpr (!BP) {
+        if (L.ctr >= 0) { s[3][t] = L.nrm.x; s[4][t] = L.nrm.y; s[5][t] = L.nrm.z; }
+    }
     s[6][t] = L.color.x; s[7][t] = L.color.y; s[8][t] = L.color.z;
     s[9][t] = L.rc;
     s[10][t] = L.gxt; s[11][t] = L.gyt;
     s[12][t] = s[16][t];
-    // (ctr = -1 - cw of a certified hit, march_update PACKW; 6 after an uncertified hit's probes)
+    // (ctr = -1 - cw of a certified hit, march_update PACKW; 6 after an uncertified hit's probes, 0
+    // for an uncertified hit whose probes the batch runs)
     s[13][t] = __int_as_float((L.bounces << 9) | (L.ctr < 0 ? (((-1 - L.ctr) & 0xff) << 1) | 1 : 0));
     s[15][t] = L.mid;
 }
 // the event as a lane in PH_HIT before its shading (o = the hit point, as the in-register batch sets it)
-RMR_D void slot_get_event(float (*s)[256], int t, Lane& E) {
+// (BP: every hit's differences come from the batch, cert_normals or probe_normals by the sign of ctr)
+// In two parts: what the batch's probes read (the hit point, the certificate), and what only shade()
+// reads. With batch probes the second part is read after the probes: the whole map() of
+// probe_normals then runs beside the marching lane with eight registers fewer alive.
+template <bool BP = false>
+RMR_D void slot_get_hit(float (*s)[256], int t, Lane& E) {
     E.o = v3(s[0][t], s[1][t], s[2][t]);
-    E.nrm = v3(s[3][t], s[4][t], s[5][t]);
-    E.color = v3(s[6][t], s[7][t], s[8][t]);
-    E.rc = s[9][t];
-    E.gxt = s[10][t]; E.gyt = s[11][t];
-    E.unit = __float_as_uint(s[12][t]);
+    E.nrm = BP ? v3s(0.0f) : v3(s[3][t], s[4][t], s[5][t]);
     const int pk = __float_as_int(s[13][t]);
     E.bounces = pk >> 9;
     E.cw = (pk >> 1) & 0xff;
     E.inside = false;
-    E.ctr = (pk & 1) ? -1 : 6;
+    E.ctr = (pk & 1) ? -1 : (BP ? 0 : 6);
+}
+RMR_D void slot_get_shading(float (*s)[256], int t, Lane& E) {
+    E.color = v3(s[6][t], s[7][t], s[8][t]);
+    E.rc = s[9][t];
+    E.gxt = s[10][t]; E.gyt = s[11][t];
+    E.unit = __float_as_uint(s[12][t]);
     E.mid = s[15][t];
+}
+template <bool BP = false>
+RMR_D void slot_get_event(float (*s)[256], int t, Lane& E) {
+    slot_get_hit<BP>(s, t, E);
+    slot_get_shading(s, t, E);
 }
 RMR_D void slot_put_ray(float (*s)[256], int t, const Lane& E) {
     s[0][t] = E.o.x; s[1][t] = E.o.y; s[2][t] = E.o.z;
@@ -2406,6 +2501,20 @@ static_assert(RMR_QUEUE_PARTS >= 1 && RMR_QUEUE_PARTS <= 64 && RMR_QUEUE_PARTS *
 #ifndef RMR_CHUNK_SLOTS
 #define RMR_CHUNK_SLOTS 64   // units per work claim of the lane-slot kernels (8 KiB of chunk rays + 17 KiB of slots)
 #endif
+// Batch probes (lane-slot kernels only; the hipRTC source asks for them with the lane slots, rmr_jit.cpp):
+// getNormal's six probes of a hit the certificate does not cover run in the shading batch, spread
+// over the wave (probe_normals), instead of as six map-loop iterations of the hit's lane. The map
+// loop then evaluates fma(d, t, o) alone and applies march_update to every active lane: no probe
+// offset, no PH_NORMAL test, no normal_update, and the marching lane carries neither e nor nrm. An
+// uncertified hit that ends its path (the park step's "cheap" events) gets no probes at all, as a
+// certified one.
+#ifndef RMR_BATCH_PROBES
+#define RMR_BATCH_PROBES 0
+#endif
+// the primary ray's first march step with the chunk's rays (chunk_ray EYEC; lane-slot kernels only)
+#ifndef RMR_EYE_CHUNK
+#define RMR_EYE_CHUNK 1   // (0: as a march_update of the fresh lanes at every refill, A/B)
+#endif
 typedef uint32_t WCount;
 template <int VAR, class MAP, bool PERSIST, bool PROG, class MATS = TableMats>
 RMR_D void trace_main(const KParams& P) {
@@ -2433,6 +2542,8 @@ RMR_D void trace_main(const KParams& P) {
     // separateChannels and without an env map only: the host picks the code object, rmr_api.cpp)
     constexpr bool SLOTS = RMR_LANE_SLOTS && PERSIST && VAR == RMR_VARIANT_RM1 && CERT && MAP::kCert && !MAP::kCache &&
                            !MAP::kStepped;
+    constexpr bool BP = SLOTS && RMR_BATCH_PROBES;   // uncertified hits' probes in the shading batch
+    constexpr bool EYEC = SLOTS && RMR_EYE_CHUNK;    // the eye step with the chunk's rays
     constexpr uint32_t CHUNK = MAP::kCache ? RMR_CHUNK_CACHE : (SLOTS ? RMR_CHUNK_SLOTS : RMR_CHUNK);
     const uint32_t n_units = (uint32_t)P.n_units;   // < 2^32 per launch (host chunking)
     // units per claim: the LDS ray buffer's CHUNK, or fewer for a small launch (the host's chunk_units)
@@ -2482,10 +2593,22 @@ RMR_D void trace_main(const KParams& P) {
         meye = v2(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(meye.x))),
                   __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(meye.y))));
     }
+    // EYEC: the step's wave-uniform outcome, once per launch. "March on" = no hit at the eye (dist >=
+    // 0.001; a NaN fails), more than one step allowed, and 0 < t1 < maxDist (so t = 0 is not past
+    // maxDist either): chunk_ray / begin_unit then hand every fresh lane the state march_update would
+    // leave. Otherwise (an eye within 0.001 of a surface, max_steps <= 1, a step to or past maxDist,
+    // stepMultiply <= 0) eye_t1 = 0 and the launch keeps the per-refill march_update below.
+    float eye_t1 = 0.0f;
+    if (EYEC && eye1) {
+        const float t1 = fmaf(meye.x, P.step_mult, 0.0f);
+        if (meye.x >= 0.001f && P.max_steps > 1 && t1 > 0.0f && t1 < P.max_dist) eye_t1 = t1;
+        eye_t1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(eye_t1)));   // (an SGPR)
+    }
 #ifdef RMR_PROFILE
     uint64_t cyc[4] = {0, 0, 0, 0};   // refill, map() iterations, shading, cache kernels: full map() batches
     uint64_t full_lanes = 0;           // cache kernels: lanes in the full map() batches
     uint64_t cyc_claim = 0, cyc_rays = 0;   // refill: work-queue claims (atomics), chunk primary rays
+    uint64_t uhits = 0, uhits_cheap = 0;    // lane-slot kernels: uncertified hits, those ending their path
     const uint64_t c_begin = __builtin_amdgcn_s_memtime();
 #define RMR_STAMP(v) const uint64_t v = __builtin_amdgcn_s_memtime()
 #else
@@ -2615,7 +2738,7 @@ RMR_D void trace_main(const KParams& P) {
                     if (!exhausted) {  // the chunk's primary rays, all 64 lanes at once
                         chunk_base = base;
                         for (uint32_t sl = lane_now(); sl < CK; sl += 64) {
-                            if (base + sl < rend) s_ray[wv][sl] = chunk_ray<HO, SLOTS>(P, base + sl);
+                            if (base + sl < rend) s_ray[wv][sl] = chunk_ray<HO, SLOTS, EYEC>(P, base + sl, eye_t1);
                         }
                         __builtin_amdgcn_wave_barrier();
 #ifdef RMR_PROFILE
@@ -2648,7 +2771,7 @@ RMR_D void trace_main(const KParams& P) {
                         s_rng[1][wv][ln] = cr.b.y;
                         s_rng[2][wv][ln] = cr.a.w;
                     }
-                    begin_unit<VAR, HO>(P, L, fu, cr.a, cr.b);
+                    begin_unit<VAR, HO, EYEC>(P, L, fu, cr.a, cr.b);
                     if constexpr (SLOTS) {
                         L.chan = -1;   // (launched without separateChannels: a constant)
                         s_slot[16][(wv << 6) + (int)lane_now()] = __uint_as_float(fu);
@@ -2661,11 +2784,13 @@ RMR_D void trace_main(const KParams& P) {
         } else if (__ballot(restart)) {
             if (restart) begin_trace<VAR, HO>(P, L, L.unit, false);
         }
-        if (eye1) {   // primary rays' first march step (eye_map above)
+        // primary rays' first march step (eye_map above); EYEC: taken with the chunk's rays unless the
+        // launch has no uniform "march on" (eye_t1 = 0)
+        if (eye1 && !(EYEC && eye_t1 > 0.0f)) {
             const float dsum = (L.d.x + L.d.y) + L.d.z;   // NaN for a NaN / infinite direction
             const bool first = (fresh || restart) && L.phase == PH_MARCH && (dsum - dsum == 0.0f);
             if (__ballot(first)) {
-                if (first) march_update<HO>(P, L, meye);
+                if (first) march_update<HO, false, false, BP>(P, L, meye);
             }
         }
         RMR_STAMP(c1);
@@ -2841,10 +2966,16 @@ RMR_D void trace_main(const KParams& P) {
             const int TL = SLOTS ? __popcll(__ballot(is_shade(L.phase))) + PK : T;
             for (;;) {
                 if (is_active(L.phase)) {
-                    const V3 p = RMR_MARCH_POINT(L);
+                    // (BP: every active lane marches; its point has no probe offset)
+                    const V3 p = BP ? vfma(L.d, L.t, L.o) : RMR_MARCH_POINT(L);
                     if constexpr (!MAP::kCounts)   // every primitive of the fold (Mandelbulb iterations: inside)
                         RMR_COUNT(P.counters, active_lanes(), (uint64_t)P.flops_static, (uint64_t)P.transc_static);
-                    if constexpr (MAP::kCert && HO) {
+                    if constexpr (BP) {
+                        int w;
+                        bool cert;
+                        const V2 m = MAP::eval_c(P, p, w, cert);
+                        march_update<HO, false, true, true>(P, L, m, w, cert);
+                    } else if constexpr (MAP::kCert && HO) {
                         int w;
                         bool cert;
                         const V2 m = MAP::eval_c(P, p, w, cert);
@@ -2877,7 +3008,11 @@ RMR_D void trace_main(const KParams& P) {
                     // expressions (chan < 0, no env map): a miss (color x sky); a hit that ends its path
                     // — any material but a diffuse one (emission: color x c x gray1; none: color x 0), or
                     // a diffuse hit at the last bounce, whose new direction only finish_trace would
-                    // follow (color x c on either branch). Such hits never enter cert_normals.
+                    // follow (color x c on either branch). Such hits never enter cert_normals (nor, with
+                    // batch probes, probe_normals: an uncertified hit's normal is as dead as a certified one's).
+#ifdef RMR_PROFILE
+                    const bool uhit0 = L.phase == PH_HIT && L.ctr >= 0;
+#endif
                     bool cheap = false;
                     if (sh) {
                         V3 nc = v3s(0.0f);
@@ -2905,6 +3040,15 @@ RMR_D void trace_main(const KParams& P) {
                         }
                     }
                     shaded += (WCount)__popcll(__ballot(cheap));
+#ifdef RMR_PROFILE
+                    // hits the certificate did not cover (ctr >= 0: 6 after in-loop probes, 0 with batch
+                    // probes), counted where their event is consumed; among them those that end their path
+                    {
+                        const bool uh = uhit0 && (cheap || sst != 1);
+                        uhits += (uint64_t)__popcll(__ballot(uh));
+                        uhits_cheap += (uint64_t)__popcll(__ballot(uh && cheap));
+                    }
+#endif
                     // a hit that goes on: its record to the lane's slot — if a ready ray waits there the
                     // lane takes it (swap), else it goes idle for the refill; with an event already in
                     // the slot the lane waits in registers for the batch below
@@ -2914,7 +3058,7 @@ RMR_D void trace_main(const KParams& P) {
                             const bool swap = sst == 2;
                             SlotRay r{};
                             if (swap) r = slot_read_ray(s_slot, st);
-                            slot_put_event(s_slot, st, L, vfma(L.d, L.t, L.o));
+                            slot_put_event<BP>(s_slot, st, L, vfma(L.d, L.t, L.o));
                             L.phase = PH_IDLE;
                             if (swap) slot_start_ray(s_slot, st, L, r);
                             L.e = v3s(-0.0f);
@@ -2930,7 +3074,8 @@ RMR_D void trace_main(const KParams& P) {
                 nev = 0;
                 const bool ev = sst == 1;
                 Lane E;
-                slot_get_event(s_slot, st, E);
+                if constexpr (BP) slot_get_hit<true>(s_slot, st, E);   // (the rest after the probes)
+                else slot_get_event(s_slot, st, E);
                 E.d = v3s(0.0f);
                 E.t = 0.0f;
                 E.hit = E.o;
@@ -2956,6 +3101,18 @@ RMR_D void trace_main(const KParams& P) {
                     RMR_COUNT(P.counters, (uint64_t)__popcll(bm), 6 * (22 + 2), 6);
                     RMR_COUNT(P.counters, (uint64_t)__popcll(cm & ~bm), 6 * (10 + 2), 6);
 #endif
+                }
+                if constexpr (BP) {   // the uncertified hits' probes: the whole map, spread the same way
+                    const bool mine = ev && E.ctr >= 0;
+                    const uint64_t um = __ballot(mine);
+                    if (um) {   // (wave-uniform: nothing runs when every event is certified)
+                        probe_normals<true, MAP>(P, E, mine, um, s_tab[wv]);
+                        maps += (WCount)(6 * __popcll(um));
+                        bmaps += (WCount)(6 * __popcll(um));
+                        if constexpr (!MAP::kCounts)   // six map() folds per hit, as the in-loop probes count
+                            RMR_COUNT(P.counters, (uint64_t)(6 * __popcll(um)), (uint64_t)P.flops_static, (uint64_t)P.transc_static);
+                    }
+                    slot_get_shading(s_slot, st, E);
                 }
                 if (ev) {
                     // (a next ray that meets no escape box is shaded as its miss in the same call)
@@ -3049,6 +3206,10 @@ RMR_D void trace_main(const KParams& P) {
         }
         atomicAdd(P.counters + 11, (unsigned long long)cyc_claim);
         atomicAdd(P.counters + 12, (unsigned long long)cyc_rays);
+        if (SLOTS) {
+            atomicAdd(P.counters + 13, (unsigned long long)uhits);
+            atomicAdd(P.counters + 15, (unsigned long long)uhits_cheap);
+        }
         atomicAdd(P.counters + 7, (unsigned long long)(__builtin_amdgcn_s_memtime() - c_begin));
 #endif
     }
