@@ -259,6 +259,74 @@ int rmr_set_output_source(rmr_ctx* ctx, int source);
  * rmr_read_guide / rmr_read_accum / rmr_read_denoised the float output path for planes and HDR images. */
 int rmr_encode_pfm(const float* rgba, int w, int h, const char* path);
 
+/* ---- per-tile error estimate and adaptive sampling ----------------------------------------- */
+/* No counterpart in the reference (it spends the same samples on every pixel). Additive: with the
+ * estimate off every launch runs the kernels it ran before, and the accumulator's bits never depend on it.
+ *
+ * While the estimate is on, each launch's running-mean fold also maintains the half image B (W x H
+ * float4, library-owned, laid out like the accumulator): a sample of odd global index n goes into B with
+ * running-mean index n >> 1, so after samples 0..N-1 B is bitwise the render of seeds 1, 3, 5, ... alone
+ * and its alpha is 1 where an odd sample has landed. B is allocated when the estimate is enabled (and
+ * again by rmr_reload for a new size); rmr_reload zeroes it; the setting survives rmr_reload like the
+ * params. The estimate is valid when it was enabled while nothing had been rendered since the last
+ * rmr_reload (rmr_create counts as one); rmr_write_accum / rmr_load_accum / rmr_bind_accum, switching it
+ * off, and rmr_trace_samples make it invalid until the next rmr_reload (or until it is enabled again on
+ * an accumulator nothing has been rendered into). */
+int rmr_set_error_estimate(rmr_ctx* ctx, int on);
+/* B as RGBA32F (synchronises) and its device pointer (NULL while the estimate is off); RMR_E_STATE
+ * while the estimate is off. */
+int rmr_read_half_accum(rmr_ctx* ctx, float* rgba, size_t bytes);
+void* rmr_half_device_ptr(rmr_ctx* ctx);
+/* The tile errors, ceil(H / 8) x ceil(W / 8) floats row-major, to the host (synchronises). Tile (tx, ty)
+ * covers pixels [8 tx, 8 tx + 8) x [8 ty, 8 ty + 8); with A the accumulator, every float32 operation
+ * rounded on its own, a pixel inside the image contributes
+ *   v = ((|A.r - B.r| + |A.g - B.g|) + |A.b - B.b|) / (offset + sqrt(max((A.r + A.g) + A.b, 0))),
+ * v = 0 when any of A.rgb, B.rgb is not finite, and the tile's error is the pairwise-tree sum of its 64
+ * lanes (pixels outside the image: 0) divided by its pixel count inside the image; +inf when a pixel of
+ * the tile inside the image has A.a == 0 or B.a == 0 (fewer than two samples). RMR_E_STATE when the
+ * estimate is not valid, RMR_E_INVALID unless offset is finite and > 0 and bytes covers the map. */
+int rmr_tile_error(rmr_ctx* ctx, float offset, float* out, size_t bytes);
+/* Test hook: the same kernel on two host images (w x h RGBA32F each) uploaded for the call; out:
+ * ceil(h / 8) x ceil(w / 8) floats. Needs no scene and no valid estimate. */
+int rmr_tile_error_images(rmr_ctx* ctx, const float* a_rgba, const float* b_rgba, int w, int h, float offset,
+                          float* out);
+
+/* Adaptive sampling: render until every decision block's error is at most `threshold`, at most
+ * max_samples samples per pixel. */
+typedef struct rmr_adaptive_params {
+    float    threshold;     /* 0.1   finite, >= 0: a block is open while its error > threshold     */
+    float    offset;        /* 1e-4  finite, > 0                                                   */
+    uint32_t min_samples;   /* 16    >= 2: rendered everywhere before the first estimate           */
+    uint32_t pass_samples;  /* 16    >= 1: samples per further pass on the open blocks             */
+    uint32_t max_samples;   /* no default (0): the length of times[]; >= min_samples               */
+    int32_t  block_tiles;   /* 2     1..8: a decision block is block_tiles x block_tiles 8x8 tiles */
+} rmr_adaptive_params;
+typedef struct rmr_adaptive_result {
+    uint32_t passes;        /* render passes, the first included                                   */
+    uint32_t tiles_open;    /* 8x8 tiles whose error is still > threshold at the stop              */
+    uint64_t samples;       /* pixel samples rendered: sum of count x pixels inside the image      */
+    float    max_error;     /* the largest tile error at the stop                                  */
+} rmr_adaptive_result;
+void rmr_default_adaptive_params(rmr_adaptive_params* p);
+/* RMR_OK when every field is in its range, else RMR_E_INVALID (no context, no GPU). */
+int rmr_check_adaptive_params(const rmr_adaptive_params* p);
+/* Needs a scene and an accumulator nothing has been rendered into since rmr_reload (else RMR_E_STATE);
+ * switches the estimate on. Samples [0, min_samples) go to the whole image; then, until no block is open
+ * or max_samples is reached, the tile errors are read back, every open block whose largest tile error is
+ * not > threshold closes for good, and the next min(pass_samples, max_samples - done) samples go to the
+ * open blocks' tiles. Sample n is seeded with times[n] everywhere, so every pixel is bit for bit the
+ * render of the first n seeds, n its tile's count (rmr_read_sample_counts). Runs on the context's stream
+ * and synchronises once per pass. Continuing after the call returns is not supported. */
+int rmr_render_adaptive(rmr_ctx* ctx, const float* times, const rmr_adaptive_params* p, rmr_adaptive_result* result);
+/* Samples per 8x8 tile of the last rmr_render_adaptive since rmr_reload, ceil(H / 8) x ceil(W / 8)
+ * row-major; RMR_E_STATE without one. */
+int rmr_read_sample_counts(rmr_ctx* ctx, uint32_t* out, size_t bytes);
+/* The decision rule alone (no context, no GPU): err is ty x tx tile errors, open_io one byte per decision
+ * block, ceil(ty / block_tiles) x ceil(tx / block_tiles) row-major, non-zero = open. A block that is open
+ * stays open iff one of its tiles has an error > threshold; a closed block stays closed. Returns the
+ * number of blocks still open, or RMR_E_INVALID. */
+int rmr_adaptive_select(const float* err, int tx, int ty, int block_tiles, float threshold, uint8_t* open_io);
+
 /* ---- display ---------------------------------------------------------------------------- */
 /* Graphics::Display(centre, zoom, min, max) (Graphics.cpp:356-390 with createFQ 227-258 and
  * FullQuad.vs / FullQuad.fs), headless: draws the accumulator into a screen_w x screen_h RGBA8 image

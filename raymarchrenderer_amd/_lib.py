@@ -28,6 +28,9 @@ EXPORTS = [
     "rmr_srgb_thresholds", "rmr_candidate_grid", "rmr_set_call_batching", "rmr_set_launch_streams", "rmr_get_launch_streams",
     "rmr_default_denoise_params", "rmr_render_guides", "rmr_read_guide", "rmr_guide_device_ptr", "rmr_denoise",
     "rmr_read_denoised", "rmr_denoised_device_ptr", "rmr_set_output_source", "rmr_encode_pfm",
+    "rmr_set_error_estimate", "rmr_read_half_accum", "rmr_half_device_ptr", "rmr_tile_error", "rmr_tile_error_images",
+    "rmr_default_adaptive_params", "rmr_check_adaptive_params", "rmr_render_adaptive", "rmr_read_sample_counts",
+    "rmr_adaptive_select",
 ]
 
 
@@ -133,6 +136,16 @@ def lib(diag=None):
         "rmr_denoised_device_ptr": (vp, [vp]),
         "rmr_set_output_source": (C.c_int, [vp, C.c_int]),
         "rmr_encode_pfm": (C.c_int, [fp, C.c_int, C.c_int, C.c_char_p]),
+        "rmr_set_error_estimate": (C.c_int, [vp, C.c_int]),
+        "rmr_read_half_accum": (C.c_int, [vp, fp, C.c_size_t]),
+        "rmr_half_device_ptr": (vp, [vp]),
+        "rmr_tile_error": (C.c_int, [vp, C.c_float, fp, C.c_size_t]),
+        "rmr_tile_error_images": (C.c_int, [vp, fp, fp, C.c_int, C.c_int, C.c_float, fp]),
+        "rmr_default_adaptive_params": (None, [C.POINTER(abi.AdaptiveParams)]),
+        "rmr_check_adaptive_params": (C.c_int, [C.POINTER(abi.AdaptiveParams)]),
+        "rmr_render_adaptive": (C.c_int, [vp, fp, C.POINTER(abi.AdaptiveParams), C.POINTER(abi.AdaptiveResult)]),
+        "rmr_read_sample_counts": (C.c_int, [vp, C.POINTER(C.c_uint32), C.c_size_t]),
+        "rmr_adaptive_select": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint8)]),
         # diagnostic library only (rmr_api.cpp RMR_DIAG): ray_exit at given rays; the a-trous passes
         # that run the LDS-tiled form
         "rmr_diag_ray_exit": (C.c_int, [vp, fp, C.c_int, fp, fp, C.c_int, ip]),

@@ -122,6 +122,29 @@ def default_denoise_params(**kw):
     return p
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("offset", C.c_float), ("min_samples", C.c_uint32),
+                ("pass_samples", C.c_uint32), ("max_samples", C.c_uint32), ("block_tiles", C.c_int32)]
+
+
+class AdaptiveResult(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("tiles_open", C.c_uint32), ("samples", C.c_uint64),
+                ("max_error", C.c_float)]
+
+
+ADAPTIVE_FIELDS = ("threshold", "offset", "min_samples", "pass_samples", "max_samples", "block_tiles")
+
+
+def default_adaptive_params(**kw):
+    """rmr_default_adaptive_params' values (rmr.h), with overrides; max_samples has no default (0)."""
+    p = AdaptiveParams(0.1, 1e-4, 16, 16, 0, 2)
+    for k, v in kw.items():
+        if k not in ADAPTIVE_FIELDS:
+            raise TypeError("unknown adaptive parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 # guide planes and output sources (rmr.h)
 GUIDE_RAY = 0
 GUIDE_HIT = 1

@@ -23,6 +23,7 @@
 #include "../../include/rmr.h"
 #include "rmr_internal.h"
 #include "accel.hpp"
+#include "adaptive.hpp"
 #include "rmr_jit.hpp"
 #include "scene.hpp"
 
@@ -36,6 +37,8 @@ hipError_t launch_display(const float4* accum, int img_w, int img_h, float cx, f
 int trace_occupancy(int variant, int np, bool prog, int* blocks_per_cu);
 hipError_t launch_guides(const KParams& P, int np, float4* ray, float4* hit, float4* nrm, hipStream_t s);
 hipError_t launch_atrous(const DenoisePass& A, bool tiled, hipStream_t s);
+hipError_t launch_fold_half(const KParams& P, float4* half, hipStream_t s);
+hipError_t launch_tile_error(const float4* A, const float4* B, int W, int H, float offset, float* out, hipStream_t s);
 }  // namespace rmr
 
 using rmr::CompiledScene;
@@ -99,6 +102,13 @@ struct rmr_ctx {
     int dn_result = -1;                   // d_dn[] index of the valid denoised image, -1: none
     int output_source = RMR_OUTPUT_ACCUM; // what rmr_save_bmp / rmr_display* read
     int dn_tiled_steps = kDenoiseTiledSteps;   // bit i: pass i (step 2^i, i < 2) runs the LDS-tiled form
+    // per-tile error estimate and adaptive sampling (rmr_estimate.hip, adaptive.hpp)
+    bool est_on = false;                  // every launch's fold is k_fold_half (rmr_set_error_estimate)
+    bool est_valid = false;               // d_half holds the odd samples of everything in the accumulator
+    bool rendered = false;                // something went into the accumulator since the last rmr_reload
+    float4* d_half = nullptr;             // the half image B, W x H (allocated while est_on)
+    float* d_tile_err = nullptr;          // ceil(H / 8) x ceil(W / 8) tile errors
+    std::vector<uint32_t> sample_counts;  // per tile, of the last rmr_render_adaptive since rmr_reload
     // Launch slots (rmr_set_launch_streams): trace launches go round-robin to private streams, each with
     // its own sample planes and work queue, so a launch's drain (its last long paths on a nearly idle
     // chip) overlaps the next launch's start. Every fold stays on the context's stream, after its trace's
@@ -265,6 +275,40 @@ void free_guides(rmr_ctx* c) {
     for (float4*& b : c->d_dn) { if (b) (void)hipFree(b); b = nullptr; }
     c->guides_valid = false;
     c->dn_result = -1;
+}
+
+// Release the half image and the tile-error map (the caller has synced the context's stream).
+void free_estimate(rmr_ctx* c) {
+    if (c->d_half) (void)hipFree(c->d_half);
+    if (c->d_tile_err) (void)hipFree(c->d_tile_err);
+    c->d_half = nullptr;
+    c->d_tile_err = nullptr;
+    c->est_valid = false;
+}
+
+// Switch the estimate on: the half image and the tile-error map at the image's size if they are not
+// there; valid, with the half image zeroed on the context's stream, when nothing has been rendered
+// since the last rmr_reload.
+int enable_estimate(rmr_ctx* c) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_half) {
+        const size_t tiles = (size_t)((c->W + 7) / 8) * ((c->H + 7) / 8);
+        if (hipMalloc((void**)&c->d_half, (size_t)c->W * c->H * sizeof(float4)) != hipSuccess ||
+            hipMalloc((void**)&c->d_tile_err, tiles * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            free_estimate(c);
+            c->est_on = false;
+            return fail(c, RMR_E_NOMEM, "cannot allocate the half image (W x H x 16 bytes)");
+        }
+        c->est_valid = false;
+    }
+    c->est_on = true;
+    if (c->est_valid) return RMR_OK;
+    if (!c->rendered) {
+        HIPCHK(c, hipMemsetAsync(c->d_half, 0, (size_t)c->W * c->H * sizeof(float4), c->stream));
+        c->est_valid = true;
+    }
+    return RMR_OK;
 }
 
 // The experiments' switches of the diagnostic library that take effect at a scene load (RMR_ENV is
@@ -724,7 +768,7 @@ int submit_launch(rmr_ctx* c, const KParams& P, rmr_ctx::Slot* S, bool use_jit, 
     // (RMR_DIAG_NO_FOLD: what the fold costs the frame, a timing experiment with a wrong accumulator;
     // the next launch then zeroes the queue with a memset)
     if (!c->diag_no_fold) {
-        HIPCHK(c, rmr::launch_fold(P, c->stream));
+        HIPCHK(c, c->est_on ? rmr::launch_fold_half(P, c->d_half, c->stream) : rmr::launch_fold(P, c->stream));
         qdirty = false;
     }
     if (S) {
@@ -745,6 +789,7 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
     if ((r = launch_precheck(c))) return r;
     if (tiles.empty() || nspp == 0) return RMR_OK;
     c->dn_result = -1;   // the accumulator changes: the denoised image is of the old one
+    c->rendered = true;
     if (!c->view_set) default_view(c);
     const TileXY* d_tiles = nullptr;
     if ((r = tile_list(c, tiles, &d_tiles))) return r;
@@ -950,6 +995,8 @@ void rmr_destroy(rmr_ctx* c) {
     for (auto& e : c->tile_cache) (void)hipFree(e.dev);
     if (c->h_times) (void)hipHostFree(c->h_times);
     free_guides(c);
+    if (c->d_half) (void)hipFree(c->d_half);
+    if (c->d_tile_err) (void)hipFree(c->d_tile_err);
     if (c->d_accum && !c->accum_external) (void)hipFree(c->d_accum);
     for (auto& k : c->jit_loaded)
         if (k.module) (void)hipModuleUnload(k.module);
@@ -1085,6 +1132,11 @@ int rmr_reload(rmr_ctx* c) {
     } else {
         HIPCHK(c, hipMemsetAsync(c->d_accum, 0, (size_t)c->W * c->H * sizeof(float4), c->stream));
     }
+    c->rendered = false;
+    c->sample_counts.clear();
+    c->est_valid = false;
+    if (resize) free_estimate(c);   // (the stream is idle)
+    if (c->est_on) return enable_estimate(c);   // the setting survives: B for the new size, zeroed
     return RMR_OK;
 }
 
@@ -1100,6 +1152,7 @@ int rmr_render(rmr_ctx* c, float time, float min_x, float min_y, float max_x, fl
     // deferred (rmr_set_call_batching): the errors the launch would give now come at the call
     if (const int r = launch_precheck(c)) return r;
     c->dn_result = -1;
+    c->rendered = true;
     rmr::DeferredCall* same = nullptr;
     bool overlap = false;
     for (auto& e : c->deferred) {
@@ -1180,6 +1233,8 @@ int rmr_write_accum(rmr_ctx* c, const float* rgba, size_t bytes) {
     const size_t need = (size_t)c->W * c->H * sizeof(float4);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
     c->dn_result = -1;
+    c->rendered = true;    // (the accumulator has contents the half image knows nothing of)
+    c->est_valid = false;
     HIPCHK(c, hipMemcpyAsync(c->d_accum, rgba, need, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RMR_OK;
@@ -1203,6 +1258,7 @@ int rmr_bind_accum(rmr_ctx* c, void* ptr, size_t bytes) {
     c->d_accum = (float4*)ptr;
     c->accum_external = true;
     c->dn_result = -1;
+    c->est_valid = false;
     return RMR_OK;
 }
 
@@ -1702,6 +1758,147 @@ int rmr_set_output_source(rmr_ctx* c, int source) {
     RMR_FLUSH(c);
     if (source != RMR_OUTPUT_ACCUM && source != RMR_OUTPUT_DENOISED) return fail(c, RMR_E_INVALID, "bad output source");
     c->output_source = source;
+    return RMR_OK;
+}
+
+// ---- per-tile error estimate and adaptive sampling (rmr_estimate.hip, adaptive.cpp) ----------------
+namespace {
+bool offset_ok(float offset) { return std::isfinite(offset) && offset > 0.0f; }
+
+// The tile errors of the context's accumulator and half image, to `out` (TX x TY floats); synchronises.
+int tile_error_host(rmr_ctx* c, float offset, float* out) {
+    const size_t tiles = (size_t)((c->W + 7) / 8) * ((c->H + 7) / 8);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, rmr::launch_tile_error(c->d_accum, c->d_half, c->W, c->H, offset, c->d_tile_err, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_tile_err, tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+}  // namespace
+
+int rmr_set_error_estimate(rmr_ctx* c, int on) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!on) {   // (the buffers stay until rmr_reload resizes them or rmr_destroy: queued folds may still write them)
+        c->est_on = false;
+        c->est_valid = false;
+        return RMR_OK;
+    }
+    return enable_estimate(c);
+}
+
+int rmr_read_half_accum(rmr_ctx* c, float* rgba, size_t bytes) {
+    if (!c || !rgba) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    const size_t need = (size_t)c->W * c->H * sizeof(float4);
+    if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
+    if (!c->est_on || !c->d_half) return fail(c, RMR_E_STATE, "the error estimate is off (call rmr_set_error_estimate)");
+    HIPCHK(c, hipMemcpyAsync(rgba, c->d_half, need, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+void* rmr_half_device_ptr(rmr_ctx* c) {
+    if (!c) return nullptr;
+    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
+    return c->est_on ? (void*)c->d_half : nullptr;
+}
+
+int rmr_tile_error(rmr_ctx* c, float offset, float* out, size_t bytes) {
+    if (!c || !out) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!c->est_on || !c->est_valid)
+        return fail(c, RMR_E_STATE, "the error estimate is not valid (enable it before the first render after rmr_reload)");
+    if (!offset_ok(offset)) return fail(c, RMR_E_INVALID, "offset must be finite and > 0");
+    const size_t tiles = (size_t)((c->W + 7) / 8) * ((c->H + 7) / 8);
+    if (bytes < tiles * sizeof(float)) return fail(c, RMR_E_INVALID, "buffer too small");
+    return tile_error_host(c, offset, out);
+}
+
+int rmr_tile_error_images(rmr_ctx* c, const float* a_rgba, const float* b_rgba, int w, int h, float offset, float* out) {
+    if (!c || !a_rgba || !b_rgba || !out) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (w <= 0 || h <= 0 || w > 32768 || h > 32768) return fail(c, RMR_E_INVALID, "bad image size");
+    if (!offset_ok(offset)) return fail(c, RMR_E_INVALID, "offset must be finite and > 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)w * h * sizeof(float4);
+    const size_t tiles = (size_t)((w + 7) / 8) * ((h + 7) / 8);
+    float4 *dA = nullptr, *dB = nullptr;
+    float* dE = nullptr;
+    hipError_t e = hipMalloc((void**)&dA, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&dB, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&dE, tiles * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(dA, a_rgba, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dB, b_rgba, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = rmr::launch_tile_error(dA, dB, w, h, offset, dE, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dE, tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    if (dA) (void)hipFree(dA);
+    if (dB) (void)hipFree(dB);
+    if (dE) (void)hipFree(dE);
+    HIPCHK(c, e);
+    return RMR_OK;
+}
+
+int rmr_render_adaptive(rmr_ctx* c, const float* times, const rmr_adaptive_params* p, rmr_adaptive_result* result) {
+    if (!c || !times || !p || !result) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!rmr::adaptive_params_ok(*p))
+        return fail(c, RMR_E_INVALID, "bad adaptive params (threshold finite >= 0, offset finite > 0, min_samples >= 2, "
+                                      "pass_samples >= 1, max_samples >= min_samples, block_tiles 1..8)");
+    int r;
+    if ((r = launch_precheck(c))) return r;
+    if (c->rendered)
+        return fail(c, RMR_E_STATE, "rmr_render_adaptive needs an accumulator nothing has been rendered into since rmr_reload");
+    c->est_valid = false;   // (zeroes the half image again: e.g. enabled, then a bound accumulator)
+    if ((r = enable_estimate(c))) return r;
+    const int W = c->W, H = c->H, TX = (W + 7) / 8, TY = (H + 7) / 8, bt = p->block_tiles;
+    const size_t tiles = (size_t)TX * TY;
+    std::vector<uint8_t> open((size_t)rmr::adaptive_blocks(TX, bt) * rmr::adaptive_blocks(TY, bt), 1);
+    std::vector<float> err(tiles);
+    std::vector<uint32_t> counts(tiles, p->min_samples);
+    // 1. samples [0, min_samples) everywhere
+    if ((r = render_tiles(c, rect_tiles(0, 0, W, H), 0, 0, W, H, times, 0, p->min_samples))) return r;
+    uint32_t done = p->min_samples, passes = 1;
+    for (;;) {
+        // 2. decide  3. stop test
+        if ((r = tile_error_host(c, p->offset, err.data()))) return r;
+        const int n_open = rmr::adaptive_select(err.data(), TX, TY, bt, p->threshold, open.data());
+        if (n_open == 0 || done == p->max_samples) break;
+        // 4. the next pass on the open blocks' tiles
+        const uint32_t n = std::min(p->pass_samples, p->max_samples - done);
+        const std::vector<int32_t> xy = rmr::adaptive_tiles(open.data(), TX, TY, bt);
+        std::vector<TileXY> t(xy.size() / 2);
+        for (size_t i = 0; i < t.size(); i++) {
+            t[i] = TileXY{xy[2 * i], xy[2 * i + 1]};
+            counts[(size_t)(xy[2 * i + 1] / 8) * TX + xy[2 * i] / 8] += n;
+        }
+        if ((r = render_tiles(c, t, 0, 0, W, H, times + done, done, n))) return r;
+        done += n;
+        passes++;
+    }
+    rmr_adaptive_result res{};
+    res.passes = passes;
+    res.max_error = 0.0f;
+    for (int ty = 0; ty < TY; ty++)
+        for (int tx = 0; tx < TX; tx++) {
+            const size_t i = (size_t)ty * TX + tx;
+            res.samples += (uint64_t)counts[i] * (uint64_t)(std::min(8, W - 8 * tx) * std::min(8, H - 8 * ty));
+            if (err[i] > p->threshold) res.tiles_open++;
+            if (err[i] > res.max_error) res.max_error = err[i];
+        }
+    c->sample_counts = counts;
+    *result = res;
+    return RMR_OK;
+}
+
+int rmr_read_sample_counts(rmr_ctx* c, uint32_t* out, size_t bytes) {
+    if (!c || !out) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (c->sample_counts.empty()) return fail(c, RMR_E_STATE, "no rmr_render_adaptive since the last rmr_reload");
+    if (bytes < c->sample_counts.size() * sizeof(uint32_t)) return fail(c, RMR_E_INVALID, "buffer too small");
+    std::memcpy(out, c->sample_counts.data(), c->sample_counts.size() * sizeof(uint32_t));
     return RMR_OK;
 }
 

@@ -193,6 +193,13 @@ void Graphics::setOutputSource(int source) {
     if (!need_ctx("setOutputSource") || !no_group("setOutputSource")) return;
     check(rmr_set_output_source(g_ctx, source), "setOutputSource");
 }
+bool Graphics::RenderAdaptive(const float* times, const rmr_adaptive_params& p, rmr_adaptive_result* result) {
+    if (!need_ctx("RenderAdaptive") || !no_group("RenderAdaptive")) return false;
+    rmr_adaptive_result res{};
+    const bool ok = check(rmr_render_adaptive(g_ctx, times, &p, &res), "RenderAdaptive");
+    if (ok && result) *result = res;
+    return ok;
+}
 void Graphics::Sync() {
     if (!need_ctx("Sync")) return;
     if (g_group) check(rmr_group_sync(g_group), "Sync");

@@ -68,6 +68,10 @@ public:
     // rmr_write_accum / a bound accumulator).
     static void Denoise(int iterations = 5);
     static void setOutputSource(int source);
+    // Adaptive sampling (rmr_render_adaptive): after a Reload, render until every decision block's tile
+    // error is at most p.threshold, at most p.max_samples samples per pixel (times[n] seeds sample n).
+    // Single-context mode only, like Denoise. Returns false (status in lastStatus) on failure.
+    static bool RenderAdaptive(const float* times, const rmr_adaptive_params& p, rmr_adaptive_result* result);
     static void Sync();
     static bool saveCheckpoint(const std::string& path, unsigned samplesDone);
     static bool loadCheckpoint(const std::string& path, unsigned* samplesDone);

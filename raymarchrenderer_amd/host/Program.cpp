@@ -59,6 +59,8 @@ struct Options {
     rmr_params params;
     int denoise = -1;               // --denoise [N]: a-trous iterations, -1 = no denoise
     std::string aov;                // --aov PREFIX: guide planes as PREFIX_*.pfm
+    double adaptive = -1.0;         // --adaptive T: the tile-error threshold, < 0 = uniform sampling
+    int min_samples = 16, pass_samples = 16;   // --min-samples / --pass-samples (rmr_adaptive_params)
     bool have_camera = false;
     double cam[6] = {0, 4, -6, 0, -3, 6};
 };
@@ -172,6 +174,16 @@ struct RenderResult {
     unsigned long long samples = 0;
 };
 
+rmr_adaptive_params adaptive_params(const Options& o) {
+    rmr_adaptive_params p;
+    rmr_default_adaptive_params(&p);
+    p.threshold = (float)o.adaptive;
+    p.min_samples = (uint32_t)o.min_samples;
+    p.pass_samples = (uint32_t)o.pass_samples;
+    p.max_samples = (uint32_t)o.samples;
+    return p;
+}
+
 // One render of the current scene: fixed-spp (samples > 0) or progressive (samples == 0).
 RenderResult render(const Options& o, unsigned first_pass) {
     Graphics::Reload();
@@ -200,6 +212,19 @@ RenderResult render(const Options& o, unsigned first_pass) {
         Graphics::Sync();
         r.samples = (unsigned long long)n * (unsigned long long)W * H;
         r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return r;
+    }
+    if (o.adaptive >= 0) {   // --adaptive T: the whole image, --samples as the maximum per pixel
+        std::vector<float> times(o.samples);
+        for (int s = 0; s < o.samples; s++) times[s] = seed_time(o.frame, s);
+        rmr_adaptive_result res{};
+        if (!Graphics::RenderAdaptive(times.data(), adaptive_params(o), &res)) return r;
+        Graphics::Sync();
+        r.samples = res.samples;
+        r.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        std::printf("adaptive: passes %u, mean spp %.3f, open tiles %u, max error %.6g\n", res.passes,
+                    (double)res.samples / ((double)W * H), res.tiles_open, (double)res.max_error);
+        if (!o.checkpoint.empty()) Graphics::saveCheckpoint(o.checkpoint, (unsigned)o.samples);
         return r;
     }
     if (o.samples > 0) {
@@ -259,6 +284,31 @@ bool write_aovs(const Options& o) {
     const struct { const char* name; const std::vector<float>* img; } files[] = {
         {"_normal.pfm", &nrm}, {"_position.pfm", &hit}, {"_ray.pfm", &ray}, {"_depth_id.pfm", &di}};
     for (const auto& f : files) {
+        const std::string path = o.aov + f.name;
+        if (rmr_encode_pfm(f.img->data(), W, H, path.c_str()) != RMR_OK) {
+            std::cerr << "--aov: cannot write " << path << std::endl;
+            return false;
+        }
+        if (!o.quiet) std::cout << "Saved plane as: " << path << std::endl;
+    }
+    if (o.adaptive < 0) return true;
+    // --adaptive: PREFIX_spp.pfm (R = the pixel's tile's sample count) and PREFIX_error.pfm (R = its tile error)
+    const int TX = (W + 7) / 8, TY = (H + 7) / 8;
+    std::vector<uint32_t> counts((size_t)TX * TY);
+    std::vector<float> err((size_t)TX * TY);
+    if (rmr_read_sample_counts(c, counts.data(), counts.size() * sizeof(uint32_t)) != RMR_OK)
+        return fail("rmr_read_sample_counts");
+    if (rmr_tile_error(c, adaptive_params(o).offset, err.data(), err.size() * sizeof(float)) != RMR_OK)
+        return fail("rmr_tile_error");
+    std::vector<float> spp(n, 0.0f), ep(n, 0.0f);
+    for (int y = 0; y < H; y++)
+        for (int x = 0; x < W; x++) {
+            const size_t t = (size_t)(y / 8) * TX + x / 8, i = 4 * ((size_t)y * W + x);
+            spp[i] = (float)counts[t];
+            ep[i] = err[t];
+        }
+    const struct { const char* name; const std::vector<float>* img; } more[] = {{"_spp.pfm", &spp}, {"_error.pfm", &ep}};
+    for (const auto& f : more) {
         const std::string path = o.aov + f.name;
         if (rmr_encode_pfm(f.img->data(), W, H, path.c_str()) != RMR_OK) {
             std::cerr << "--aov: cannot write " << path << std::endl;
@@ -365,6 +415,11 @@ void usage() {
         "                      and write --out from the denoised image\n"
         "  --aov PREFIX        first-hit planes as float PFM: PREFIX_normal.pfm, PREFIX_position.pfm,\n"
         "                      PREFIX_ray.pfm, PREFIX_depth_id.pfm (R = t, G = material id or -1, B = 0)\n"
+        "  --adaptive T        adaptive sampling: render until every block's tile error is <= T, at most\n"
+        "                      --samples per pixel, over the whole image; prints passes, mean spp, open tiles\n"
+        "                      and max error; with --aov also PREFIX_spp.pfm (R = samples) and PREFIX_error.pfm\n"
+        "  --min-samples N     adaptive: samples everywhere before the first estimate (default 16, >= 2)\n"
+        "  --pass-samples N    adaptive: samples per further pass on the open blocks (default 16)\n"
         "  --checkpoint FILE   write the float accumulator at the end; --resume FILE continue from one\n"
         "  --device N  --interactive (CLI.cpp commands on stdin)  --scene-dir DIR  --quiet\n"
         "  --gpus N | --devices a,b,..  the frame tile-partitioned over those GPUs (one process, RCCL reduce)");
@@ -415,6 +470,13 @@ bool parse(int argc, char** argv, Options& o) {
             o.aov = next("--aov");
             if (o.aov.empty()) return false;
         }
+        else if (a == "--adaptive") {
+            char* end = nullptr;
+            const char* v = next("--adaptive");
+            o.adaptive = std::strtod(v, &end);
+            if (end == v || *end != '\0' || !std::isfinite(o.adaptive) || o.adaptive < 0) return false;
+        } else if (a == "--min-samples") o.min_samples = std::atoi(next("--min-samples"));
+        else if (a == "--pass-samples") o.pass_samples = std::atoi(next("--pass-samples"));
         else if (a == "--checkpoint") o.checkpoint = next("--checkpoint");
         else if (a == "--resume") o.resume = next("--resume");
         else if (a == "--device") o.device = std::atoi(next("--device"));
@@ -451,6 +513,10 @@ bool parse(int argc, char** argv, Options& o) {
     if (o.variant < 0) o.variant = (o.scene.empty() && !o.interactive) ? RMR_VARIANT_RM3 : RMR_VARIANT_RM1;
     if (o.width <= 0 || o.height <= 0 || o.grid_w <= 0 || o.grid_h <= 0 || o.samples < 0 || o.passes < 0)
         return false;
+    if (o.adaptive >= 0 && (o.min_samples < 2 || o.pass_samples < 1 || o.samples < o.min_samples)) {
+        std::fprintf(stderr, "--adaptive: --min-samples >= 2, --pass-samples >= 1 and --samples >= --min-samples\n");
+        return false;
+    }
     return true;
 }
 
@@ -473,6 +539,10 @@ int main(int argc, char** argv) {
         cam.getRays(r[0], r[1], r[2], r[3]);
         for (auto& v : r) std::printf("%.9g %.9g %.9g\n", v.x, v.y, v.z);
         return 0;
+    }
+    if (o.adaptive >= 0 && (!o.devices.empty() || !o.resume.empty() || o.per_sample || o.interactive)) {
+        std::fprintf(stderr, "--adaptive: not with --gpus / --devices, --resume, --per-sample or --interactive\n");
+        return 2;
     }
     Screen::setScreenSize(Vector2(1280, 720));  // Program.cpp:89
     Graphics::setDevice(o.device);

@@ -383,6 +383,70 @@ class Renderer:
             source = names[source]
         self._chk(self._L.rmr_set_output_source(self._ctx, int(source)))
 
+    # -- per-tile error estimate and adaptive sampling --
+    def set_error_estimate(self, on=True):
+        """rmr_set_error_estimate: while on, every fold also keeps the half image (the mean of the
+        odd-indexed samples). Valid when enabled before the first render after a reload."""
+        self._chk(self._L.rmr_set_error_estimate(self._ctx, 1 if on else 0))
+
+    def read_half(self):
+        """The half image as an (H, W, 4) float32 array (rmr_read_half_accum)."""
+        w, h = self.image_size()
+        out = np.zeros((h, w, 4), np.float32)
+        self._chk(self._L.rmr_read_half_accum(self._ctx, _fp(out), out.nbytes))
+        return out
+
+    def half_device_ptr(self):
+        return self._L.rmr_half_device_ptr(self._ctx)
+
+    def tile_error(self, offset=1e-4):
+        """rmr_tile_error: the (ceil(H / 8), ceil(W / 8)) float32 map of tile errors of the accumulator
+        against the half image; +inf where a tile has a pixel with fewer than two samples."""
+        w, h = self.image_size()
+        out = np.zeros(((h + 7) // 8, (w + 7) // 8), np.float32)
+        self._chk(self._L.rmr_tile_error(self._ctx, float(offset), _fp(out), out.nbytes))
+        return out
+
+    def tile_error_images(self, A, B, offset=1e-4):
+        """rmr_tile_error_images (test hook): the tile-error kernel on two host (h, w, 4) images."""
+        A = np.ascontiguousarray(A, np.float32)
+        B = np.ascontiguousarray(B, np.float32)
+        if A.ndim != 3 or A.shape[2] != 4 or A.shape != B.shape:
+            raise ValueError("tile_error_images: A and B must be (h, w, 4) images of one shape, got %s and %s"
+                             % (A.shape, B.shape))
+        h, w = A.shape[:2]
+        out = np.zeros(((h + 7) // 8, (w + 7) // 8), np.float32)
+        self._chk(self._L.rmr_tile_error_images(self._ctx, _fp(A), _fp(B), w, h, float(offset), _fp(out)))
+        return out
+
+    def render_adaptive(self, times, params=None, **kw):
+        """rmr_render_adaptive: samples 0 .. min_samples-1 everywhere, then pass_samples at a time on the
+        decision blocks whose tile error is still > threshold, at most len(times) (or max_samples) per
+        pixel. Keywords: threshold (0.1), offset (1e-4), min_samples (16), pass_samples (16),
+        max_samples (len(times)), block_tiles (2). Returns the abi.AdaptiveResult."""
+        times = np.ascontiguousarray(times, np.float32)
+        if params is not None and not isinstance(params, abi.AdaptiveParams):
+            raise TypeError("render_adaptive: params must be an abi.AdaptiveParams")
+        p = abi.default_adaptive_params() if params is None else abi.AdaptiveParams.from_buffer_copy(params)
+        for k, v in kw.items():
+            if k not in abi.ADAPTIVE_FIELDS:
+                raise TypeError("render_adaptive: unknown parameter %r" % k)
+            setattr(p, k, v)
+        if p.max_samples == 0:
+            p.max_samples = len(times)
+        if p.max_samples > len(times):
+            raise ValueError("render_adaptive: max_samples %d exceeds the %d seeds given" % (p.max_samples, len(times)))
+        res = abi.AdaptiveResult()
+        self._chk(self._L.rmr_render_adaptive(self._ctx, _fp(times), C.byref(p), C.byref(res)))
+        return res
+
+    def sample_counts(self):
+        """Samples per 8x8 tile of the last render_adaptive: (ceil(H / 8), ceil(W / 8)) uint32."""
+        w, h = self.image_size()
+        out = np.zeros(((h + 7) // 8, (w + 7) // 8), np.uint32)
+        self._chk(self._L.rmr_read_sample_counts(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.nbytes))
+        return out
+
     def stats(self):
         s = abi.Stats()
         self._chk(self._L.rmr_get_stats(self._ctx, C.byref(s)))
@@ -438,6 +502,23 @@ def encode_pfm(rgba, path):
     rc = lib().rmr_encode_pfm(_fp(a), w, h, path.encode())
     if rc != abi.RMR_OK:
         raise RMRError(rc, "rmr_encode_pfm(%s)" % path)
+
+
+def adaptive_select(err, block_tiles, threshold, open_blocks=None):
+    """rmr_adaptive_select (no GPU): the adaptive loop's decision rule on a (TY, TX) tile-error map.
+    open_blocks: (ceil(TY / bt), ceil(TX / bt)) bools, all open without one. Returns the blocks still
+    open: an open block stays open iff one of its tiles has an error > threshold."""
+    err = np.ascontiguousarray(err, np.float32)
+    if err.ndim != 2:
+        raise ValueError("adaptive_select: err must be a (TY, TX) map, got shape %s" % (err.shape,))
+    ty, tx = err.shape
+    bt = int(block_tiles)
+    shape = (-(-ty // max(bt, 1)), -(-tx // max(bt, 1)))
+    o = np.ones(shape, np.uint8) if open_blocks is None else np.ascontiguousarray(open_blocks).astype(np.uint8).reshape(shape)
+    rc = lib().rmr_adaptive_select(_fp(err), tx, ty, bt, float(threshold), o.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc < 0:
+        raise RMRError(rc, "rmr_adaptive_select")
+    return o.astype(bool)
 
 
 # ------------------------------------------------------------------------------------------
