@@ -327,6 +327,101 @@ int rmr_read_sample_counts(rmr_ctx* ctx, uint32_t* out, size_t bytes);
  * number of blocks still open, or RMR_E_INVALID. */
 int rmr_adaptive_select(const float* err, int tx, int ty, int block_tiles, float threshold, uint8_t* open_io);
 
+/* ---- camera models and caller-supplied rays ------------------------------------------------ */
+/* No counterpart in the reference, whose only camera is main()'s jittered interpolation of the four
+ * corner rays from one point, the eye (RM1:569-584). Additive: with RMR_CAMERA_VIEW (the default) every
+ * launch runs the kernels it ran before.
+ *
+ * A ray is trace()'s arguments and the state of the invocation's rand() chain when trace() starts:
+ * origin o, unit direction d, the invocation (gx, gy) and seed `time` (rand()'s gl_GlobalInvocationID +
+ * time terms), and rc, the chain value (randChange) at that point, 0 for a fresh chain. */
+typedef struct rmr_ray {
+    float   o[3], time;
+    float   d[3], rc;
+    int32_t gx, gy;
+} rmr_ray;
+
+/* With a model other than RMR_CAMERA_VIEW set, each launch of rmr_render / rmr_render_spp /
+ * rmr_render_tiles / rmr_trace_samples / rmr_render_adaptive first writes one ray per pixel sample into a
+ * device ray buffer (3 x 16 bytes per sample, counted against the per-launch plane budget of
+ * rmr_set_tuning together with the sample's 16 bytes), then runs the ray-source form of the scene's trace
+ * kernel on it, then the unchanged running-mean fold. Such launches take no launch streams
+ * (rmr_set_launch_streams), are not call-batched (rmr_set_call_batching: rmr_render launches at once)
+ * and run without lane slots, the once-per-wave eye step and batch probes; a pixel's samples do not
+ * depend on how a frame is cut into launches.
+ *
+ * Every model starts a pixel sample's chain as main() does: rc = 0, seeds gxt = px + time, gyt =
+ * py + time, rand(co) = the reference's rand() (RM1:49-56). All arithmetic is float32, each operation
+ * rounded on its own except where fma() is written; sqrt is correctly rounded, sin / cos are the
+ * kernels' own (oracle/detmath.h det_sin / det_cos). W, H: the image size. U, V, FWD: rmr_camera_frame
+ * of the view. The first three calls are main()'s jitters:
+ *   j1 = rand(gxt, gyt), j2 = rand(gxt, gyt), j3 = rand(gyt, gxt)
+ *   dir0 = normalize(mix(mix(r00, r01, px / W + j1 / W), mix(r10, r11, px / W + j2 / W), py / H + j3 / H))
+ *   u = px / W + j1 / W,  v = py / H + j3 / H
+ * The ray's rc is the chain value after the model's last call.
+ *
+ * RMR_CAMERA_VIEW       o = eye, d = dir0 (computed inside the trace kernel: today's path).
+ * RMR_CAMERA_THIN_LENS  aperture >= 0 (the lens radius), focus > 0, both finite.
+ *     aperture == 0: o = eye, d = dir0, no further rand(): the same image as RMR_CAMERA_VIEW, bit for bit.
+ *     aperture > 0:  r1 = rand(gxt, gyt), r2 = rand(gyt, gxt)
+ *                    rad = sqrt(r1), phi = 6.28318548202514648438f * r2
+ *                    lx = rad * cos(phi), ly = rad * sin(phi)
+ *                    F = fma(dir0, focus, eye)          (the sphere of radius focus about the eye is sharp)
+ *                    o = fma(V, aperture * ly, fma(U, aperture * lx, eye))
+ *                    d = normalize(F - o)
+ * RMR_CAMERA_EQUIRECT   a full panorama about the eye: image column = longitude about V (0 at FWD, towards
+ *     U), row = polar angle from -V (row 0 is the top; V points down the image).
+ *                    lon = 6.28318548202514648438f * (u - 0.5f), pol = 3.14159274101257324219f * v
+ *                    a = sin(pol) * sin(lon), b = sin(pol) * cos(lon), m = -cos(pol)
+ *                    o = eye, d = normalize(fma(U, a, fma(FWD, b, V * m)))
+ * RMR_CAMERA_ORTHO      width, height > 0, finite: the extent of the image plane along U and V.
+ *                    o = fma(V, (v - 0.5f) * height, fma(U, (u - 0.5f) * width, eye)), d = FWD
+ * (fma(A, s, B) on vectors is componentwise; normalize(a) = a * (1 / sqrt(dot(a, a))) as in the kernels.) */
+#define RMR_CAMERA_VIEW 0
+#define RMR_CAMERA_THIN_LENS 1
+#define RMR_CAMERA_EQUIRECT 2
+#define RMR_CAMERA_ORTHO 3
+typedef struct rmr_camera_model {
+    int32_t model;      /* RMR_CAMERA_VIEW                                                       */
+    float   aperture;   /* 0   RMR_CAMERA_THIN_LENS: lens radius, finite, >= 0                   */
+    float   focus;      /* 1   RMR_CAMERA_THIN_LENS: focus distance from the eye, finite, > 0    */
+    float   width;      /* 1   RMR_CAMERA_ORTHO: finite, > 0                                     */
+    float   height;     /* 1   RMR_CAMERA_ORTHO: finite, > 0                                     */
+} rmr_camera_model;
+void rmr_default_camera_model(rmr_camera_model* m);
+/* RMR_OK when the model is known and its own fields are in range (the other models' fields are not
+ * looked at), else RMR_E_INVALID (no context, no GPU). */
+int rmr_check_camera_model(const rmr_camera_model* m);
+/* The setting survives rmr_reload, like the params. Setting a model flushes held rmr_render calls. */
+int rmr_set_camera_model(rmr_ctx* ctx, const rmr_camera_model* m);
+int rmr_get_camera_model(const rmr_ctx* ctx, rmr_camera_model* m);
+/* The camera frame of a view (eye, ray00, ray01, ray10, ray11 in shader order, as rmr_set_view takes
+ * them): out = U.xyz, V.xyz, FWD.xyz, orthonormal, computed in double and rounded to float. U along
+ * ray01 - ray00 (the image's x); V along ray10 - ray00 made orthogonal to U (down the image); FWD along
+ * ((ray00 + ray01) + ray10) + ray11 made orthogonal to both. RMR_E_INVALID for a view that is not finite
+ * or whose U, V or FWD vanishes (below 1e-9 of the vector it is taken from). No context, no GPU. */
+int rmr_camera_frame(const float view[15], float out[9]);
+/* RMR_OK iff every float of every ray is finite, |d.d - 1| <= 1e-5 (in double) and 0 <= gx, gy < 2^24
+ * (so that gx + time is one rounding); no context, no GPU. The work-skipping bounds of the kernels
+ * (rmr_set_culling) assume unit directions to float precision, as normalize() gives for every bounce
+ * ray: pass directions normalised in float or double, not merely within this check's 1e-5. */
+int rmr_check_rays(const rmr_ray* rays, size_t n);
+/* The radiance along each ray: out_rgba[i] = (trace(o, d).rgb, 1) of ray i, RGBA32F, with the loaded
+ * scene, the params and the env map, bit for bit the reference's trace() for that invocation and chain
+ * state. Any n >= 0 (the list's last 64-unit tile is padded with "no ray" records); the per-launch
+ * plane budget cuts the list into launches (64 bytes per ray). Runs on the context's stream and
+ * synchronises; the accumulator, the half image, the error estimate and the guides are left as they are.
+ * RMR_E_INVALID for a list rmr_check_rays rejects; RMR_E_STATE without a scene and with
+ * params.separate_channels set (a caller's ray has no channel passes: use three calls). */
+int rmr_trace_rays(rmr_ctx* ctx, const rmr_ray* rays, size_t n, float* out_rgba);
+/* The current model's rays (RMR_CAMERA_VIEW: the view's own) of samples seeded times[0 .. nspp) over the
+ * integer rect [x0,x1) x [y0,y1) (clamped to the image; out is sized for the clamped rect), as
+ * out[k][y - y0][x - x0], generated by the same kernel the render launches use. Synchronises. */
+int rmr_camera_rays(rmr_ctx* ctx, const float* times, uint32_t nspp, int x0, int y0, int x1, int y1, rmr_ray* out);
+/* rmr_render_guides / rmr_denoise under a model: unchanged for RMR_CAMERA_VIEW and RMR_CAMERA_THIN_LENS
+ * (the guide ray is the lens centre's, i.e. the view's); RMR_E_STATE for RMR_CAMERA_EQUIRECT and
+ * RMR_CAMERA_ORTHO. */
+
 /* ---- display ---------------------------------------------------------------------------- */
 /* Graphics::Display(centre, zoom, min, max) (Graphics.cpp:356-390 with createFQ 227-258 and
  * FullQuad.vs / FullQuad.fs), headless: draws the accumulator into a screen_w x screen_h RGBA8 image
@@ -386,6 +481,9 @@ int rmr_set_instrument(rmr_ctx* ctx, int flags);
 /* Compile the specialised kernel of a scene without a GPU (json NULL = the variant's built-in
  * scene). On success `log` receives the code-object key, otherwise the compiler log. */
 int rmr_jit_compile_scene(int variant, const char* json, size_t len, char* log, size_t loglen);
+/* The same for the scene's ray-source kernel (rmr_jit_trace_rays: the specialised kernel of launches
+ * under a camera model and of rmr_trace_rays). */
+int rmr_jit_compile_scene_rays(int variant, const char* json, size_t len, char* log, size_t loglen);
 /* Tuning knobs (<= 0 / < 0 keeps the current value): deferred-shading batch size in lanes (1..64),
  * persistent workgroups per CU (0 = occupancy), per-launch sample-plane budget in bytes. Until a
  * batch size is set (here, or by env RMR_SHADE_T in librmr_diag.so) it is chosen per kernel: 8 for general maps

@@ -6,9 +6,9 @@ reference's Graphics / Camera / Screen host interfaces.
 """
 from . import abi
 from ._lib import RMRError, lib
-from .renderer import (Camera, Graphics, Renderer, Screen, adaptive_select, camera_view, default_camera_view,
-                       encode_bmp, encode_pfm, parity_schedule, save_name, tile_spiral, time_schedule)
+from .renderer import (Camera, Graphics, Renderer, Screen, adaptive_select, camera_frame, camera_view,
+                       check_camera_model, check_rays, default_camera_view, encode_bmp, encode_pfm, parity_schedule, save_name, tile_spiral, time_schedule)
 
 __all__ = ["abi", "lib", "RMRError", "Renderer", "Graphics", "Camera", "Screen", "camera_view",
            "default_camera_view", "encode_bmp", "encode_pfm", "tile_spiral", "time_schedule", "parity_schedule",
-           "save_name", "adaptive_select"]
+           "save_name", "adaptive_select", "camera_frame", "check_camera_model", "check_rays"]

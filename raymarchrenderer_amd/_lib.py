@@ -31,6 +31,8 @@ EXPORTS = [
     "rmr_set_error_estimate", "rmr_read_half_accum", "rmr_half_device_ptr", "rmr_tile_error", "rmr_tile_error_images",
     "rmr_default_adaptive_params", "rmr_check_adaptive_params", "rmr_render_adaptive", "rmr_read_sample_counts",
     "rmr_adaptive_select",
+    "rmr_default_camera_model", "rmr_check_camera_model", "rmr_set_camera_model", "rmr_get_camera_model",
+    "rmr_camera_frame", "rmr_check_rays", "rmr_trace_rays", "rmr_camera_rays", "rmr_jit_compile_scene_rays",
 ]
 
 
@@ -146,6 +148,15 @@ def lib(diag=None):
         "rmr_render_adaptive": (C.c_int, [vp, fp, C.POINTER(abi.AdaptiveParams), C.POINTER(abi.AdaptiveResult)]),
         "rmr_read_sample_counts": (C.c_int, [vp, C.POINTER(C.c_uint32), C.c_size_t]),
         "rmr_adaptive_select": (C.c_int, [fp, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint8)]),
+        "rmr_default_camera_model": (None, [C.POINTER(abi.CameraModel)]),
+        "rmr_check_camera_model": (C.c_int, [C.POINTER(abi.CameraModel)]),
+        "rmr_set_camera_model": (C.c_int, [vp, C.POINTER(abi.CameraModel)]),
+        "rmr_get_camera_model": (C.c_int, [vp, C.POINTER(abi.CameraModel)]),
+        "rmr_camera_frame": (C.c_int, [fp, fp]),
+        "rmr_check_rays": (C.c_int, [C.c_void_p, C.c_size_t]),
+        "rmr_trace_rays": (C.c_int, [vp, C.c_void_p, C.c_size_t, fp]),
+        "rmr_camera_rays": (C.c_int, [vp, fp, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+        "rmr_jit_compile_scene_rays": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]),
         # diagnostic library only (rmr_api.cpp RMR_DIAG): ray_exit at given rays; the a-trous passes
         # that run the LDS-tiled form
         "rmr_diag_ray_exit": (C.c_int, [vp, fp, C.c_int, fp, fp, C.c_int, ip]),

@@ -145,6 +145,43 @@ def default_adaptive_params(**kw):
     return p
 
 
+# camera models (rmr.h rmr_camera_model) and caller-supplied rays (rmr_ray)
+CAMERA_VIEW = 0
+CAMERA_THIN_LENS = 1
+CAMERA_EQUIRECT = 2
+CAMERA_ORTHO = 3
+CAMERA_MODELS = {"view": CAMERA_VIEW, "thinlens": CAMERA_THIN_LENS, "equirect": CAMERA_EQUIRECT, "ortho": CAMERA_ORTHO}
+CAMERA_FIELDS = ("aperture", "focus", "width", "height")
+
+
+class CameraModel(C.Structure):
+    _fields_ = [("model", C.c_int32), ("aperture", C.c_float), ("focus", C.c_float), ("width", C.c_float),
+                ("height", C.c_float)]
+
+
+def default_camera_model(model=CAMERA_VIEW, **kw):
+    """rmr_default_camera_model's values (rmr.h) for `model` (abi.CAMERA_* or its name), with overrides."""
+    if isinstance(model, str):
+        if model not in CAMERA_MODELS:
+            raise ValueError("unknown camera model %r (view, thinlens, equirect, ortho)" % model)
+        model = CAMERA_MODELS[model]
+    m = CameraModel(int(model), 0.0, 1.0, 1.0, 1.0)
+    for k, v in kw.items():
+        if k not in CAMERA_FIELDS:
+            raise TypeError("unknown camera model field %r" % k)
+        setattr(m, k, v)
+    return m
+
+
+class Ray(C.Structure):
+    _fields_ = [("o", C.c_float * 3), ("time", C.c_float), ("d", C.c_float * 3), ("rc", C.c_float),
+                ("gx", C.c_int32), ("gy", C.c_int32)]
+
+
+# rmr_ray as a numpy structured dtype (Renderer.camera_rays / trace_rays), byte for byte the C struct
+RAY_DTYPE = [("o", "<f4", (3,)), ("time", "<f4"), ("d", "<f4", (3,)), ("rc", "<f4"), ("gx", "<i4"), ("gy", "<i4")]
+
+
 # guide planes and output sources (rmr.h)
 GUIDE_RAY = 0
 GUIDE_HIT = 1

@@ -333,14 +333,14 @@ std::vector<float> inflate_escape_boxes(const std::vector<float>& raw, double in
     return bx;
 }
 
-SamplePlan plan_samples(size_t plane, uint32_t nspp, size_t samp_budget, int launch_streams) {
-    size_t chunk = std::max<size_t>(1, samp_budget / (plane * sizeof(float4)));
+SamplePlan plan_samples(size_t plane, uint32_t nspp, size_t samp_budget, int launch_streams, size_t unit_bytes) {
+    size_t chunk = std::max<size_t>(1, samp_budget / (plane * unit_bytes));
     chunk = std::min<size_t>(chunk, nspp);
     // the trace kernel indexes units with 32 bits (atomic work counter included): < 2^31 per launch
     chunk = std::max<size_t>(1, std::min<size_t>(chunk, (((size_t)1 << 31) - 1) / plane));
     // slots for launches whose planes fit the budget shared between the slots (larger ones, C4's 34-GB
     // 4K 256-spp frame, run on the context's stream: one plane buffer of them is enough)
-    const bool slotted = launch_streams >= 2 && plane * chunk * sizeof(float4) <= samp_budget / (size_t)launch_streams;
+    const bool slotted = launch_streams >= 2 && plane * chunk * unit_bytes <= samp_budget / (size_t)launch_streams;
     return SamplePlan{chunk, slotted};
 }
 

@@ -96,7 +96,9 @@ std::vector<float> inflate_escape_boxes(const std::vector<float>& raw, double in
 // Samples per launch of `nspp` samples over `plane` units each, and whether the launches may go to
 // the launch slots.
 struct SamplePlan { size_t per_launch; bool slotted; };
-SamplePlan plan_samples(size_t plane, uint32_t nspp, size_t samp_budget, int launch_streams);
+// unit_bytes: what a unit of a launch holds in the budget's buffers: its sample (16), and for a
+// ray-source launch its ray record as well (rmr_camera.hpp kRayRecordBytes)
+SamplePlan plan_samples(size_t plane, uint32_t nspp, size_t samp_budget, int launch_streams, size_t unit_bytes = 16);
 
 // Workgroups of a launch of n_units, and the units a wave claims at a time (0: the kernel's chunk).
 struct GridPlan { int grid; uint32_t chunk_units; };

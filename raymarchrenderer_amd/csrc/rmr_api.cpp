@@ -24,12 +24,17 @@
 #include "rmr_internal.h"
 #include "accel.hpp"
 #include "adaptive.hpp"
+#include "rmr_camera.hpp"
 #include "rmr_jit.hpp"
 #include "scene.hpp"
 
 namespace rmr {
 hipError_t launch_trace(const KParams& P, int variant, int np, bool prog, bool persistent, int grid, hipStream_t s);
 hipError_t launch_fold(const KParams& P, hipStream_t s);
+hipError_t launch_trace_rays(const KParams& P, const float4* rays, int variant, int np, bool prog, bool persistent,
+                             int grid, hipStream_t s);
+int trace_rays_occupancy(int variant, int np, bool prog, int* blocks_per_cu);
+hipError_t launch_camera_rays(const KParams& P, const CamParams& C, float4* rays, hipStream_t s);
 hipError_t launch_ray_exit(const KParams& P, const float* rays, float* out, int n, hipStream_t s);
 hipError_t launch_display(const float4* accum, int img_w, int img_h, float cx, float cy, float zoom, float min_x,
                           float min_y, float max_x, float max_y, int scr_w, int scr_h, uint32_t* rgba8,
@@ -94,6 +99,12 @@ struct rmr_ctx {
     bool accum_external = false;
     float4* d_samp = nullptr;
     size_t samp_cap = 0;
+    // camera models and caller-supplied rays (rmr_camera.hip, rmr_trace.h RAYS): the
+    // model (survives rmr_reload), and the ray buffer of the ray-source launches, kRayRecordBytes per unit
+    // next to the sample planes (such launches run on the context's stream only, one after the other)
+    rmr_camera_model camera{RMR_CAMERA_VIEW, 0.0f, 1.0f, 1.0f, 1.0f};
+    float4* d_rays = nullptr;
+    size_t rays_cap = 0;                  // units
     // first-hit guides and the preview denoiser (rmr_render_guides / rmr_denoise): three guide planes and
     // two filter images of W x H float4, allocated at first use, freed at rmr_reload / rmr_destroy
     float4* d_guide[3] = {nullptr, nullptr, nullptr};
@@ -187,6 +198,8 @@ struct rmr_ctx {
     bool jit_ready = false;     // `jit` matches the loaded scene
     bool jit_failed = false;    // compile/load failed for the loaded scene (auto mode falls back)
     rmr::JitKernel jit;
+    bool jit_rays_ready = false;   // `jit_rays`, the scene's ray-source kernel (rmr_jit_trace_rays), matches it
+    rmr::JitKernel jit_rays;
     std::string jit_struct_src;  // structure-only source of the last specialised scene
     std::vector<rmr_prim> jit_base;   // primitive values the specialised kernel was baked with
     std::vector<char> jit_live;       // primitives that moved since: loaded, not literals
@@ -402,6 +415,7 @@ int upload_scene(rmr_ctx* c) {
     c->dn_result = -1;
     c->scene_loaded = true;
     c->jit_ready = false;
+    c->jit_rays_ready = false;
     c->jit_failed = false;
     c->stats.flops_per_map = s.flops_per_map();
     return RMR_OK;
@@ -416,11 +430,14 @@ int slots_request(const rmr_ctx* c) {
 }
 
 // Compile (or fetch from the cache) and load the specialised trace kernel of the loaded scene.
-int ensure_jit(rmr_ctx* c) {
-    const int slots = slots_request(c);
-    if (c->jit_ready && c->jit_slots == slots) return RMR_OK;
-    c->jit_ready = false;
-    c->jit_slots = slots;
+// rays: the ray-source kernel (rmr_jit_trace_rays; never with lane slots), kept beside the other.
+int ensure_jit(rmr_ctx* c, bool rays = false) {
+    const int slots = rays ? 0 : slots_request(c);
+    rmr::JitKernel& jk = rays ? c->jit_rays : c->jit;
+    bool& ready = rays ? c->jit_rays_ready : c->jit_ready;
+    if (ready && (rays || c->jit_slots == slots)) return RMR_OK;
+    ready = false;
+    if (!rays) c->jit_slots = slots;
     // animation: same structure as the last specialised scene, different numbers -> the primitives
     // that changed since the kernel's baked values become loads ("live"), the others stay literals:
     // one compile when the motion starts, then the same kernel every frame
@@ -437,7 +454,7 @@ int ensure_jit(rmr_ctx* c) {
     const rmr::CacheFacts cache = rmr::cache_kernel_facts(c->accel, c->accel.grid_on);
     rmr::JitFacts facts;
     const std::string src = rmr::jit_source(c->scene, c->accel.has_prog, true, c->cull, &c->jit_live,
-                                            c->npc_ksel ? c->npc_ksel : cache.npc_k, cache.npc_spheres, &facts, slots);
+                                            c->npc_ksel ? c->npc_ksel : cache.npc_k, cache.npc_spheres, &facts, slots, rays);
     std::vector<char> code;
     std::string key, log;
     std::vector<std::string> opts;
@@ -448,8 +465,8 @@ int ensure_jit(rmr_ctx* c) {
     }
     for (const auto& k : c->jit_loaded) {
         if (k.key == key) {
-            c->jit = k;
-            c->jit_ready = true;
+            jk = k;
+            ready = true;
             return RMR_OK;
         }
     }
@@ -461,10 +478,11 @@ int ensure_jit(rmr_ctx* c) {
         c->jit_failed = true;
         return fail(c, RMR_E_HIP, "hipModuleLoadData of the specialised kernel failed (key " + key + ")");
     }
-    if (hipModuleGetFunction(&k.fn, k.module, "rmr_jit_trace") != hipSuccess) {
+    const char* entry = rays ? "rmr_jit_trace_rays" : "rmr_jit_trace";
+    if (hipModuleGetFunction(&k.fn, k.module, entry) != hipSuccess) {
         (void)hipModuleUnload(k.module);
         c->jit_failed = true;
-        return fail(c, RMR_E_HIP, "rmr_jit_trace missing from the specialised code object (key " + key + ")");
+        return fail(c, RMR_E_HIP, std::string(entry) + " missing from the specialised code object (key " + key + ")");
     }
     k.block = 256;
     k.chunk = facts.chunk();
@@ -483,8 +501,28 @@ int ensure_jit(rmr_ctx* c) {
     k.park_t = facts.park_t();
     k.slot_t = facts.slot_t();
     c->jit_loaded.push_back(k);
-    c->jit = k;
-    c->jit_ready = true;
+    jk = k;
+    ready = true;
+    return RMR_OK;
+}
+
+// The ray buffer for `units` records. A failed allocation leaves the context without one (and as it was
+// otherwise): RMR_E_NOMEM.
+int ensure_rays(rmr_ctx* c, size_t units) {
+    if (units <= c->rays_cap) return RMR_OK;
+    if (c->d_rays) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // launches queued before may still read it
+        (void)hipFree(c->d_rays);
+        c->d_rays = nullptr;
+        c->rays_cap = 0;
+    }
+    if (hipMalloc((void**)&c->d_rays, units * rmr::kRayRecordBytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c->d_rays = nullptr;
+        return fail(c, RMR_E_NOMEM, "cannot allocate the ray buffer (" + std::to_string(units * rmr::kRayRecordBytes) +
+                                        " bytes; lower the plane budget, rmr_set_tuning)");
+    }
+    c->rays_cap = units;
     return RMR_OK;
 }
 
@@ -664,9 +702,15 @@ int collect_timing(rmr_ctx* c) {
 
 // The launch's escape bound (rmr_trace.h ray_exit, accel.hpp escape_inflation): on for scenes whose every
 // primitive takes part; the boxes go to the device again when the inflation changed.
-int escape_params(rmr_ctx* c, KParams& P) {
+// org_extent >= 0 (ray-source launches): the largest |coordinate| of any ray origin, in the eye's place.
+int escape_params(rmr_ctx* c, KParams& P, double org_extent = -1.0) {
     const rmr::SceneAccel& a = c->accel;
-    const double infl = rmr::escape_inflation(c->view, a.esc_extent, c->params.max_dist);
+    float org[3] = {c->view[0], c->view[1], c->view[2]};
+    if (org_extent >= 0.0) {
+        org[0] = std::nextafter((float)org_extent, INFINITY);
+        org[1] = org[2] = 0.0f;
+    }
+    const double infl = rmr::escape_inflation(org, a.esc_extent, c->params.max_dist);
     // (infl < 2^44: |eye|, E, maxDist < 2^60, the range ray_exit's FMA slab form is exact in)
     P.esc_on = (c->cull & RMR_CULL_ESCAPE) && a.esc_all && infl < 0x1p44 && !a.esc_raw.empty() ? 1 : 0;
     if (P.esc_on && infl != c->esc_infl_dev) {
@@ -698,10 +742,10 @@ float am_direct_bound(float max_dist, float am_r2) {
 }
 
 // The view, the render parameters, the env map and the buffers on top of the scene's parameters.
-int view_params(rmr_ctx* c, KParams& P) {
+int view_params(rmr_ctx* c, KParams& P, double org_extent = -1.0) {
     P = c->scene_kp;
     int r;
-    if ((r = escape_params(c, P))) return r;
+    if ((r = escape_params(c, P, org_extent))) return r;
     {
         // primary rays' first march step from the eye (rmr_trace.h eye_map): the march point
         // fma(dir, 0, eye) is the eye itself for every finite direction unless an eye coordinate is
@@ -738,7 +782,11 @@ int view_params(rmr_ctx* c, KParams& P) {
 
 // One trace launch and its fold, queued: the trace on the slot's stream (or the context's), the fold on the
 // context's stream after it.
-int submit_launch(rmr_ctx* c, const KParams& P, rmr_ctx::Slot* S, bool use_jit, int grid) {
+// rays: the launch's ray buffer (the ray-source kernels), null for the view's own rays. fold false
+// (rmr_trace_rays): the planes are the result, the accumulator is not touched (the next launch then
+// zeroes the queue with a memset).
+int submit_launch(rmr_ctx* c, const KParams& P, rmr_ctx::Slot* S, bool use_jit, int grid, const float4* rays = nullptr,
+                  bool fold = true) {
     const hipStream_t ts = S ? S->s : c->stream;   // the trace's stream
     bool& qdirty = S ? S->queue_dirty : c->queue_dirty;
     if (qdirty) HIPCHK(c, hipMemsetAsync(P.queue, 0, rmr::kQueueBytes, ts));
@@ -747,9 +795,12 @@ int submit_launch(rmr_ctx* c, const KParams& P, rmr_ctx::Slot* S, bool use_jit, 
     HIPCHK(c, hipEventRecord(ev.a, ts));
     hipError_t le;
     if (use_jit) {
-        void* args[] = {const_cast<KParams*>(&P)};
-        le = hipModuleLaunchKernel(c->jit.fn, (unsigned)grid, 1, 1, (unsigned)c->jit.block, 1, 1, 0, ts, args, nullptr);
+        const rmr::JitKernel& jk = rays ? c->jit_rays : c->jit;
+        void* args[] = {const_cast<KParams*>(&P), (void*)&rays};
+        le = hipModuleLaunchKernel(jk.fn, (unsigned)grid, 1, 1, (unsigned)jk.block, 1, 1, 0, ts, args, nullptr);
         if (le == hipSuccess) c->stats.jit_launches++;
+    } else if (rays) {
+        le = rmr::launch_trace_rays(P, rays, c->scene.variant, c->accel.map_np, c->accel.has_prog, c->kernel_mode == 0, grid, ts);
     } else {
         le = rmr::launch_trace(P, c->scene.variant, c->accel.map_np, c->accel.has_prog, c->kernel_mode == 0, grid, ts);
     }
@@ -767,7 +818,7 @@ int submit_launch(rmr_ctx* c, const KParams& P, rmr_ctx::Slot* S, bool use_jit, 
     if (le != hipSuccess) return fail(c, RMR_E_HIP, std::string("trace launch: ") + hipGetErrorString(le));
     // (RMR_DIAG_NO_FOLD: what the fold costs the frame, a timing experiment with a wrong accumulator;
     // the next launch then zeroes the queue with a memset)
-    if (!c->diag_no_fold) {
+    if (!c->diag_no_fold && fold) {
         HIPCHK(c, c->est_on ? rmr::launch_fold_half(P, c->d_half, c->stream) : rmr::launch_fold(P, c->stream));
         qdirty = false;
     }
@@ -782,42 +833,95 @@ int submit_launch(rmr_ctx* c, const KParams& P, rmr_ctx::Slot* S, bool use_jit, 
     return RMR_OK;
 }
 
+// A caller's ray list as the core's work (rmr_trace_rays): n rays, their radiance to out (RGBA32F).
+struct RayList { const rmr_ray* rays; size_t n; float* out; };
+
+// The device records (rmr_trace.h ray_record) of list units [u0, u0 + h.size() / 3): the caller's rays,
+// then "no ray" records up to the end of the last tile.
+void pack_rays(const RayList& rl, size_t u0, std::vector<float4>& h) {
+    const size_t units = h.size() / 3;
+    for (size_t i = 0; i < units; i++) {
+        float4* q = &h[3 * i];
+        if (u0 + i < rl.n) {
+            const rmr_ray& y = rl.rays[u0 + i];
+            q[0] = make_float4(y.o[0], y.o[1], y.o[2], y.time);
+            q[1] = make_float4(y.d[0], y.d[1], y.d[2], y.rc);
+            q[2] = make_float4((float)y.gx + y.time, (float)y.gy + y.time, 0.0f, 0.0f);   // gid + time, one rounding
+        } else {
+            q[0] = q[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            q[2] = make_float4(0.0f, 0.0f, NAN, 0.0f);
+        }
+    }
+}
+
 // Core: nspp samples over an 8x8 tile list, clipped to [x0,x1)x[y0,y1).
+// With a camera model other than the view's own, each launch is the generator (k_camera_rays), the
+// ray-source trace kernel on its records, and the unchanged fold. With a ray list (rl; tiles, the rect,
+// the seeds and the sample indices are then not used) the list's 64-ray tiles take the samples' place
+// in the plan (one "tile" of 64 units, ceil(n / 64) "samples": the same unit order), each launch is the
+// upload of its records, the ray-source kernel and the readback of its planes, and nothing is folded.
+// Ray-source launches run on the context's stream: no launch slots.
 int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, int x1, int y1,
-                 const float* times, uint32_t first_sample, uint32_t nspp) {
+                 const float* times, uint32_t first_sample, uint32_t nspp, const RayList* rl = nullptr) {
     int r;
     if ((r = launch_precheck(c))) return r;
-    if (tiles.empty() || nspp == 0) return RMR_OK;
-    c->dn_result = -1;   // the accumulator changes: the denoised image is of the old one
-    c->rendered = true;
+    if (rl) nspp = (uint32_t)((rl->n + 63) / 64);
+    if ((!rl && tiles.empty()) || nspp == 0) return RMR_OK;
+    const bool rays = rl || c->camera.model != RMR_CAMERA_VIEW;
     if (!c->view_set) default_view(c);
+    // the model's frame (not needed where every ray starts at the eye along the view's own direction)
+    rmr::CamParams cam{};
+    double org_extent = -1.0;
+    if (rays && !rl) {
+        const rmr_camera_model& m = c->camera;
+        cam.model = m.model;
+        cam.p[0] = m.aperture; cam.p[1] = m.focus; cam.p[2] = m.width; cam.p[3] = m.height;
+        float f[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (!(m.model == RMR_CAMERA_THIN_LENS && m.aperture == 0.0f) && !rmr::camera_frame(c->view, f))
+            return fail(c, RMR_E_INVALID, "the view has no camera frame (rmr_camera_frame): the camera model needs one");
+        for (int k = 0; k < 3; k++) { cam.U[k] = f[k]; cam.V[k] = f[3 + k]; cam.F[k] = f[6 + k]; }
+        org_extent = rmr::camera_origin_extent(m, c->view);
+    }
+    if (rl) {
+        org_extent = 0.0;
+        for (size_t i = 0; i < rl->n; i++)
+            for (int k = 0; k < 3; k++) org_extent = std::max(org_extent, std::fabs((double)rl->rays[i].o[k]));
+    }
     const TileXY* d_tiles = nullptr;
-    if ((r = tile_list(c, tiles, &d_tiles))) return r;
-    const size_t plane = tiles.size() * 64;
-    const rmr::SamplePlan sp = rmr::plan_samples(plane, nspp, c->samp_budget, c->launch_streams);
+    if (!rl) {
+        c->dn_result = -1;   // the accumulator changes: the denoised image is of the old one
+        c->rendered = true;
+        if ((r = tile_list(c, tiles, &d_tiles))) return r;
+    }
+    const size_t plane = rl ? 64 : tiles.size() * 64;
+    const rmr::SamplePlan sp = rmr::plan_samples(plane, nspp, c->samp_budget, rays ? 0 : c->launch_streams,
+                                                 rays ? sizeof(float4) + rmr::kRayRecordBytes : sizeof(float4));
     const size_t chunk = sp.per_launch;
     if (sp.slotted && c->slots.size() != (size_t)c->launch_streams) {
         if ((r = free_slots(c)) || (r = make_slots(c))) return r;
     }
     KParams P;
-    if ((r = view_params(c, P))) return r;
+    if ((r = view_params(c, P, org_extent))) return r;
     P.x0 = x0; P.y0 = y0; P.x1 = x1; P.y1 = y1;
     P.tiles = d_tiles;
-    P.n_tiles = (int)tiles.size();
+    P.n_tiles = rl ? 1 : (int)tiles.size();
 
     // hipRTC specialisation for large launches (always when jit_mode == 1)
     bool use_jit = false;
     if (c->kernel_mode == 0 && c->jit_mode != 0 && !(c->jit_mode == 2 && c->jit_failed)) {
         if (c->jit_mode == 1 || (uint64_t)chunk * plane >= c->jit_min_units) {
-            const int jr = ensure_jit(c);
+            const int jr = ensure_jit(c, rays);
             if (jr == RMR_OK) use_jit = true;
             else if (c->jit_mode == 1) return jr;
         }
     }
+    const rmr::JitKernel& jk = rays ? c->jit_rays : c->jit;   // (when use_jit)
     int bpc = c->grid_per_cu;
     if (bpc <= 0) {
-        if (use_jit) bpc = c->jit.blocks_per_cu;
-        else if (rmr::trace_occupancy(c->scene.variant, c->accel.map_np, c->accel.has_prog, &bpc) != 0 || bpc <= 0) bpc = 4;
+        if (use_jit) bpc = jk.blocks_per_cu;
+        else if ((rays ? rmr::trace_rays_occupancy(c->scene.variant, c->accel.map_np, c->accel.has_prog, &bpc)
+                       : rmr::trace_occupancy(c->scene.variant, c->accel.map_np, c->accel.has_prog, &bpc)) != 0 || bpc <= 0)
+            bpc = 4;
     }
     const int full_grid = c->n_cu * bpc;
     for (uint32_t k0 = 0; k0 < nspp; k0 += (uint32_t)chunk) {
@@ -834,33 +938,47 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
             P.samp = c->d_samp;
             P.queue = c->d_queue;
         }
+        if (rays && (r = ensure_rays(c, plane * n))) return r;
         const float* d_times = nullptr;
-        if (n > 1 && (r = stage_times(c, times + k0, n, &d_times, S ? S->s : c->stream))) return r;
+        if (!rl && n > 1 && (r = stage_times(c, times + k0, n, &d_times, S ? S->s : c->stream))) return r;
         c->last_samp = P.samp;
         P.nspp = n;
         P.first_sample = first_sample + k0;
         P.times = d_times;
-        P.time1 = times[k0];   // the seed when this launch has one sample (unit_pixel)
+        P.time1 = rl ? 0.0f : times[k0];   // the seed when this launch has one sample (unit_pixel)
         P.n_units = (uint64_t)n * plane;
+        std::vector<float4> h_rays;   // (a list's records; the launch is synchronised below)
+        if (rl) {
+            h_rays.resize(3 * (size_t)P.n_units);
+            pack_rays(*rl, (size_t)k0 * 64, h_rays);
+            HIPCHK(c, hipMemcpyAsync(c->d_rays, h_rays.data(), h_rays.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        } else if (rays) {
+            HIPCHK(c, rmr::launch_camera_rays(P, cam, c->d_rays, c->stream));
+        }
         // slotted launches leave workgroups free for the previous launch's fold, which waits behind
         // the next trace's persistent workgroups otherwise (and the slot's reuse behind that fold)
         const int reserve = (S && c->grid_reserve == 0) ? c->slot_reserve : c->grid_reserve;
-        const rmr::GridPlan gp = rmr::plan_grid(P.n_units, full_grid, reserve, (use_jit ? c->jit.block : 256) / 64,
-                                                use_jit ? c->jit.chunk : 128, c->small_chunk, P.max_bounces,
+        const rmr::GridPlan gp = rmr::plan_grid(P.n_units, full_grid, reserve, (use_jit ? jk.block : 256) / 64,
+                                                use_jit ? jk.chunk : 128, c->small_chunk, P.max_bounces,
                                                 c->grid_per_cu, c->kernel_mode);
         P.chunk_units = gp.chunk_units;
         // tuned shading batch size of the kernel that runs (measured: C2 +2% at 20; the Mandelbulb
         // and the cached BVH map -1..2%)
         if (c->shade_auto) {
-            P.shade_threshold = use_jit ? c->jit.shade_t : 16;
+            P.shade_threshold = use_jit ? jk.shade_t : 16;
             P.refill_threshold = refill_for(c->refill_threshold, P.shade_threshold);
         }
-        if (use_jit && c->jit.slots) {
-            const int park = c->park_threshold > 0 ? c->park_threshold : c->jit.park_t;
-            P.shade_threshold = park | ((c->slot_threshold > 0 ? c->slot_threshold : c->jit.slot_t) << 8);
+        if (use_jit && jk.slots) {
+            const int park = c->park_threshold > 0 ? c->park_threshold : jk.park_t;
+            P.shade_threshold = park | ((c->slot_threshold > 0 ? c->slot_threshold : jk.slot_t) << 8);
             P.refill_threshold = refill_for(c->refill_threshold, park);
         }
-        if ((r = submit_launch(c, P, S, use_jit, gp.grid))) return r;
+        if ((r = submit_launch(c, P, S, use_jit, gp.grid, rays ? c->d_rays : nullptr, !rl))) return r;
+        if (rl) {
+            const size_t u0 = (size_t)k0 * 64, cnt = std::min<size_t>((size_t)P.n_units, rl->n - u0);
+            HIPCHK(c, hipMemcpyAsync(rl->out + 4 * u0, P.samp, cnt * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
     }
     return RMR_OK;
 }
@@ -988,7 +1106,7 @@ void rmr_destroy(rmr_ctx* c) {
     (void)free_slots(c);
     for (auto& e : c->pending) c->pool.push_back(e);
     for (auto& e : c->pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); (void)hipEventDestroy(e.c); }
-    void* bufs[] = {c->d_prims, c->d_ops, c->d_consts, c->d_mats, c->d_spec, c->d_rm2, c->d_dprims, c->d_dmats, c->d_bvh, c->d_esc, c->d_env, c->d_samp,
+    void* bufs[] = {c->d_prims, c->d_ops, c->d_consts, c->d_mats, c->d_spec, c->d_rm2, c->d_dprims, c->d_dmats, c->d_bvh, c->d_esc, c->d_env, c->d_samp, c->d_rays,
                     c->d_times, c->d_queue, c->d_counters, c->d_srgb_thr, c->d_screen, c->d_grid, c->d_grid_list};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -1145,7 +1263,7 @@ int rmr_render(rmr_ctx* c, float time, float min_x, float min_y, float max_x, fl
     // pix >= bounds.xy && pix < bounds.zw for integer pix (RM1:572) <=> pix in [ceil(min), ceil(max))
     int x0 = (int)std::ceil(min_x), y0 = (int)std::ceil(min_y), x1 = (int)std::ceil(max_x), y1 = (int)std::ceil(max_y);
     if (!rmr::clamp_rect(c->W, c->H, x0, y0, x1, y1)) return RMR_OK;
-    if (!batching_on(c)) {
+    if (!batching_on(c) || c->camera.model != RMR_CAMERA_VIEW) {   // (ray-source launches are not call-batched)
         RMR_FLUSH(c);
         return render_tiles(c, rect_tiles(x0, y0, x1, y1), x0, y0, x1, y1, &time, current_sample, 1);
     }
@@ -1513,12 +1631,12 @@ int rmr_set_jit(rmr_ctx* c, int mode) {
 int rmr_set_culling(rmr_ctx* c, int flags) {
     if (!c || (flags & ~(RMR_CULL_ESCAPE | RMR_CULL_NPC | RMR_CULL_APPROX | RMR_CULL_EYE))) return RMR_E_INVALID;
     RMR_FLUSH(c);
-    if (flags != c->cull) c->jit_ready = false;   // the specialised kernel depends on it
+    if (flags != c->cull) c->jit_ready = c->jit_rays_ready = false;   // the specialised kernels depend on it
     c->cull = flags;
     return RMR_OK;
 }
 
-int rmr_jit_compile_scene(int variant, const char* json, size_t len, char* log, size_t loglen) {
+static int jit_compile_scene(int variant, const char* json, size_t len, char* log, size_t loglen, bool rays) {
     std::string lg;
     try {
         CompiledScene s = (json && len) ? rmr::compile_scene(std::string(json, len), variant) : rmr::builtin_scene(variant);
@@ -1532,7 +1650,7 @@ int rmr_jit_compile_scene(int variant, const char* json, size_t len, char* log, 
         std::string key;
         const bool ok = rmr::jit_compile(
             rmr::jit_source(s, a.has_prog, true, RMR_CULL_ESCAPE | RMR_CULL_NPC | RMR_CULL_APPROX | RMR_CULL_EYE, nullptr,
-                            cache.npc_k, cache.npc_spheres),
+                            cache.npc_k, cache.npc_spheres, nullptr, -1, rays),
             code, key, lg);
         if (log && loglen) std::snprintf(log, loglen, "%s", ok ? key.c_str() : lg.c_str());
         return ok ? RMR_OK : RMR_E_HIP;
@@ -1541,13 +1659,19 @@ int rmr_jit_compile_scene(int variant, const char* json, size_t len, char* log, 
         return RMR_E_SCENE;
     }
 }
+int rmr_jit_compile_scene(int variant, const char* json, size_t len, char* log, size_t loglen) {
+    return jit_compile_scene(variant, json, len, log, loglen, false);
+}
+int rmr_jit_compile_scene_rays(int variant, const char* json, size_t len, char* log, size_t loglen) {
+    return jit_compile_scene(variant, json, len, log, loglen, true);
+}
 
 int rmr_set_instrument(rmr_ctx* c, int flags) {
     if (!c || (flags & ~RMR_INSTR_COUNT_FLOPS)) return RMR_E_INVALID;
     RMR_FLUSH(c);
     if (flags != c->instrument) {
         c->instrument = flags;
-        c->jit_ready = false;   // another code object (its own cache key)
+        c->jit_ready = c->jit_rays_ready = false;   // another code object (its own cache key)
         c->jit_failed = false;
     }
     return RMR_OK;
@@ -1593,7 +1717,9 @@ int rmr_trace_samples(rmr_ctx* c, const float* times, int x0, int y0, int x1, in
     std::vector<TileXY> tiles = rect_tiles(x0, y0, x1, y1);
     const size_t saved_budget = c->samp_budget;
     const size_t plane = tiles.size() * 64;
-    c->samp_budget = std::max(saved_budget, plane * nspp * sizeof(float4));  // one chunk
+    // one chunk (under a camera model a unit also holds its ray record)
+    const size_t unit_bytes = sizeof(float4) + (c->camera.model != RMR_CAMERA_VIEW ? rmr::kRayRecordBytes : 0);
+    c->samp_budget = std::max(saved_budget, plane * nspp * unit_bytes);
     // render into a scratch accumulator region: trace writes samp planes; fold into accum is harmless
     std::vector<float> keep((size_t)c->W * c->H * 4);
     int r = rmr_read_accum(c, keep.data(), keep.size() * sizeof(float));
@@ -1615,6 +1741,96 @@ int rmr_trace_samples(rmr_ctx* c, const float* times, int x0, int y0, int x1, in
                 o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
             }
     return rmr_write_accum(c, keep.data(), keep.size() * sizeof(float));
+}
+
+// ---- camera models and caller-supplied rays (rmr_camera.hip, camera.cpp, rmr_trace.h RAYS) ---------
+int rmr_set_camera_model(rmr_ctx* c, const rmr_camera_model* m) {
+    if (!c || !m) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!rmr::camera_model_ok(*m))
+        return fail(c, RMR_E_INVALID, "bad camera model (thin lens: aperture finite >= 0, focus finite > 0; ortho: width, "
+                                      "height finite > 0)");
+    c->camera = *m;
+    return RMR_OK;
+}
+
+int rmr_get_camera_model(const rmr_ctx* c, rmr_camera_model* m) {
+    if (!c || !m) return RMR_E_INVALID;
+    *m = c->camera;
+    return RMR_OK;
+}
+
+int rmr_trace_rays(rmr_ctx* c, const rmr_ray* rays, size_t n, float* out_rgba) {
+    if (!c || (n && (!rays || !out_rgba))) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    int r;
+    if ((r = launch_precheck(c))) return r;
+    if (c->params.separate_channels != 0)
+        return fail(c, RMR_E_STATE, "rmr_trace_rays with separate_channels set: a caller's ray has no channel passes");
+    if (n >= ((size_t)1 << 37)) return fail(c, RMR_E_INVALID, "rmr_trace_rays: too many rays");
+    const long long bad = rmr::first_bad_ray(rays, n);
+    if (bad >= 0)
+        return fail(c, RMR_E_INVALID, "rmr_trace_rays: ray " + std::to_string(bad) + " fails rmr_check_rays");
+    if (n == 0) return RMR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const RayList rl{rays, n, out_rgba};
+    return render_tiles(c, std::vector<TileXY>(), 0, 0, 0, 0, nullptr, 0, 0, &rl);
+}
+
+int rmr_camera_rays(rmr_ctx* c, const float* times, uint32_t nspp, int x0, int y0, int x1, int y1, rmr_ray* out) {
+    if (!c || (nspp && (!times || !out))) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!rmr::clamp_rect(c->W, c->H, x0, y0, x1, y1) || nspp == 0) return RMR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->view_set) default_view(c);
+    const rmr_camera_model& m = c->camera;
+    rmr::CamParams cam{};
+    cam.model = m.model;
+    cam.p[0] = m.aperture; cam.p[1] = m.focus; cam.p[2] = m.width; cam.p[3] = m.height;
+    float f[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const bool eye_rays = m.model == RMR_CAMERA_VIEW || (m.model == RMR_CAMERA_THIN_LENS && m.aperture == 0.0f);
+    if (!eye_rays && !rmr::camera_frame(c->view, f))
+        return fail(c, RMR_E_INVALID, "the view has no camera frame (rmr_camera_frame): the camera model needs one");
+    for (int k = 0; k < 3; k++) { cam.U[k] = f[k]; cam.V[k] = f[3 + k]; cam.F[k] = f[6 + k]; }
+    const std::vector<TileXY> tiles = rect_tiles(x0, y0, x1, y1);
+    const TileXY* d_tiles = nullptr;
+    int r;
+    if ((r = tile_list(c, tiles, &d_tiles))) return r;
+    KParams P;
+    if ((r = view_params(c, P))) return r;
+    P.x0 = x0; P.y0 = y0; P.x1 = x1; P.y1 = y1;
+    P.tiles = d_tiles;
+    P.n_tiles = (int)tiles.size();
+    const size_t plane = tiles.size() * 64;
+    const size_t chunk = rmr::plan_samples(plane, nspp, c->samp_budget, 0, rmr::kRayRecordBytes).per_launch;
+    const int w = x1 - x0, hh = y1 - y0, tx = (w + 7) / 8;
+    std::vector<float4> h;
+    for (uint32_t k0 = 0; k0 < nspp; k0 += (uint32_t)chunk) {
+        const uint32_t n = (uint32_t)std::min<size_t>(chunk, nspp - k0);
+        if ((r = ensure_rays(c, plane * n))) return r;
+        const float* d_times = nullptr;
+        if (n > 1 && (r = stage_times(c, times + k0, n, &d_times))) return r;
+        P.nspp = n;
+        P.times = d_times;
+        P.time1 = times[k0];
+        P.n_units = (uint64_t)n * plane;
+        HIPCHK(c, rmr::launch_camera_rays(P, cam, c->d_rays, c->stream));
+        h.resize(3 * plane * n);
+        HIPCHK(c, hipMemcpyAsync(h.data(), c->d_rays, h.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (uint32_t k = 0; k < n; k++)
+            for (int y = 0; y < hh; y++)
+                for (int x = 0; x < w; x++) {
+                    const size_t tile = (size_t)(y / 8) * tx + (x / 8), lane = (size_t)(y % 8) * 8 + (x % 8);
+                    const float4* q = &h[3 * ((size_t)k * plane + tile * 64 + lane)];
+                    rmr_ray& o = out[((size_t)(k0 + k) * hh + y) * w + x];
+                    o.o[0] = q[0].x; o.o[1] = q[0].y; o.o[2] = q[0].z; o.time = q[0].w;
+                    o.d[0] = q[1].x; o.d[1] = q[1].y; o.d[2] = q[1].z; o.rc = q[1].w;
+                    o.gx = x0 + x;
+                    o.gy = y0 + y;
+                }
+    }
+    return RMR_OK;
 }
 
 // ---- first-hit guides and the preview denoiser (rmr_guides.hip, rmr_denoise.hip) ------------------
@@ -1645,6 +1861,8 @@ int ensure_guides(rmr_ctx* c) {
 int render_guides(rmr_ctx* c, int x0, int y0, int x1, int y1) {
     int r;
     if (!c->scene_loaded) return fail(c, RMR_E_STATE, "no scene loaded (call rmr_load_scene_json / rmr_load_builtin_scene)");
+    if (c->camera.model == RMR_CAMERA_EQUIRECT || c->camera.model == RMR_CAMERA_ORTHO)
+        return fail(c, RMR_E_STATE, "no first-hit guides for the equirect and ortho camera models");
     HIPCHK(c, hipSetDevice(c->device));
     if ((r = ensure_guides(c))) return r;
     if (!c->view_set) default_view(c);

@@ -81,9 +81,12 @@ struct JitFacts {
 // map's candidates take the sphere distance, the same value as the general form for a sphere).
 // facts (optional): the kernel class, for the launch settings.
 // slots: the lane-slot schedule where the class can run it: 1 on, 0 off, -1 the class's default.
+// rays: the ray-source kernel (entry point "rmr_jit_trace_rays(KParams, const float4* rays)", the source
+// defines RMR_RAY_SRC): primary rays from a ray buffer, no lane slots. With rays off the source is
+// what it was without the switch.
 std::string jit_source(const CompiledScene& s, bool prog, bool bake = true, int cull = 7,
                        const std::vector<char>* live = nullptr, int npc_k = 2, bool npc_spheres = false,
-                       JitFacts* facts = nullptr, int slots = -1);
+                       JitFacts* facts = nullptr, int slots = -1, bool rays = false);
 // Compile `src` for gfx950 (no GPU needed). Code-object cache: in-process, then the directory
 // $RMR_JIT_CACHE (default $HOME/.cache/rmr-jit). Returns false with the compiler log in `log`.
 // opts: further compiler options, part of the key (the instrumented build of rmr_set_instrument:

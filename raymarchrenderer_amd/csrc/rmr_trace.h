@@ -1392,9 +1392,12 @@ RMR_D void start_march(const KParams& P, Lane& L, int phase_on_run, float te_pre
 
 // trace() prologue: o = eye, d = dir, per-variant throughput init (RM1:485-492, RM2:422-429,
 // RM3:349-355). Returns false if the trace has zero bounces (loop body never runs).
-template <int VAR, bool HO>
-RMR_D bool trace_prologue(const KParams& P, Lane& L, V3 dir, float te_pre = __builtin_nanf("")) {
-    L.o = v3(P.eye[0], P.eye[1], P.eye[2]);
+// RAYS (the ray-source kernels, RMR_RAY_SRC below): o = org, the ray record's origin, and the escape
+// bound from there.
+template <int VAR, bool HO, bool RAYS = false>
+RMR_D bool trace_prologue(const KParams& P, Lane& L, V3 dir, float te_pre = __builtin_nanf(""), V3 org = V3{0.0f, 0.0f, 0.0f}) {
+    if constexpr (RAYS) L.o = org;
+    else L.o = v3(P.eye[0], P.eye[1], P.eye[2]);
     L.d = dir;
     L.bounces = 0;
     L.inside = false;
@@ -1404,7 +1407,8 @@ RMR_D bool trace_prologue(const KParams& P, Lane& L, V3 dir, float te_pre = __bu
     if (L.bounces < P.max_bounces) {
         L.bounces = 1;
         // a primary ray's escape bound from the eye (o.x + o.y = the host's eye_xy, the same bits)
-        start_march_te<HO>(P, L, PH_MARCH, (te_pre == te_pre) ? te_pre : ray_exit(P, L.o, dir, P.eye_xy));
+        if constexpr (RAYS) start_march_te<HO>(P, L, PH_MARCH, (te_pre == te_pre) ? te_pre : ray_exit(P, L.o, dir));
+        else start_march_te<HO>(P, L, PH_MARCH, (te_pre == te_pre) ? te_pre : ray_exit(P, L.o, dir, P.eye_xy));
         return true;
     }
     return false;
@@ -1535,29 +1539,65 @@ RMR_D void next_bounce(const KParams& P, Lane& L) {
 // main(): jittered corner ray, RM1:569-584 (identical in RM2/RM3)
 // (Re)start a trace: a fresh unit (fresh = true: pixel, seed chain, channel) or the next
 // separateChannels pass of this lane's unit (same primary ray; the rand chain continues).
-template <int VAR, bool HO>
-RMR_D void begin_trace(const KParams& P, Lane& L, uint32_t u, bool fresh) {
-    int px, py;
-    float time, rc;
-    const bool in_rect = unit_pixel(P, u, px, py, time);
+//
+// Ray source (RAYS; the ray-source kernels k_trace_rays / rmr_jit_trace_rays): unit u's primary ray is
+// the record rays[3 u .. 3 u + 2] of a device buffer parallel to the sample planes, written by
+// k_camera_rays (rmr_camera.hip) or uploaded from the caller's rmr_ray list:
+//   (o.xyz, time)  (d.xyz, rc)  (gid.x + time, gid.y + time, mark, 0)
+// o / d: trace()'s arguments; rc: the rand chain's state at the start of trace(); mark: NaN = no ray (a
+// pixel outside the clip rect, the padding of a list's last tile), anything else = a ray. The pixel,
+// the view's corner rays and the eye are not read.
+// In a hipRTC source the switch is RMR_RAY_SRC (rmr_jit.cpp: defined to 1 ahead of this header, and the
+// entry point is rmr_jit_trace_rays); ahead of time it is the template argument RAYS.
+#ifndef RMR_RAY_SRC
+#define RMR_RAY_SRC 0
+#endif
+constexpr uint32_t kRayRecord = 3;   // float4 per record
+struct RayRec { float4 o, d, s; };
+RMR_D RayRec ray_record(const float4* rays, uint32_t u) {
+    const float4* r = rays + (size_t)u * kRayRecord;
+    return RayRec{r[0], r[1], r[2]};
+}
+template <int VAR, bool HO, bool RAYS = false>
+RMR_D void begin_trace(const KParams& P, Lane& L, uint32_t u, bool fresh, const float4* rays = nullptr) {
+    int px = 0, py = 0;
+    float time, rc, gxt, gyt;
+    V3 dir, org = v3s(0.0f);
+    bool in_rect;
+    if constexpr (RAYS) {
+        const RayRec q = ray_record(rays, u);
+        in_rect = q.s.z == q.s.z;
+        dir = v3(q.d.x, q.d.y, q.d.z);
+        org = v3(q.o.x, q.o.y, q.o.z);
+        time = q.o.w;
+        rc = q.d.w;
+        gxt = q.s.x;
+        gyt = q.s.y;
+    } else {
+        in_rect = unit_pixel(P, u, px, py, time);
+    }
     if (fresh && !in_rect) {
         L.phase = PH_IDLE;
         return;
     }
-    const V3 dir = primary_dir(P, px, py, time, rc);
+    if constexpr (!RAYS) {
+        dir = primary_dir(P, px, py, time, rc);
+        gxt = (float)px + time;
+        gyt = (float)py + time;
+    }
     L.cw = 0;
     L.cw2 = 0;
     L.cs = -__builtin_inff();
     if (fresh) {
         L.unit = u;
         L.time = time;
-        L.gxt = (float)px + time;
-        L.gyt = (float)py + time;
+        L.gxt = gxt;
+        L.gyt = gyt;
         L.rc = rc;
         L.chan = (VAR != RMR_VARIANT_RM3 && P.separate_channels != 0) ? 0 : -1;
     }
     for (;;) {  // a zero-bounce trace finishes at once (and may start the next channel)
-        if (trace_prologue<VAR, HO>(P, L, dir)) return;
+        if (trace_prologue<VAR, HO, RAYS>(P, L, dir, __builtin_nanf(""), org)) return;
         if (finish_trace<VAR, HO>(P, L)) {
             L.phase = PH_DONE;
             return;
@@ -1604,9 +1644,23 @@ RMR_D ChunkRay chunk_ray(const KParams& P, uint32_t u, float t1 = 0.0f) {
     }
     return r;
 }
+// The ray-source kernels' chunk rays: the record, with the ray's escape bound from its own origin in
+// the mark's place (NaN = no ray, as outside the clip rect), and the origin as a third vector.
+template <bool RAYS> struct ChunkRayT : ChunkRay {};
+template <> struct ChunkRayT<true> : ChunkRay { float4 c; };
+RMR_D ChunkRayT<true> chunk_ray_src(const KParams& P, const float4* rays, uint32_t u) {
+    const RayRec q = ray_record(rays, u);
+    ChunkRayT<true> r;
+    float te = __builtin_nanf("");
+    if (q.s.z == q.s.z) te = ray_exit(P, v3(q.o.x, q.o.y, q.o.z), v3(q.d.x, q.d.y, q.d.z));   // never NaN
+    r.a = q.d;
+    r.b = make_float4(q.s.x, q.s.y, q.o.w, te);
+    r.c = q.o;
+    return r;
+}
 // begin_trace for a fresh unit whose primary ray is in LDS
-template <int VAR, bool HO, bool EYEC = false>
-RMR_D void begin_unit(const KParams& P, Lane& L, uint32_t u, float4 a, float4 b) {
+template <int VAR, bool HO, bool EYEC = false, bool RAYS = false>
+RMR_D void begin_unit(const KParams& P, Lane& L, uint32_t u, float4 a, float4 b, V3 org = V3{0.0f, 0.0f, 0.0f}) {
     if (!(b.w == b.w)) {   // outside the clip rect
         L.phase = PH_IDLE;
         return;
@@ -1622,7 +1676,7 @@ RMR_D void begin_unit(const KParams& P, Lane& L, uint32_t u, float4 a, float4 b)
     L.chan = (VAR != RMR_VARIANT_RM3 && P.separate_channels != 0) ? 0 : -1;
     const V3 dir = v3(a.x, a.y, a.z);
     for (;;) {  // a zero-bounce trace finishes at once (and may start the next channel)
-        if (trace_prologue<VAR, HO>(P, L, dir, b.w)) {   // the escape bound from chunk_ray
+        if (trace_prologue<VAR, HO, RAYS>(P, L, dir, b.w, org)) {   // the escape bound from chunk_ray
             if constexpr (EYEC) {   // the first step (chunk_ray): b.z = its t, 0 = none taken
                 const bool run = L.phase == PH_MARCH;
                 L.t = run ? b.z : L.t;
@@ -2516,8 +2570,11 @@ static_assert(RMR_QUEUE_PARTS >= 1 && RMR_QUEUE_PARTS <= 64 && RMR_QUEUE_PARTS *
 #define RMR_EYE_CHUNK 1   // (0: as a march_update of the fresh lanes at every refill, A/B)
 #endif
 typedef uint32_t WCount;
-template <int VAR, class MAP, bool PERSIST, bool PROG, class MATS = TableMats>
-RMR_D void trace_main(const KParams& P) {
+// RAYS (RMR_RAY_SRC, the ray-source kernels): primary rays from the record buffer `rays` (begin_trace)
+// instead of the pixel and the view; no eye step, no lane slots (hence no EYEC, no batch probes), a
+// third vector per chunk ray in LDS. Everything after a ray's start is the same code.
+template <int VAR, class MAP, bool PERSIST, bool PROG, class MATS = TableMats, bool RAYS = false>
+RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
     constexpr bool HO = hit_in_origin<VAR, PROG>();
     // certified hits (march_update: ctr = -1) get getNormal's probes in the shading batch from one
     // primitive: the approximate sphere/box maps' certificate (MAP::kCert), the one-primitive cache's
@@ -2541,7 +2598,7 @@ RMR_D void trace_main(const KParams& P) {
     // lane slots: RM1 HO kernels with the certifying inline map, persistent (launched without
     // separateChannels and without an env map only: the host picks the code object, rmr_api.cpp)
     constexpr bool SLOTS = RMR_LANE_SLOTS && PERSIST && VAR == RMR_VARIANT_RM1 && CERT && MAP::kCert && !MAP::kCache &&
-                           !MAP::kStepped;
+                           !MAP::kStepped && !RAYS;
     constexpr bool BP = SLOTS && RMR_BATCH_PROBES;   // uncertified hits' probes in the shading batch
     constexpr bool EYEC = SLOTS && RMR_EYE_CHUNK;    // the eye step with the chunk's rays
     constexpr uint32_t CHUNK = MAP::kCache ? RMR_CHUNK_CACHE : (SLOTS ? RMR_CHUNK_SLOTS : RMR_CHUNK);
@@ -2568,7 +2625,7 @@ RMR_D void trace_main(const KParams& P) {
     bool exhausted = false;
     if (!PERSIST) {
         const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-        if (u < n_units) begin_trace<VAR, HO>(P, L, u, true);
+        if (u < n_units) begin_trace<VAR, HO, RAYS>(P, L, u, true, rays);
         exhausted = true;
     }
     const int T = P.shade_threshold, TR = P.refill_threshold;
@@ -2586,7 +2643,7 @@ RMR_D void trace_main(const KParams& P) {
     // map's most frequent exact-fold fallback.
     // (HO kernels: RM1 without node-program materials and RM3; the node-program-material kernels
     // measured 0.3-1% slower with it, RM2 neutral)
-    const bool eye1 = HO && !MAP::kCache && P.eye_step != 0;
+    const bool eye1 = HO && !MAP::kCache && !RAYS && P.eye_step != 0;
     V2 meye = v2(0.0f, 0.0f);
     if (eye1) {
         meye = MAP::eval(P, v3(P.eye[0], P.eye[1], P.eye[2]));
@@ -2614,7 +2671,7 @@ RMR_D void trace_main(const KParams& P) {
 #else
 #define RMR_STAMP(v)
 #endif
-    __shared__ ChunkRay s_ray[4][CHUNK];   // per wave (256-thread blocks = 4 waves)
+    __shared__ ChunkRayT<RAYS> s_ray[4][CHUNK];   // per wave (256-thread blocks = 4 waves)
     __shared__ int s_tab[4][CERT ? 64 : 1];   // cert_normals: certified lanes by rank
     // cache kernels: the lane's shading-only state during the inner march loop (cold_put / cold_get)
     constexpr bool kStash = MAP::kCache && HO;
@@ -2738,7 +2795,10 @@ RMR_D void trace_main(const KParams& P) {
                     if (!exhausted) {  // the chunk's primary rays, all 64 lanes at once
                         chunk_base = base;
                         for (uint32_t sl = lane_now(); sl < CK; sl += 64) {
-                            if (base + sl < rend) s_ray[wv][sl] = chunk_ray<HO, SLOTS, EYEC>(P, base + sl, eye_t1);
+                            if (base + sl < rend) {
+                                if constexpr (RAYS) s_ray[wv][sl] = chunk_ray_src(P, rays, base + sl);
+                                else static_cast<ChunkRay&>(s_ray[wv][sl]) = chunk_ray<HO, SLOTS, EYEC>(P, base + sl, eye_t1);
+                            }
                         }
                         __builtin_amdgcn_wave_barrier();
 #ifdef RMR_PROFILE
@@ -2764,14 +2824,15 @@ RMR_D void trace_main(const KParams& P) {
         if (PERSIST) {
             if (__ballot(fresh)) {
                 if (fresh) {
-                    const ChunkRay cr = s_ray[wv][fu - chunk_base];
+                    const ChunkRayT<RAYS> cr = s_ray[wv][fu - chunk_base];
                     if constexpr (kSeeds) {
                         const uint32_t ln = lane_now();
                         s_rng[0][wv][ln] = cr.b.x;
                         s_rng[1][wv][ln] = cr.b.y;
                         s_rng[2][wv][ln] = cr.a.w;
                     }
-                    begin_unit<VAR, HO, EYEC>(P, L, fu, cr.a, cr.b);
+                    if constexpr (RAYS) begin_unit<VAR, HO, false, true>(P, L, fu, cr.a, cr.b, v3(cr.c.x, cr.c.y, cr.c.z));
+                    else begin_unit<VAR, HO, EYEC>(P, L, fu, cr.a, cr.b);
                     if constexpr (SLOTS) {
                         L.chan = -1;   // (launched without separateChannels: a constant)
                         s_slot[16][(wv << 6) + (int)lane_now()] = __uint_as_float(fu);
@@ -2779,10 +2840,10 @@ RMR_D void trace_main(const KParams& P) {
                 }
             }
             if (__ballot(restart)) {
-                if (restart) begin_trace<VAR, HO>(P, L, L.unit, false);
+                if (restart) begin_trace<VAR, HO, RAYS>(P, L, L.unit, false, rays);
             }
         } else if (__ballot(restart)) {
-            if (restart) begin_trace<VAR, HO>(P, L, L.unit, false);
+            if (restart) begin_trace<VAR, HO, RAYS>(P, L, L.unit, false, rays);
         }
         // primary rays' first march step (eye_map above); EYEC: taken with the chunk's rays unless the
         // launch has no uniform "march on" (eye_t1 = 0)

@@ -200,6 +200,10 @@ bool Graphics::RenderAdaptive(const float* times, const rmr_adaptive_params& p, 
     if (ok && result) *result = res;
     return ok;
 }
+void Graphics::setCameraModel(const rmr_camera_model& m) {
+    if (!need_ctx("setCameraModel") || !no_group("setCameraModel")) return;
+    check(rmr_set_camera_model(g_ctx, &m), "setCameraModel");
+}
 void Graphics::Sync() {
     if (!need_ctx("Sync")) return;
     if (g_group) check(rmr_group_sync(g_group), "Sync");

@@ -72,6 +72,8 @@ public:
     // error is at most p.threshold, at most p.max_samples samples per pixel (times[n] seeds sample n).
     // Single-context mode only, like Denoise. Returns false (status in lastStatus) on failure.
     static bool RenderAdaptive(const float* times, const rmr_adaptive_params& p, rmr_adaptive_result* result);
+    // The camera model of the renders that follow (rmr_set_camera_model; single-context mode only).
+    static void setCameraModel(const rmr_camera_model& m);
     static void Sync();
     static bool saveCheckpoint(const std::string& path, unsigned samplesDone);
     static bool loadCheckpoint(const std::string& path, unsigned* samplesDone);

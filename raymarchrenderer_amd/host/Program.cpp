@@ -63,6 +63,7 @@ struct Options {
     int min_samples = 16, pass_samples = 16;   // --min-samples / --pass-samples (rmr_adaptive_params)
     bool have_camera = false;
     double cam[6] = {0, 4, -6, 0, -3, 6};
+    rmr_camera_model model;         // --camera thinlens:A,F | equirect | ortho:W,H (default: the view's own rays)
 };
 
 // Program.cpp:113-115, 203-222: the outward spiral over the tile grid
@@ -407,6 +408,8 @@ void usage() {
         "  --grid GWxGH        tile grid (default 4x4)\n"
         "  --bounces B --max-steps N --max-dist D --step-mult S --separate-channels 0|1\n"
         "  --camera ex,ey,ez,dx,dy,dz   (default 0,4,-6,0,-3,6)\n"
+        "  --camera thinlens:APERTURE,FOCUS | equirect | ortho:WIDTH,HEIGHT   the camera model (rmr.h\n"
+        "                      rmr_camera_model; both forms of --camera may be given); not with --gpus / --devices\n"
         "  --env-map FILE WxH  raw RGBA8 envTex for skyColor (row 0 = up); enables useEnvTex\n"
         "  --frame F           seed schedule frame: time = 1000 F + 0.016 s\n"
         "  --per-sample        one Graphics::Render launch per sample per tile (reference pattern)\n"
@@ -425,8 +428,33 @@ void usage() {
         "  --gpus N | --devices a,b,..  the frame tile-partitioned over those GPUs (one process, RCCL reduce)");
 }
 
+// --camera's model form: thinlens:APERTURE,FOCUS | equirect | ortho:WIDTH,HEIGHT | view. False when the
+// argument is none of them (the numbers' ranges are checked by rmr_check_camera_model afterwards).
+bool camera_model_arg(const std::string& v, rmr_camera_model& m) {
+    char tail = 0;
+    float a = 0, b = 0;
+    if (v == "equirect" || v == "view") {
+        m.model = v == "view" ? RMR_CAMERA_VIEW : RMR_CAMERA_EQUIRECT;
+        return true;
+    }
+    if (std::sscanf(v.c_str(), "thinlens:%f,%f%c", &a, &b, &tail) == 2) {
+        m.model = RMR_CAMERA_THIN_LENS;
+        m.aperture = a;
+        m.focus = b;
+        return true;
+    }
+    if (std::sscanf(v.c_str(), "ortho:%f,%f%c", &a, &b, &tail) == 2) {
+        m.model = RMR_CAMERA_ORTHO;
+        m.width = a;
+        m.height = b;
+        return true;
+    }
+    return false;
+}
+
 bool parse(int argc, char** argv, Options& o) {
     rmr_default_params(&o.params);
+    rmr_default_camera_model(&o.model);
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&](const char* name) -> const char* {
@@ -453,8 +481,10 @@ bool parse(int argc, char** argv, Options& o) {
         else if (a == "--step-mult") o.params.step_multiply = (float)std::atof(next("--step-mult"));
         else if (a == "--separate-channels") o.params.separate_channels = std::atoi(next("--separate-channels"));
         else if (a == "--camera") {
+            const std::string v = next("--camera");
+            if (camera_model_arg(v, o.model)) continue;   // a model; else the eye and the direction
             double* c = o.cam;
-            if (std::sscanf(next("--camera"), "%lf,%lf,%lf,%lf,%lf,%lf", c, c + 1, c + 2, c + 3, c + 4, c + 5) != 6)
+            if (std::sscanf(v.c_str(), "%lf,%lf,%lf,%lf,%lf,%lf", c, c + 1, c + 2, c + 3, c + 4, c + 5) != 6)
                 return false;
             o.have_camera = true;
         } else if (a == "--frame") o.frame = std::atoi(next("--frame"));
@@ -513,6 +543,10 @@ bool parse(int argc, char** argv, Options& o) {
     if (o.variant < 0) o.variant = (o.scene.empty() && !o.interactive) ? RMR_VARIANT_RM3 : RMR_VARIANT_RM1;
     if (o.width <= 0 || o.height <= 0 || o.grid_w <= 0 || o.grid_h <= 0 || o.samples < 0 || o.passes < 0)
         return false;
+    if (rmr_check_camera_model(&o.model) != RMR_OK) {
+        std::fprintf(stderr, "--camera: thinlens needs APERTURE >= 0 and FOCUS > 0, ortho WIDTH > 0 and HEIGHT > 0\n");
+        return false;
+    }
     if (o.adaptive >= 0 && (o.min_samples < 2 || o.pass_samples < 1 || o.samples < o.min_samples)) {
         std::fprintf(stderr, "--adaptive: --min-samples >= 2, --pass-samples >= 1 and --samples >= --min-samples\n");
         return false;
@@ -544,6 +578,14 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--adaptive: not with --gpus / --devices, --resume, --per-sample or --interactive\n");
         return 2;
     }
+    if (o.model.model != RMR_CAMERA_VIEW && !o.devices.empty()) {
+        std::fprintf(stderr, "--camera MODEL: not with --gpus / --devices (the device group keeps the view's own rays)\n");
+        return 2;
+    }
+    if ((o.model.model == RMR_CAMERA_EQUIRECT || o.model.model == RMR_CAMERA_ORTHO) && (o.denoise >= 0 || !o.aov.empty())) {
+        std::fprintf(stderr, "--camera equirect / ortho: no --denoise and no --aov (no first-hit guides for these models)\n");
+        return 2;
+    }
     Screen::setScreenSize(Vector2(1280, 720));  // Program.cpp:89
     Graphics::setDevice(o.device);
     if (!o.devices.empty()) {
@@ -560,6 +602,10 @@ int main(int argc, char** argv) {
     if (!Graphics::context()) return 3;  // no device: fail loudly, there is no CPU path
     if (!o.interactive && Graphics::lastStatus() != RMR_OK) return 1;  // interactive: scene comes later
     Graphics::setParams(o.params);
+    if (o.model.model != RMR_CAMERA_VIEW) {
+        Graphics::setCameraModel(o.model);
+        if (Graphics::lastStatus() != RMR_OK) return 1;
+    }
     if (!o.env_map.empty()) {
         bool ok = false;
         const std::string tex = read_file(o.env_map, &ok);

@@ -251,6 +251,37 @@ class Renderer:
         self._chk(self._L.rmr_trace_samples(self._ctx, _fp(times), x0, y0, x1, y1, len(times), _fp(out)))
         return out
 
+    # -- camera models and caller-supplied rays --
+    def set_camera_model(self, model=abi.CAMERA_VIEW, **fields):
+        """rmr_set_camera_model: model abi.CAMERA_* or 'view' / 'thinlens' / 'equirect' / 'ortho';
+        fields aperture, focus (thin lens), width, height (ortho). Survives reload()."""
+        m = model if isinstance(model, abi.CameraModel) else abi.default_camera_model(model, **fields)
+        self._chk(self._L.rmr_set_camera_model(self._ctx, C.byref(m)))
+
+    def camera_model(self):
+        m = abi.CameraModel()
+        self._chk(self._L.rmr_get_camera_model(self._ctx, C.byref(m)))
+        return m
+
+    def camera_rays(self, times, rect=None):
+        """rmr_camera_rays: the current model's rays of samples seeded `times` over the rect, a
+        (len(times), h, w) structured array of abi.RAY_DTYPE (o, time, d, rc, gx, gy)."""
+        times = np.ascontiguousarray(times, np.float32)
+        w, h = self.image_size()
+        x0, y0, x1, y1 = (int(v) for v in (rect if rect is not None else (0, 0, w, h)))
+        x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, w), min(y1, h)
+        out = np.zeros((len(times), max(y1 - y0, 0), max(x1 - x0, 0)), np.dtype(abi.RAY_DTYPE))
+        self._chk(self._L.rmr_camera_rays(self._ctx, _fp(times), len(times), x0, y0, x1, y1, out.ctypes.data))
+        return out
+
+    def trace_rays(self, rays):
+        """rmr_trace_rays: the radiance along each ray of a structured array of abi.RAY_DTYPE (any
+        shape; taken in C order), (n, 4) float32 with alpha 1. The accumulator is not touched."""
+        r = np.ascontiguousarray(rays, np.dtype(abi.RAY_DTYPE)).reshape(-1)
+        out = np.zeros((len(r), 4), np.float32)
+        self._chk(self._L.rmr_trace_rays(self._ctx, r.ctypes.data, len(r), _fp(out)))
+        return out
+
     def sync(self):
         self._chk(self._L.rmr_sync(self._ctx))
 
@@ -481,6 +512,28 @@ def jit_compile_scene(scene, variant, diag=None):
     if rc != abi.RMR_OK:
         raise RMRError(rc, log.value.decode(errors="replace"))
     return log.value.decode()
+
+
+def camera_frame(view):
+    """rmr_camera_frame (no GPU): U, V, FWD of a 15-float view as a (3, 3) float32 array (rows)."""
+    v = np.ascontiguousarray(view, np.float32).reshape(15)
+    out = np.zeros(9, np.float32)
+    rc = lib().rmr_camera_frame(_fp(v), _fp(out))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_camera_frame: degenerate view")
+    return out.reshape(3, 3)
+
+
+def check_camera_model(model, **fields):
+    """rmr_check_camera_model (no GPU): True iff the model is known and its fields are in range."""
+    m = model if isinstance(model, abi.CameraModel) else abi.default_camera_model(model, **fields)
+    return lib().rmr_check_camera_model(C.byref(m)) == abi.RMR_OK
+
+
+def check_rays(rays):
+    """rmr_check_rays (no GPU): True iff rmr_trace_rays would accept the structured array."""
+    r = np.ascontiguousarray(rays, np.dtype(abi.RAY_DTYPE)).reshape(-1)
+    return lib().rmr_check_rays(r.ctypes.data, len(r)) == abi.RMR_OK
 
 
 def encode_bmp(rgba, path):
