@@ -422,6 +422,68 @@ int rmr_camera_rays(rmr_ctx* ctx, const float* times, uint32_t nspp, int x0, int
  * (the guide ray is the lens centre's, i.e. the view's); RMR_E_STATE for RMR_CAMERA_EQUIRECT and
  * RMR_CAMERA_ORTHO. */
 
+/* ---- first-hit and distance queries, device-resident lists -------------------------------- */
+/* No counterpart in the reference. Additive: no other entry point changes.
+ *
+ * The first hit of a ray: the guide planes' HIT and NORMAL (rmr_render_guides) for one ray. */
+typedef struct rmr_hit {
+    float pos[3], t;
+    float n[3], id;
+} rmr_hit;
+#define RMR_CAST_NORMALS 1
+/* out[i] = the first hit of ray i: the guide pass's statement with the ray's origin o where the guide
+ * pass has the eye, and its direction d. With maxDist, maxSteps, stepMultiply of the context's params:
+ *   t = 0, id = -1; then up to maxSteps times: m = map(fma(d, t, o));
+ *       if m.x < 0.001: the march ends with id = m.y
+ *       else if t >= maxDist: it ends with t = maxDist
+ *       else t = fma(m.x, stepMultiply, t)
+ *   a march that falls out of the loop is (maxDist, -1).
+ *   It is a hit iff t < maxDist (a far hit, an id found at t >= maxDist, is a miss that keeps march's t).
+ *   pos = fma(d, t, o), for hits and misses alike.
+ *   With RMR_CAST_NORMALS in flags, a hit gets n = getNormal(pos): the six probes map(pos +- 0.001 e_k)
+ *   in the reference's order (+x, -x, +y, -y, +z, -z; the other two coordinates get +0 / -0 added, as
+ *   the reference's vector sum does), n_k = plus_k - minus_k, then normalize. A miss gets n = (0, 0, 0)
+ *   and id = -1. Without the flag n = (0, 0, 0), id is still given and no probe is evaluated (the
+ *   visibility-query form).
+ * The ray's time, rc, gx and gy are not used (but rmr_check_rays looks at them). map() is the scene's
+ * table-driven map: no escape bound, no approximate map, no hipRTC kernel, so every kernel class gives
+ * the same bits (those of the guide planes for the same ray). rays, out: host memory. Flushes held
+ * rmr_render calls, runs on the context's stream and synchronises; the accumulator, the half image, the
+ * error estimate, the guides and the denoised image are left as they are. The list is uploaded as it
+ * is and checked on the GPU: RMR_E_INVALID, naming the first failing index, for a list rmr_check_rays
+ * rejects (out is then not written) and for unknown flags; RMR_E_STATE without a scene. */
+int rmr_cast_rays(rmr_ctx* ctx, const rmr_ray* rays, size_t n, int flags, rmr_hit* out);
+/* out_dist_id[2 i], [2 i + 1] = map(xyz[3 i .. 3 i + 2]) as (distance, id): the fold over the scene's
+ * primitives that starts from (maxDist, -1), as the reference's map() does. Points are not checked (a
+ * NaN gives what map() gives). Host memory; state rules as rmr_cast_rays. */
+int rmr_eval_map(rmr_ctx* ctx, const float* xyz, size_t n, float* out_dist_id);
+/* The device forms: every pointer is device memory of the context's device (d_out_dist_id and d_xyz
+ * float arrays, d_rays / d_out arrays of the structs, any 4-byte alignment). The work is queued on the
+ * context's stream and the call returns without synchronising: order the producer of the inputs and the
+ * consumer of the outputs against that stream (rmr_set_stream), as with a bound accumulator. Not
+ * capturable into a graph: buffers are allocated at first use (and when a list outgrows them).
+ * Nothing is validated on the host, so the rule moves to the GPU: a ray is rejected iff rmr_check_rays
+ * would reject it, and for rmr_trace_rays_device also iff some |o_k| > origin_extent. A rejected ray's
+ * result is (0, 0, 0, 0) for trace (alpha 0 marks it: every traced ray has alpha 1) and pos = 0, t = -1,
+ * n = 0, id = -2 for cast; every other ray's result is what the host form gives, bit for bit. Each
+ * rejected ray adds one to the context's counter (rmr_query_rejects).
+ * origin_extent: the caller's bound on |origin coordinate| over the list, where rmr_trace_rays takes
+ * the list's maximum (the inflation of the escape bound's boxes). The bound is exact work skipping, so
+ * any value at least the true maximum gives the same bits; finite and >= 0, else RMR_E_INVALID.
+ * rmr_trace_rays_device keeps rmr_trace_rays' plan (64 bytes per ray of the plane budget, launches of
+ * whole 64-ray tiles), kernels and state rules: RMR_E_STATE without a scene and with
+ * params.separate_channels, RMR_E_INVALID for n >= 2^37. */
+int rmr_trace_rays_device(rmr_ctx* ctx, const rmr_ray* d_rays, size_t n, float origin_extent, float* d_out_rgba);
+int rmr_cast_rays_device(rmr_ctx* ctx, const rmr_ray* d_rays, size_t n, int flags, rmr_hit* d_out);
+int rmr_eval_map_device(rmr_ctx* ctx, const float* d_xyz, size_t n, float* d_out_dist_id);
+/* *out = the rays the device forms rejected since the last call of it (or since rmr_create).
+ * Synchronises the context's stream. */
+int rmr_query_rejects(rmr_ctx* ctx, uint64_t* out);
+/* Caps the grid of the cast and eval kernels at `blocks` workgroups of 256 threads (0, the default: one
+ * thread per ray / point). A tuning knob like rmr_set_grid_reserve: scheduling only, results do not
+ * depend on it. RMR_E_INVALID for blocks < 0. */
+int rmr_set_query_grid(rmr_ctx* ctx, int blocks);
+
 /* ---- display ---------------------------------------------------------------------------- */
 /* Graphics::Display(centre, zoom, min, max) (Graphics.cpp:356-390 with createFQ 227-258 and
  * FullQuad.vs / FullQuad.fs), headless: draws the accumulator into a screen_w x screen_h RGBA8 image

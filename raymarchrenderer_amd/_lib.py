@@ -33,6 +33,8 @@ EXPORTS = [
     "rmr_adaptive_select",
     "rmr_default_camera_model", "rmr_check_camera_model", "rmr_set_camera_model", "rmr_get_camera_model",
     "rmr_camera_frame", "rmr_check_rays", "rmr_trace_rays", "rmr_camera_rays", "rmr_jit_compile_scene_rays",
+    "rmr_cast_rays", "rmr_eval_map", "rmr_trace_rays_device", "rmr_cast_rays_device", "rmr_eval_map_device",
+    "rmr_query_rejects", "rmr_set_query_grid",
 ]
 
 
@@ -157,6 +159,13 @@ def lib(diag=None):
         "rmr_trace_rays": (C.c_int, [vp, C.c_void_p, C.c_size_t, fp]),
         "rmr_camera_rays": (C.c_int, [vp, fp, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
         "rmr_jit_compile_scene_rays": (C.c_int, [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]),
+        "rmr_cast_rays": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+        "rmr_eval_map": (C.c_int, [vp, fp, C.c_size_t, fp]),
+        "rmr_trace_rays_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]),
+        "rmr_cast_rays_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+        "rmr_eval_map_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_void_p]),
+        "rmr_query_rejects": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+        "rmr_set_query_grid": (C.c_int, [vp, C.c_int]),
         # diagnostic library only (rmr_api.cpp RMR_DIAG): ray_exit at given rays; the a-trous passes
         # that run the LDS-tiled form
         "rmr_diag_ray_exit": (C.c_int, [vp, fp, C.c_int, fp, fp, C.c_int, ip]),

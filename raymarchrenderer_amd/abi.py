@@ -182,6 +182,14 @@ class Ray(C.Structure):
 RAY_DTYPE = [("o", "<f4", (3,)), ("time", "<f4"), ("d", "<f4", (3,)), ("rc", "<f4"), ("gx", "<i4"), ("gy", "<i4")]
 
 
+# rmr_hit (rmr_cast_rays): the guide planes' HIT and NORMAL of one ray, 32 bytes
+class Hit(C.Structure):
+    _fields_ = [("pos", C.c_float * 3), ("t", C.c_float), ("n", C.c_float * 3), ("id", C.c_float)]
+
+
+HIT_DTYPE = [("pos", "<f4", (3,)), ("t", "<f4"), ("n", "<f4", (3,)), ("id", "<f4")]
+CAST_NORMALS = 1
+
 # guide planes and output sources (rmr.h)
 GUIDE_RAY = 0
 GUIDE_HIT = 1

@@ -1,6 +1,7 @@
 // camera.cpp — the host side of the camera models and ray lists that needs no GPU: range checks, the
 // camera frame of a view, the checks of a caller's rays (rmr_camera.hpp). No HIP, no context.
 #include "rmr_camera.hpp"
+#include "rmr_ray_check.h"
 
 #include <algorithm>
 #include <cmath>
@@ -60,15 +61,8 @@ bool camera_frame(const float view[15], float out[9]) {
 }
 
 long long first_bad_ray(const rmr_ray* rays, size_t n) {
-    for (size_t i = 0; i < n; i++) {
-        const rmr_ray& r = rays[i];
-        bool ok = std::isfinite(r.time) && std::isfinite(r.rc);
-        for (int k = 0; k < 3; k++) ok = ok && std::isfinite(r.o[k]) && std::isfinite(r.d[k]);
-        const double dd = (double)r.d[0] * r.d[0] + (double)r.d[1] * r.d[1] + (double)r.d[2] * r.d[2];
-        ok = ok && std::fabs(dd - 1.0) <= 1e-5;
-        ok = ok && r.gx >= 0 && r.gy >= 0 && r.gx < (1 << 24) && r.gy < (1 << 24);
-        if (!ok) return (long long)i;
-    }
+    for (size_t i = 0; i < n; i++)
+        if (!ray_ok(rays[i])) return (long long)i;   // (rmr_ray_check.h: the rule the kernels apply too)
     return -1;
 }
 

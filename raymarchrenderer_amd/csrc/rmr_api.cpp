@@ -25,6 +25,7 @@
 #include "accel.hpp"
 #include "adaptive.hpp"
 #include "rmr_camera.hpp"
+#include "rmr_ray_check.h"
 #include "rmr_jit.hpp"
 #include "scene.hpp"
 
@@ -44,6 +45,12 @@ hipError_t launch_guides(const KParams& P, int np, float4* ray, float4* hit, flo
 hipError_t launch_atrous(const DenoisePass& A, bool tiled, hipStream_t s);
 hipError_t launch_fold_half(const KParams& P, float4* half, hipStream_t s);
 hipError_t launch_tile_error(const float4* A, const float4* B, int W, int H, float offset, float* out, hipStream_t s);
+hipError_t launch_cast_rays(const KParams& P, int np, bool normals, const rmr_ray* rays, uint64_t n, rmr_hit* out,
+                            unsigned long long* rejects, unsigned long long* first_bad, int grid_cap, hipStream_t s);
+hipError_t launch_eval_map(const KParams& P, int np, const float* xyz, uint64_t n, float* out, int grid_cap, hipStream_t s);
+hipError_t launch_pack_rays(const rmr_ray* rays, uint64_t n, uint64_t u0, uint32_t units, float extent, float4* rec,
+                            unsigned long long* rejects, unsigned long long* first_bad, hipStream_t s);
+hipError_t launch_unpack_rgba(const float4* samp, const float4* rec, float* out, uint32_t cnt, hipStream_t s);
 }  // namespace rmr
 
 using rmr::CompiledScene;
@@ -105,6 +112,13 @@ struct rmr_ctx {
     rmr_camera_model camera{RMR_CAMERA_VIEW, 0.0f, 1.0f, 1.0f, 1.0f};
     float4* d_rays = nullptr;
     size_t rays_cap = 0;                  // units
+    // first-hit and distance queries (rmr_query.hip), allocated at first use: the
+    // counters (kQuery* words), and the host forms' device copies of the caller's list and result
+    unsigned long long* d_query = nullptr;
+    void* d_qin = nullptr;
+    void* d_qout = nullptr;
+    size_t qin_cap = 0, qout_cap = 0;     // bytes
+    int query_grid = 0;                   // rmr_set_query_grid: 0 = one thread per ray / point
     // first-hit guides and the preview denoiser (rmr_render_guides / rmr_denoise): three guide planes and
     // two filter images of W x H float4, allocated at first use, freed at rmr_reload / rmr_destroy
     float4* d_guide[3] = {nullptr, nullptr, nullptr};
@@ -834,7 +848,21 @@ int submit_launch(rmr_ctx* c, const KParams& P, rmr_ctx::Slot* S, bool use_jit, 
 }
 
 // A caller's ray list as the core's work (rmr_trace_rays): n rays, their radiance to out (RGBA32F).
-struct RayList { const rmr_ray* rays; size_t n; float* out; };
+// d_rays set (rmr_trace_rays_device): the list and the result live on the device, the records are
+// packed and the planes unpacked by kernels (rmr_query.hip), `extent` bounds the origins, and nothing
+// is copied or synchronised.
+struct RayList { const rmr_ray* rays; size_t n; float* out; const rmr_ray* d_rays; float* d_out; float extent; };
+
+// words of rmr_ctx::d_query: rays the device forms rejected (rmr_query_rejects); the device forms'
+// first rejected index (not read); the same two of a host form's call
+enum { kQueryRejects = 0, kQueryFirstBad = 1, kQueryHostRejects = 2, kQueryHostFirstBad = 3, kQueryWords = 4 };
+
+int ensure_query(rmr_ctx* c) {
+    if (c->d_query) return RMR_OK;
+    HIPCHK(c, hipMalloc((void**)&c->d_query, kQueryWords * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->d_query, 0, kQueryWords * sizeof(unsigned long long), c->stream));
+    return RMR_OK;
+}
 
 // The device records (rmr_trace.h ray_record) of list units [u0, u0 + h.size() / 3): the caller's rays,
 // then "no ray" records up to the end of the last tile.
@@ -860,6 +888,8 @@ void pack_rays(const RayList& rl, size_t u0, std::vector<float4>& h) {
 // the seeds and the sample indices are then not used) the list's 64-ray tiles take the samples' place
 // in the plan (one "tile" of 64 units, ceil(n / 64) "samples": the same unit order), each launch is the
 // upload of its records, the ray-source kernel and the readback of its planes, and nothing is folded.
+// A device list (rl->d_rays) has k_pack_rays in the upload's place and k_unpack_rgba in the readback's, and
+// is not synchronised.
 // Ray-source launches run on the context's stream: no launch slots.
 int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, int x1, int y1,
                  const float* times, uint32_t first_sample, uint32_t nspp, const RayList* rl = nullptr) {
@@ -882,7 +912,10 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
         for (int k = 0; k < 3; k++) { cam.U[k] = f[k]; cam.V[k] = f[3 + k]; cam.F[k] = f[6 + k]; }
         org_extent = rmr::camera_origin_extent(m, c->view);
     }
-    if (rl) {
+    if (rl && rl->d_rays) {
+        org_extent = (double)rl->extent;
+        if ((r = ensure_query(c))) return r;
+    } else if (rl) {
         org_extent = 0.0;
         for (size_t i = 0; i < rl->n; i++)
             for (int k = 0; k < 3; k++) org_extent = std::max(org_extent, std::fabs((double)rl->rays[i].o[k]));
@@ -948,7 +981,10 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
         P.time1 = rl ? 0.0f : times[k0];   // the seed when this launch has one sample (unit_pixel)
         P.n_units = (uint64_t)n * plane;
         std::vector<float4> h_rays;   // (a list's records; the launch is synchronised below)
-        if (rl) {
+        if (rl && rl->d_rays) {
+            HIPCHK(c, rmr::launch_pack_rays(rl->d_rays, rl->n, (uint64_t)k0 * 64, (uint32_t)P.n_units, rl->extent, c->d_rays,
+                                            c->d_query + kQueryRejects, c->d_query + kQueryFirstBad, c->stream));
+        } else if (rl) {
             h_rays.resize(3 * (size_t)P.n_units);
             pack_rays(*rl, (size_t)k0 * 64, h_rays);
             HIPCHK(c, hipMemcpyAsync(c->d_rays, h_rays.data(), h_rays.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
@@ -974,7 +1010,10 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
             P.refill_threshold = refill_for(c->refill_threshold, park);
         }
         if ((r = submit_launch(c, P, S, use_jit, gp.grid, rays ? c->d_rays : nullptr, !rl))) return r;
-        if (rl) {
+        if (rl && rl->d_rays) {
+            const size_t u0 = (size_t)k0 * 64, cnt = std::min<size_t>((size_t)P.n_units, rl->n - u0);
+            HIPCHK(c, rmr::launch_unpack_rgba(P.samp, c->d_rays, rl->d_out + 4 * u0, (uint32_t)cnt, c->stream));
+        } else if (rl) {
             const size_t u0 = (size_t)k0 * 64, cnt = std::min<size_t>((size_t)P.n_units, rl->n - u0);
             HIPCHK(c, hipMemcpyAsync(rl->out + 4 * u0, P.samp, cnt * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1106,7 +1145,7 @@ void rmr_destroy(rmr_ctx* c) {
     (void)free_slots(c);
     for (auto& e : c->pending) c->pool.push_back(e);
     for (auto& e : c->pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); (void)hipEventDestroy(e.c); }
-    void* bufs[] = {c->d_prims, c->d_ops, c->d_consts, c->d_mats, c->d_spec, c->d_rm2, c->d_dprims, c->d_dmats, c->d_bvh, c->d_esc, c->d_env, c->d_samp, c->d_rays,
+    void* bufs[] = {c->d_prims, c->d_ops, c->d_consts, c->d_mats, c->d_spec, c->d_rm2, c->d_dprims, c->d_dmats, c->d_bvh, c->d_esc, c->d_env, c->d_samp, c->d_rays, c->d_query, c->d_qin, c->d_qout,
                     c->d_times, c->d_queue, c->d_counters, c->d_srgb_thr, c->d_screen, c->d_grid, c->d_grid_list};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -1773,7 +1812,7 @@ int rmr_trace_rays(rmr_ctx* c, const rmr_ray* rays, size_t n, float* out_rgba) {
         return fail(c, RMR_E_INVALID, "rmr_trace_rays: ray " + std::to_string(bad) + " fails rmr_check_rays");
     if (n == 0) return RMR_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    const RayList rl{rays, n, out_rgba};
+    const RayList rl{rays, n, out_rgba, nullptr, nullptr, 0.0f};
     return render_tiles(c, std::vector<TileXY>(), 0, 0, 0, 0, nullptr, 0, 0, &rl);
 }
 
@@ -1830,6 +1869,138 @@ int rmr_camera_rays(rmr_ctx* c, const float* times, uint32_t nspp, int x0, int y
                     o.gy = y0 + y;
                 }
     }
+    return RMR_OK;
+}
+
+// ---- first-hit and distance queries, device-resident ray lists (rmr_query.hip) -----
+namespace {
+// What the cast and eval kernels need: a scene, the counters, the launch parameters (the view is not read).
+int query_begin(rmr_ctx* c, KParams& P) {
+    if (!c->scene_loaded) return fail(c, RMR_E_STATE, "no scene loaded (call rmr_load_scene_json / rmr_load_builtin_scene)");
+    HIPCHK(c, hipSetDevice(c->device));
+    int r;
+    if ((r = ensure_query(c))) return r;
+    if (!c->view_set) default_view(c);
+    return view_params(c, P);
+}
+
+// A host form's device copy of the caller's list or result: grows only, after the stream's work on it.
+int ensure_qbuf(rmr_ctx* c, void** buf, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return RMR_OK;
+    if (*buf) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(*buf);
+        *buf = nullptr;
+        *cap = 0;
+    }
+    if (hipMalloc(buf, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *buf = nullptr;
+        return fail(c, RMR_E_NOMEM, "cannot allocate a query buffer (" + std::to_string(bytes) + " bytes)");
+    }
+    *cap = bytes;
+    return RMR_OK;
+}
+}  // namespace
+
+int rmr_cast_rays_device(rmr_ctx* c, const rmr_ray* d_rays, size_t n, int flags, rmr_hit* d_out) {
+    if (!c || (n && (!d_rays || !d_out))) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (flags & ~RMR_CAST_NORMALS) return fail(c, RMR_E_INVALID, "rmr_cast_rays: unknown flags");
+    KParams P;
+    int r;
+    if ((r = query_begin(c, P))) return r;
+    HIPCHK(c, rmr::launch_cast_rays(P, c->accel.map_np, (flags & RMR_CAST_NORMALS) != 0, d_rays, n, d_out,
+                                    c->d_query + kQueryRejects, c->d_query + kQueryFirstBad, c->query_grid, c->stream));
+    return RMR_OK;
+}
+
+int rmr_eval_map_device(rmr_ctx* c, const float* d_xyz, size_t n, float* d_out) {
+    if (!c || (n && (!d_xyz || !d_out))) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    KParams P;
+    int r;
+    if ((r = query_begin(c, P))) return r;
+    HIPCHK(c, rmr::launch_eval_map(P, c->accel.map_np, d_xyz, n, d_out, c->query_grid, c->stream));
+    return RMR_OK;
+}
+
+int rmr_cast_rays(rmr_ctx* c, const rmr_ray* rays, size_t n, int flags, rmr_hit* out) {
+    if (!c || (n && (!rays || !out))) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (flags & ~RMR_CAST_NORMALS) return fail(c, RMR_E_INVALID, "rmr_cast_rays: unknown flags");
+    KParams P;
+    int r;
+    if ((r = query_begin(c, P))) return r;
+    if (n == 0) return RMR_OK;
+    if ((r = ensure_qbuf(c, &c->d_qin, &c->qin_cap, n * sizeof(rmr_ray)))) return r;
+    if ((r = ensure_qbuf(c, &c->d_qout, &c->qout_cap, n * sizeof(rmr_hit)))) return r;
+    // the caller's list as it is; the kernel validates it and leaves the first failing index
+    HIPCHK(c, hipMemcpyAsync(c->d_qin, rays, n * sizeof(rmr_ray), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_query + kQueryHostRejects, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_query + kQueryHostFirstBad, 0xff, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, rmr::launch_cast_rays(P, c->accel.map_np, (flags & RMR_CAST_NORMALS) != 0, (const rmr_ray*)c->d_qin, n,
+                                    (rmr_hit*)c->d_qout, c->d_query + kQueryHostRejects, c->d_query + kQueryHostFirstBad,
+                                    c->query_grid, c->stream));
+    unsigned long long bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, c->d_query + kQueryHostFirstBad, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (bad != ~0ull) return fail(c, RMR_E_INVALID, "rmr_cast_rays: ray " + std::to_string(bad) + " fails rmr_check_rays");
+    HIPCHK(c, hipMemcpyAsync(out, c->d_qout, n * sizeof(rmr_hit), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+int rmr_eval_map(rmr_ctx* c, const float* xyz, size_t n, float* out) {
+    if (!c || (n && (!xyz || !out))) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    KParams P;
+    int r;
+    if ((r = query_begin(c, P))) return r;
+    if (n == 0) return RMR_OK;
+    if ((r = ensure_qbuf(c, &c->d_qin, &c->qin_cap, n * 3 * sizeof(float)))) return r;
+    if ((r = ensure_qbuf(c, &c->d_qout, &c->qout_cap, n * 2 * sizeof(float)))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_qin, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, rmr::launch_eval_map(P, c->accel.map_np, (const float*)c->d_qin, n, (float*)c->d_qout, c->query_grid, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_qout, n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+int rmr_trace_rays_device(rmr_ctx* c, const rmr_ray* d_rays, size_t n, float origin_extent, float* d_out_rgba) {
+    if (!c || (n && (!d_rays || !d_out_rgba))) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    int r;
+    if ((r = launch_precheck(c))) return r;
+    if (c->params.separate_channels != 0)
+        return fail(c, RMR_E_STATE, "rmr_trace_rays_device with separate_channels set: a caller's ray has no channel passes");
+    if (n >= ((size_t)1 << 37)) return fail(c, RMR_E_INVALID, "rmr_trace_rays_device: too many rays");
+    if (!rmr::extent_ok(origin_extent))
+        return fail(c, RMR_E_INVALID, "rmr_trace_rays_device: origin_extent must be finite and >= 0");
+    if (n == 0) return RMR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const RayList rl{nullptr, n, nullptr, d_rays, d_out_rgba, origin_extent};
+    return render_tiles(c, std::vector<TileXY>(), 0, 0, 0, 0, nullptr, 0, 0, &rl);
+}
+
+int rmr_query_rejects(rmr_ctx* c, uint64_t* out) {
+    if (!c || !out) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    *out = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!c->d_query) return RMR_OK;
+    unsigned long long v = 0;
+    HIPCHK(c, hipMemcpyAsync(&v, c->d_query + kQueryRejects, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_query + kQueryRejects, 0, sizeof(v), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *out = (uint64_t)v;
+    return RMR_OK;
+}
+
+int rmr_set_query_grid(rmr_ctx* c, int blocks) {
+    if (!c || blocks < 0) return RMR_E_INVALID;
+    c->query_grid = blocks;
     return RMR_OK;
 }
 

@@ -282,6 +282,84 @@ class Renderer:
         self._chk(self._L.rmr_trace_rays(self._ctx, r.ctypes.data, len(r), _fp(out)))
         return out
 
+    # -- first-hit and distance queries, device-resident lists (rmr.h) --
+    def cast_rays(self, rays, normals=True):
+        """rmr_cast_rays: the first hit of each ray of a structured array of abi.RAY_DTYPE (any shape;
+        taken in C order), a structured array of abi.HIT_DTYPE (pos, t, n, id); id -1 marks a miss.
+        normals=False: n stays zero and no probe is evaluated (visibility queries)."""
+        r = np.ascontiguousarray(rays, np.dtype(abi.RAY_DTYPE)).reshape(-1)
+        out = np.zeros(len(r), np.dtype(abi.HIT_DTYPE))
+        self._chk(self._L.rmr_cast_rays(self._ctx, r.ctypes.data, len(r), abi.CAST_NORMALS if normals else 0,
+                                        out.ctypes.data))
+        return out
+
+    def eval_map(self, points):
+        """rmr_eval_map: map(p) of each point of an (..., 3) array as (n, 2) float32 (distance, id)."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        out = np.zeros((len(p), 2), np.float32)
+        self._chk(self._L.rmr_eval_map(self._ctx, _fp(p), len(p), _fp(out)))
+        return out
+
+    @staticmethod
+    def _device_rays(rays):
+        """A torch CUDA tensor of rays, (n, 40) uint8 or (n, 10) float32 (views of abi.RAY_DTYPE): n."""
+        import torch
+        ok = (rays.is_cuda and rays.dim() == 2 and rays.is_contiguous() and
+              ((rays.dtype == torch.uint8 and rays.shape[1] == 40) or (rays.dtype == torch.float32 and rays.shape[1] == 10)))
+        if not ok:
+            raise ValueError("device rays: a contiguous CUDA tensor, (n, 40) uint8 or (n, 10) float32 (abi.RAY_DTYPE)")
+        return rays.shape[0]
+
+    @staticmethod
+    def _device_out(out, n, cols, like):
+        import torch
+        if out is None:
+            return torch.empty((n, cols), dtype=torch.float32, device=like.device)
+        if not (out.is_cuda and out.device == like.device and out.dtype == torch.float32 and out.is_contiguous() and
+                tuple(out.shape) == (n, cols)):
+            raise ValueError("out: a contiguous float32 CUDA tensor of shape (%d, %d) on %s" % (n, cols, like.device))
+        return out
+
+    def trace_rays_device(self, rays, origin_extent, out=None):
+        """rmr_trace_rays_device: the radiance along each ray of a torch CUDA tensor (see _device_rays), an
+        (n, 4) float32 tensor on the same device; queued on the context's stream (set_stream), no copy to
+        the host and no sync. origin_extent: a bound on |origin coordinate| over the list. A ray the
+        GPU's check rejects gives (0, 0, 0, 0) and counts in query_rejects()."""
+        n = self._device_rays(rays)
+        out = self._device_out(out, n, 4, rays)
+        self._chk(self._L.rmr_trace_rays_device(self._ctx, rays.data_ptr(), n, float(origin_extent), out.data_ptr()))
+        return out
+
+    def cast_rays_device(self, rays, normals=True, out=None):
+        """rmr_cast_rays_device: (n, 8) float32 (pos, t, n, id: abi.HIT_DTYPE) on the rays' device; a
+        rejected ray gives (0, 0, 0, -1, 0, 0, 0, -2). Queued on the context's stream, no sync."""
+        n = self._device_rays(rays)
+        out = self._device_out(out, n, 8, rays)
+        self._chk(self._L.rmr_cast_rays_device(self._ctx, rays.data_ptr(), n, abi.CAST_NORMALS if normals else 0,
+                                               out.data_ptr()))
+        return out
+
+    def eval_map_device(self, points, out=None):
+        """rmr_eval_map_device: map(p) of an (n, 3) float32 CUDA tensor as (n, 2) float32 (distance, id)."""
+        import torch
+        if not (points.is_cuda and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3 and
+                points.is_contiguous()):
+            raise ValueError("points: a contiguous (n, 3) float32 CUDA tensor")
+        n = points.shape[0]
+        out = self._device_out(out, n, 2, points)
+        self._chk(self._L.rmr_eval_map_device(self._ctx, points.data_ptr(), n, out.data_ptr()))
+        return out
+
+    def query_rejects(self):
+        """rmr_query_rejects: rays the device forms rejected since the last call (synchronises)."""
+        v = C.c_uint64(0)
+        self._chk(self._L.rmr_query_rejects(self._ctx, C.byref(v)))
+        return int(v.value)
+
+    def set_query_grid(self, blocks):
+        """rmr_set_query_grid: cap the cast / eval kernels' grid (0: automatic). Scheduling only."""
+        self._chk(self._L.rmr_set_query_grid(self._ctx, int(blocks)))
+
     def sync(self):
         self._chk(self._L.rmr_sync(self._ctx))
 
