@@ -327,6 +327,61 @@ int rmr_read_sample_counts(rmr_ctx* ctx, uint32_t* out, size_t bytes);
  * number of blocks still open, or RMR_E_INVALID. */
 int rmr_adaptive_select(const float* err, int tx, int ty, int block_tiles, float threshold, uint8_t* open_io);
 
+/* ---- variance-guided mode of the preview denoiser ------------------------------------------ */
+/* rmr_denoise's filter with one more edge-stopping weight, on luminance, scaled by a per-pixel variance
+ * estimate taken from the accumulator A and the half image B: it backs off where the render has converged
+ * and works hard where it has not. Additive: rmr_denoise and every other call compute what they did, and
+ * a context that never calls rmr_denoise_variance allocates nothing for it.
+ *
+ * lum(v) = (0.2126 v.r + 0.7152 v.g) + 0.0722 v.b, always applied to a difference of two colours taken
+ * per channel first. A pixel is v-live iff it is live in rmr_denoise's sense for A (guide id >= 0,
+ * A.w != 0, A.rgb finite) and B.w != 0 and B.rgb is finite; this is settled once, from A and B. A pixel
+ * that is not v-live (so also a live pixel with fewer than two samples) passes through every pass bit for
+ * bit, contributes to no tap and no window, and has variance -1 in both variance planes.
+ *   Seed: d(p) = lum(A(p).rgb - B(p).rgb); var_0(p) = sum_q d(q)^2 / n_p over the n_p pixels q with
+ *     |dx|, |dy| <= var_radius that are on the image, v-live and have id_q == id_p (the centre is one).
+ *     (A - B)^2 is an unbiased estimate of Var(A) for an even sample count n; for odd n it overestimates
+ *     by at most 1 + 2 / (n - 1).
+ *   Pass i = 0 .. iterations-1, step 2^i, c_0 = A: for a v-live centre p, w_q is rmr_denoise's tap weight
+ *     (rmr_denoise_params above, "live" read as "v-live") times
+ *       l_q = exp(-|lum(c_i(q).rgb - c_i(p).rgb)| / (sigma_l sqrt(max(var_i(p), 0)) + 1e-8)),
+ *     the centre tap 1 exactly, and
+ *       c_{i+1}(p).rgb = sum_q k_q w_q c_i(q).rgb / sum_q k_q w_q,     alpha unchanged,
+ *       var_{i+1}(p)   = sum_q (k_q w_q)^2 var_i(q) / (sum_q k_q w_q)^2.
+ *   iterations = 0 copies A, and the filtered variance is then the seed. */
+typedef struct rmr_variance_params {
+    float   sigma_l;     /* 4     finite, > 0: luminance distance in standard deviations           */
+    int32_t var_radius;  /* 3     0..4: the seed's window is (2 var_radius + 1)^2 pixels           */
+} rmr_variance_params;
+void rmr_default_variance_params(rmr_variance_params* p);
+/* RMR_OK when both fields are in their ranges, else RMR_E_INVALID (no context, no GPU). */
+int rmr_check_variance_params(const rmr_variance_params* p);
+/* Filter the accumulator into the context's denoised image, as rmr_denoise does and with its validity
+ * rules: rmr_read_denoised, rmr_denoised_device_ptr, RMR_OUTPUT_DENOISED, rmr_save_bmp and rmr_display*
+ * then read the guided image. NULL = the defaults, for either struct; RMR_E_INVALID outside the ranges.
+ * RMR_E_STATE when the error estimate is not valid (it is valid when rmr_set_error_estimate was on before
+ * the first render since rmr_reload, or after rmr_render_adaptive). Renders full-image guides first when
+ * they are not valid (RMR_E_STATE under the equirect and ortho camera models). Three W x H float planes
+ * (the seed and two filter planes) are allocated at the first call (RMR_E_NOMEM if that fails) and freed
+ * with the guide planes by rmr_reload / rmr_destroy. The accumulator, B, the guides, the tile errors and
+ * the sample counts are not written. Runs on the context's stream. */
+int rmr_denoise_variance(rmr_ctx* ctx, const rmr_denoise_params* p, const rmr_variance_params* v);
+/* The variance planes, W x H floats laid out like the accumulator: the seed var_0, and the filtered
+ * variance var_iterations that belongs to the denoised image. Valid exactly while a denoised image made
+ * by rmr_denoise_variance is valid (a later rmr_denoise makes them invalid), else RMR_E_STATE / NULL.
+ * rmr_read_variance synchronises. */
+#define RMR_VARIANCE_SEED 0
+#define RMR_VARIANCE_FILTERED 1
+int rmr_read_variance(rmr_ctx* ctx, int which, float* out, size_t bytes);
+void* rmr_variance_device_ptr(rmr_ctx* ctx, int which);
+/* Test hook: the same kernels on four host images (w x h RGBA32F each: A, B, RMR_GUIDE_HIT,
+ * RMR_GUIDE_NORMAL) uploaded for the call; out_rgba: w x h RGBA32F, out_seed / out_var: w x h floats
+ * (either may be NULL). Needs no scene, no valid estimate and no guides, and leaves every image of the
+ * context as it was. */
+int rmr_denoise_variance_images(rmr_ctx* ctx, const float* a_rgba, const float* b_rgba, const float* hit_rgba,
+                                const float* nrm_rgba, int w, int h, const rmr_denoise_params* p,
+                                const rmr_variance_params* v, float* out_rgba, float* out_seed, float* out_var);
+
 /* ---- camera models and caller-supplied rays ------------------------------------------------ */
 /* No counterpart in the reference, whose only camera is main()'s jittered interpolation of the four
  * corner rays from one point, the eye (RM1:569-584). Additive: with RMR_CAMERA_VIEW (the default) every

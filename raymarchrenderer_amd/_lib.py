@@ -35,6 +35,8 @@ EXPORTS = [
     "rmr_camera_frame", "rmr_check_rays", "rmr_trace_rays", "rmr_camera_rays", "rmr_jit_compile_scene_rays",
     "rmr_cast_rays", "rmr_eval_map", "rmr_trace_rays_device", "rmr_cast_rays_device", "rmr_eval_map_device",
     "rmr_query_rejects", "rmr_set_query_grid",
+    "rmr_default_variance_params", "rmr_check_variance_params", "rmr_denoise_variance", "rmr_read_variance",
+    "rmr_variance_device_ptr", "rmr_denoise_variance_images",
 ]
 
 
@@ -166,6 +168,13 @@ def lib(diag=None):
         "rmr_eval_map_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_void_p]),
         "rmr_query_rejects": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         "rmr_set_query_grid": (C.c_int, [vp, C.c_int]),
+        "rmr_default_variance_params": (None, [C.POINTER(abi.VarianceParams)]),
+        "rmr_check_variance_params": (C.c_int, [C.POINTER(abi.VarianceParams)]),
+        "rmr_denoise_variance": (C.c_int, [vp, C.POINTER(abi.DenoiseParams), C.POINTER(abi.VarianceParams)]),
+        "rmr_read_variance": (C.c_int, [vp, C.c_int, fp, C.c_size_t]),
+        "rmr_variance_device_ptr": (vp, [vp, C.c_int]),
+        "rmr_denoise_variance_images": (C.c_int, [vp, fp, fp, fp, fp, C.c_int, C.c_int, C.POINTER(abi.DenoiseParams),
+                                                  C.POINTER(abi.VarianceParams), fp, fp, fp]),
         # diagnostic library only (rmr_api.cpp RMR_DIAG): ray_exit at given rays; the a-trous passes
         # that run the LDS-tiled form
         "rmr_diag_ray_exit": (C.c_int, [vp, fp, C.c_int, fp, fp, C.c_int, ip]),

@@ -122,6 +122,26 @@ def default_denoise_params(**kw):
     return p
 
 
+DENOISE_FIELDS = ("iterations", "normal_pow2", "sigma_z", "sigma_c")
+
+
+class VarianceParams(C.Structure):
+    _fields_ = [("sigma_l", C.c_float), ("var_radius", C.c_int32)]
+
+
+VARIANCE_FIELDS = ("sigma_l", "var_radius")
+
+
+def default_variance_params(**kw):
+    """rmr_default_variance_params' values (rmr.h), with overrides."""
+    p = VarianceParams(4.0, 3)
+    for k, v in kw.items():
+        if k not in VARIANCE_FIELDS:
+            raise TypeError("unknown variance parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("threshold", C.c_float), ("offset", C.c_float), ("min_samples", C.c_uint32),
                 ("pass_samples", C.c_uint32), ("max_samples", C.c_uint32), ("block_tiles", C.c_int32)]
@@ -197,6 +217,10 @@ GUIDE_NORMAL = 2
 GUIDE_PLANES = {"ray": GUIDE_RAY, "hit": GUIDE_HIT, "normal": GUIDE_NORMAL}
 OUTPUT_ACCUM = 0
 OUTPUT_DENOISED = 1
+# variance planes of the variance-guided denoiser (rmr.h)
+VARIANCE_SEED = 0
+VARIANCE_FILTERED = 1
+VARIANCE_PLANES = {"seed": VARIANCE_SEED, "filtered": VARIANCE_FILTERED}
 # rmr_set_culling flags (rmr.h)
 CULL_ESCAPE = 1
 CULL_NPC = 2

@@ -62,6 +62,8 @@ struct EventPair { hipEvent_t a, b, c; };
 constexpr int kSlotGridReserve = 32;   // workgroups a slotted launch leaves free for the previous fold
 // a-trous passes that run the LDS-tiled form (bit i: step 2^i); DESIGN.md §4.7 has the measurements
 constexpr int kDenoiseTiledSteps = 3;
+// the same for the variance-guided passes (rmr_denoise_var.hip); DESIGN.md §4.11
+constexpr int kDenoiseVarTiledSteps = 3;
 
 struct rmr_ctx {
     int device = 0;
@@ -127,6 +129,12 @@ struct rmr_ctx {
     int dn_result = -1;                   // d_dn[] index of the valid denoised image, -1: none
     int output_source = RMR_OUTPUT_ACCUM; // what rmr_save_bmp / rmr_display* read
     int dn_tiled_steps = kDenoiseTiledSteps;   // bit i: pass i (step 2^i, i < 2) runs the LDS-tiled form
+    // variance-guided mode (rmr_denoise_variance): the seed plane and two filter planes of
+    // W x H floats, allocated at the first call, freed with the guide planes
+    float* d_var[3] = {nullptr, nullptr, nullptr};
+    bool dn_guided = false;               // the valid denoised image is rmr_denoise_variance's
+    int var_result = 0;                   // d_var[] index of its filtered variance (0: the seed itself)
+    int dnv_tiled_steps = kDenoiseVarTiledSteps;
     // per-tile error estimate and adaptive sampling (rmr_estimate.hip, adaptive.hpp)
     bool est_on = false;                  // every launch's fold is k_fold_half (rmr_set_error_estimate)
     bool est_valid = false;               // d_half holds the odd samples of everything in the accumulator
@@ -300,6 +308,7 @@ int free_slots(rmr_ctx* c);
 void free_guides(rmr_ctx* c) {
     for (float4*& b : c->d_guide) { if (b) (void)hipFree(b); b = nullptr; }
     for (float4*& b : c->d_dn) { if (b) (void)hipFree(b); b = nullptr; }
+    for (float*& b : c->d_var) { if (b) (void)hipFree(b); b = nullptr; }
     c->guides_valid = false;
     c->dn_result = -1;
 }
@@ -2097,6 +2106,7 @@ int rmr_denoise(rmr_ctx* c, const rmr_denoise_params* p) {
         return fail(c, RMR_E_INVALID, "bad denoise params (iterations 0..8, normal_pow2 0..7, sigma_z finite > 0, sigma_c finite >= 0)");
     int r;
     c->dn_result = -1;
+    c->dn_guided = false;
     if (!c->guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
@@ -2291,12 +2301,164 @@ int rmr_read_sample_counts(rmr_ctx* c, uint32_t* out, size_t bytes) {
     return RMR_OK;
 }
 
+// ---- variance-guided mode of the preview denoiser (rmr_denoise_var.hip) ----------------------------
+namespace {
+bool variance_params_ok(const rmr_variance_params& v) {
+    return std::isfinite(v.sigma_l) && v.sigma_l > 0.0f && v.var_radius >= 0 && v.var_radius <= 4;
+}
+
+// The seed and the guided passes over w x h images, queued on s: a / b / hit / nrm are read, dn[2] and
+// var[3] (var[0] the seed) written. *img and *vres receive the indices of the result in dn[] and var[].
+hipError_t run_guided(const float4* a, const float4* b, const float4* hit, const float4* nrm, int w, int h,
+                      const rmr_denoise_params& q, const rmr_variance_params& v, float4* const dn[2],
+                      float* const var[3], int tiled_mask, hipStream_t s, int* img, int* vres) {
+    rmr::VarianceSeed V{a, b, nrm, var[0], w, h, v.var_radius};
+    hipError_t e = rmr::launch_variance_seed(V, s);
+    if (e != hipSuccess) return e;
+    *img = 0;
+    *vres = 0;
+    if (q.iterations == 0)
+        return hipMemcpyAsync(dn[0], a, (size_t)w * h * sizeof(float4), hipMemcpyDeviceToDevice, s);
+    rmr::DenoiseVarPass P{};
+    P.d.hit = hit;
+    P.d.nrm = nrm;
+    P.d.W = w;
+    P.d.H = h;
+    P.d.normal_pow2 = q.normal_pow2;
+    P.sigma_l = v.sigma_l;
+    for (int i = 0; i < q.iterations; i++) {
+        P.d.in = i == 0 ? a : dn[(i - 1) & 1];
+        P.d.out = dn[i & 1];
+        P.var_in = i == 0 ? var[0] : var[1 + ((i - 1) & 1)];
+        P.var_out = var[1 + (i & 1)];
+        P.d.step = 1 << i;
+        P.d.sigma_z_step = q.sigma_z * (float)P.d.step;
+        const double sc = (double)q.sigma_c / (double)P.d.step;   // sigma_c 2^-i, as rmr_denoise
+        P.d.inv_sigma_c2 = q.sigma_c > 0.0f ? (float)std::min(1.0 / (sc * sc), (double)FLT_MAX) : 0.0f;
+        if ((e = rmr::launch_atrous_var(P, i < 2 && ((tiled_mask >> i) & 1), s)) != hipSuccess) return e;
+    }
+    *img = (q.iterations - 1) & 1;
+    *vres = 1 + ((q.iterations - 1) & 1);
+    return hipSuccess;
+}
+
+int guided_params(rmr_ctx* c, const rmr_denoise_params* p, const rmr_variance_params* v, rmr_denoise_params& q,
+                  rmr_variance_params& u) {
+    rmr_default_denoise_params(&q);
+    rmr_default_variance_params(&u);
+    if (p) q = *p;
+    if (v) u = *v;
+    if (!denoise_params_ok(q))
+        return fail(c, RMR_E_INVALID, "bad denoise params (iterations 0..8, normal_pow2 0..7, sigma_z finite > 0, sigma_c finite >= 0)");
+    if (!variance_params_ok(u)) return fail(c, RMR_E_INVALID, "bad variance params (sigma_l finite > 0, var_radius 0..4)");
+    return RMR_OK;
+}
+}  // namespace
+
+void rmr_default_variance_params(rmr_variance_params* p) {
+    if (!p) return;
+    p->sigma_l = 4.0f;
+    p->var_radius = 3;
+}
+
+int rmr_check_variance_params(const rmr_variance_params* p) {
+    return p && variance_params_ok(*p) ? RMR_OK : RMR_E_INVALID;
+}
+
+int rmr_denoise_variance(rmr_ctx* c, const rmr_denoise_params* p, const rmr_variance_params* v) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_denoise_params q;
+    rmr_variance_params u;
+    int r;
+    if ((r = guided_params(c, p, v, q, u))) return r;
+    if (!c->est_on || !c->est_valid || !c->d_half)
+        return fail(c, RMR_E_STATE, "the error estimate is not valid: call rmr_set_error_estimate before the first "
+                                    "render since rmr_reload, or render with rmr_render_adaptive");
+    c->dn_result = -1;
+    c->dn_guided = false;
+    if (!c->guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_var[0]) {
+        float* b[3] = {nullptr, nullptr, nullptr};
+        for (int i = 0; i < 3; i++)
+            if (hipMalloc((void**)&b[i], (size_t)c->W * c->H * sizeof(float)) != hipSuccess) {
+                (void)hipGetLastError();
+                for (int k = 0; k < i; k++) (void)hipFree(b[k]);
+                return fail(c, RMR_E_NOMEM, "cannot allocate the variance planes (3 x W x H x 4 bytes)");
+            }
+        for (int i = 0; i < 3; i++) c->d_var[i] = b[i];
+    }
+    int img = 0, vres = 0;
+    HIPCHK(c, run_guided(c->d_accum, c->d_half, c->d_guide[RMR_GUIDE_HIT], c->d_guide[RMR_GUIDE_NORMAL], c->W, c->H, q, u,
+                         c->d_dn, c->d_var, c->dnv_tiled_steps, c->stream, &img, &vres));
+    c->dn_result = img;
+    c->var_result = vres;
+    c->dn_guided = true;
+    return RMR_OK;
+}
+
+int rmr_read_variance(rmr_ctx* c, int which, float* out, size_t bytes) {
+    if (!c || !out) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (which != RMR_VARIANCE_SEED && which != RMR_VARIANCE_FILTERED) return fail(c, RMR_E_INVALID, "bad variance plane");
+    const size_t need = (size_t)c->W * c->H * sizeof(float);
+    if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
+    if (c->dn_result < 0 || !c->dn_guided)
+        return fail(c, RMR_E_STATE, "no valid variance planes (call rmr_denoise_variance)");
+    const float* src = c->d_var[which == RMR_VARIANCE_SEED ? 0 : c->var_result];
+    HIPCHK(c, hipMemcpyAsync(out, src, need, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+void* rmr_variance_device_ptr(rmr_ctx* c, int which) {
+    if (!c || (which != RMR_VARIANCE_SEED && which != RMR_VARIANCE_FILTERED)) return nullptr;
+    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
+    if (c->dn_result < 0 || !c->dn_guided) return nullptr;
+    return (void*)c->d_var[which == RMR_VARIANCE_SEED ? 0 : c->var_result];
+}
+
+int rmr_denoise_variance_images(rmr_ctx* c, const float* a_rgba, const float* b_rgba, const float* hit_rgba,
+                                const float* nrm_rgba, int w, int h, const rmr_denoise_params* p,
+                                const rmr_variance_params* v, float* out_rgba, float* out_seed, float* out_var) {
+    if (!c || !a_rgba || !b_rgba || !hit_rgba || !nrm_rgba || !out_rgba) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (w <= 0 || h <= 0 || w > 32768 || h > 32768) return fail(c, RMR_E_INVALID, "bad image size");
+    rmr_denoise_params q;
+    rmr_variance_params u;
+    int r;
+    if ((r = guided_params(c, p, v, q, u))) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)w * h * sizeof(float4), vbytes = (size_t)w * h * sizeof(float);
+    const float* src[4] = {a_rgba, b_rgba, hit_rgba, nrm_rgba};
+    float4* img[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // A, B, HIT, NORMAL, two filter images
+    float* var[3] = {nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipMalloc((void**)&img[i], bytes);
+    for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipMalloc((void**)&var[i], vbytes);
+    for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipMemcpyAsync(img[i], src[i], bytes, hipMemcpyHostToDevice, c->stream);
+    int ri = 0, rv = 0;
+    if (e == hipSuccess)
+        e = run_guided(img[0], img[1], img[2], img[3], w, h, q, u, img + 4, var, c->dnv_tiled_steps, c->stream, &ri, &rv);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rgba, img[4 + ri], bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && out_seed) e = hipMemcpyAsync(out_seed, var[0], vbytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && out_var) e = hipMemcpyAsync(out_var, var[rv], vbytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    for (float4* b : img) if (b) (void)hipFree(b);
+    for (float* b : var) if (b) (void)hipFree(b);
+    HIPCHK(c, e);
+    return RMR_OK;
+}
+
 #if RMR_DIAG
 // Diagnostic library only (not in include/rmr.h; tools/denoise_time.py): which a-trous passes run the
 // LDS-tiled form, bit i = the pass of step 2^i (i < 2); the results are the same either way.
 int rmr_diag_denoise_tiled(rmr_ctx* c, int mask) {
     if (!c || mask < 0 || mask > 3) return RMR_E_INVALID;
     c->dn_tiled_steps = mask;
+    c->dnv_tiled_steps = mask;
     return RMR_OK;
 }
 

@@ -153,4 +153,28 @@ struct DenoisePass {
     float inv_sigma_c2;         // 1 / (sigma_c 2^-i)^2; 0: no colour term
 };
 
+// The variance-guided filter (rmr_denoise_var.hip). The seed: the per-pixel variance
+// estimate of the accumulator A from the half image B, W x H floats, -1 where the pixel is not v-live.
+struct VarianceSeed {
+    const float4* a;
+    const float4* b;
+    const float4* nrm;          // (normal.xyz, id)
+    float* out;
+    int32_t W, H;
+    int32_t radius;             // the window is (2 radius + 1)^2 pixels, 0..4
+};
+// One guided pass: DenoisePass's, with the variance plane filtered alongside (never the same buffer in
+// and out). A pixel is v-live iff var_in >= 0.
+struct DenoiseVarPass {
+    DenoisePass d;
+    const float* var_in;
+    float* var_out;
+    float sigma_l;
+};
+#ifndef __HIPCC_RTC__
+hipError_t launch_variance_seed(const VarianceSeed& V, hipStream_t s);
+// tiled: the LDS form (step 1 or 2 only; other steps run the plain form)
+hipError_t launch_atrous_var(const DenoiseVarPass& A, bool tiled, hipStream_t s);
+#endif
+
 }  // namespace rmr

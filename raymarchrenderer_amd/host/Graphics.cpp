@@ -189,6 +189,20 @@ void Graphics::Denoise(int iterations) {
     p.iterations = iterations;
     check(rmr_denoise(g_ctx, &p), "Denoise");
 }
+void Graphics::setErrorEstimate(bool on) {
+    if (!need_ctx("setErrorEstimate") || !no_group("setErrorEstimate")) return;
+    check(rmr_set_error_estimate(g_ctx, on ? 1 : 0), "setErrorEstimate");
+}
+void Graphics::DenoiseVariance(int iterations, float sigma_l) {
+    if (!need_ctx("DenoiseVariance") || !no_group("DenoiseVariance")) return;
+    rmr_denoise_params p;
+    rmr_default_denoise_params(&p);
+    p.iterations = iterations;
+    rmr_variance_params v;
+    rmr_default_variance_params(&v);
+    v.sigma_l = sigma_l;
+    check(rmr_denoise_variance(g_ctx, &p, &v), "DenoiseVariance");
+}
 void Graphics::setOutputSource(int source) {
     if (!need_ctx("setOutputSource") || !no_group("setOutputSource")) return;
     check(rmr_set_output_source(g_ctx, source), "setOutputSource");

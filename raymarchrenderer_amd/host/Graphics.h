@@ -67,6 +67,11 @@ public:
     // fail with RMR_E_UNSUPPORTED and a message (rank 0 can denoise the reduced frame through
     // rmr_write_accum / a bound accumulator).
     static void Denoise(int iterations = 5);
+    // The variance-guided mode (rmr_denoise_variance, the other parameters at their defaults): needs the
+    // error estimate, so setErrorEstimate(true) after a Reload and before the first Render, or
+    // RenderAdaptive. Single-context mode only, like Denoise.
+    static void setErrorEstimate(bool on);
+    static void DenoiseVariance(int iterations = 5, float sigma_l = 4.0f);
     static void setOutputSource(int source);
     // Adaptive sampling (rmr_render_adaptive): after a Reload, render until every decision block's tile
     // error is at most p.threshold, at most p.max_samples samples per pixel (times[n] seeds sample n).

@@ -58,6 +58,7 @@ struct Options {
     bool print_tiles = false, print_view = false;  // host-only diagnostics (no GPU needed)
     rmr_params params;
     int denoise = -1;               // --denoise [N]: a-trous iterations, -1 = no denoise
+    double variance_guided = -1.0;  // --variance-guided [SIGMA_L]: the guided filter's sigma_l, < 0 = the plain filter
     std::string aov;                // --aov PREFIX: guide planes as PREFIX_*.pfm
     double adaptive = -1.0;         // --adaptive T: the tile-error threshold, < 0 = uniform sampling
     int min_samples = 16, pass_samples = 16;   // --min-samples / --pass-samples (rmr_adaptive_params)
@@ -188,6 +189,10 @@ rmr_adaptive_params adaptive_params(const Options& o) {
 // One render of the current scene: fixed-spp (samples > 0) or progressive (samples == 0).
 RenderResult render(const Options& o, unsigned first_pass) {
     Graphics::Reload();
+    if (o.variance_guided > 0) {   // the half image from the first sample on (rmr_denoise_variance needs it)
+        Graphics::setErrorEstimate(true);
+        if (Graphics::lastStatus() != RMR_OK) return RenderResult();
+    }
     Camera camera(Vector3(o.cam[0], o.cam[1], o.cam[2]), Vector3(o.cam[3], o.cam[4], o.cam[5]).normalized(),
                   (float)(Graphics::getImageSize().x / Graphics::getImageSize().y), PI / 4);
     if (!o.resume.empty()) {
@@ -287,6 +292,18 @@ bool write_aovs(const Options& o) {
     for (const auto& f : files) {
         const std::string path = o.aov + f.name;
         if (rmr_encode_pfm(f.img->data(), W, H, path.c_str()) != RMR_OK) {
+            std::cerr << "--aov: cannot write " << path << std::endl;
+            return false;
+        }
+        if (!o.quiet) std::cout << "Saved plane as: " << path << std::endl;
+    }
+    if (o.variance_guided > 0) {   // PREFIX_variance.pfm (R = the filtered variance, -1: not filtered)
+        std::vector<float> var((size_t)W * H), vp(n, 0.0f);
+        if (rmr_read_variance(c, RMR_VARIANCE_FILTERED, var.data(), var.size() * sizeof(float)) != RMR_OK)
+            return fail("rmr_read_variance");
+        for (size_t i = 0; i < var.size(); i++) vp[4 * i] = var[i];
+        const std::string path = o.aov + "_variance.pfm";
+        if (rmr_encode_pfm(vp.data(), W, H, path.c_str()) != RMR_OK) {
             std::cerr << "--aov: cannot write " << path << std::endl;
             return false;
         }
@@ -416,6 +433,9 @@ void usage() {
         "  --out FILE.bmp      (default output/<timestamp>.bmp)\n"
         "  --denoise [N]       after the render, filter the image with N a-trous iterations (0..8, default 5)\n"
         "                      and write --out from the denoised image\n"
+        "  --variance-guided [SIGMA_L]  with --denoise: the variance-guided filter (luminance weight of\n"
+        "                      SIGMA_L standard deviations, default 4; safe at any sample count); keeps the\n"
+        "                      error estimate on from the first sample; --aov adds PREFIX_variance.pfm\n"
         "  --aov PREFIX        first-hit planes as float PFM: PREFIX_normal.pfm, PREFIX_position.pfm,\n"
         "                      PREFIX_ray.pfm, PREFIX_depth_id.pfm (R = t, G = material id or -1, B = 0)\n"
         "  --adaptive T        adaptive sampling: render until every block's tile error is <= T, at most\n"
@@ -495,6 +515,16 @@ bool parse(int argc, char** argv, Options& o) {
             if (i + 1 < argc && argv[i + 1][0] != '\0' && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1])) {
                 o.denoise = std::atoi(argv[++i]);
                 if (o.denoise > 8 || std::strlen(argv[i]) > 2) return false;
+            }
+        } else if (a == "--variance-guided") {   // SIGMA_L is optional: taken when the next argument is no option
+            o.variance_guided = 4.0;
+            if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {
+                char* end = nullptr;
+                const char* v = argv[++i];
+                o.variance_guided = std::strtod(v, &end);
+                if (end == v || *end != '\0' || !std::isfinite(o.variance_guided) || !(o.variance_guided > 0) ||
+                    !std::isfinite((float)o.variance_guided) || !((float)o.variance_guided > 0.0f))
+                    return false;
             }
         } else if (a == "--aov") {
             o.aov = next("--aov");
@@ -578,6 +608,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--adaptive: not with --gpus / --devices, --resume, --per-sample or --interactive\n");
         return 2;
     }
+    if (o.variance_guided > 0 && (o.denoise < 0 || !o.devices.empty() || !o.resume.empty() || o.per_sample)) {
+        std::fprintf(stderr, "--variance-guided: needs --denoise; not with --gpus / --devices, --resume or --per-sample\n");
+        return 2;
+    }
     if (o.model.model != RMR_CAMERA_VIEW && !o.devices.empty()) {
         std::fprintf(stderr, "--camera MODEL: not with --gpus / --devices (the device group keeps the view's own rays)\n");
         return 2;
@@ -620,7 +654,8 @@ int main(int argc, char** argv) {
     if (Graphics::lastStatus() != RMR_OK) return 1;
     report(o, r);
     if (o.denoise >= 0) {
-        Graphics::Denoise(o.denoise);
+        if (o.variance_guided > 0) Graphics::DenoiseVariance(o.denoise, (float)o.variance_guided);
+        else Graphics::Denoise(o.denoise);
         if (Graphics::lastStatus() != RMR_OK) return 1;
         Graphics::setOutputSource(RMR_OUTPUT_DENOISED);
     }

@@ -492,6 +492,72 @@ class Renderer:
             source = names[source]
         self._chk(self._L.rmr_set_output_source(self._ctx, int(source)))
 
+    # -- variance-guided mode of the preview denoiser --
+    @staticmethod
+    def _guided_params(who, params, variance, kw):
+        if params is not None and not isinstance(params, abi.DenoiseParams):
+            raise TypeError("%s: params must be an abi.DenoiseParams" % who)
+        if variance is not None and not isinstance(variance, abi.VarianceParams):
+            raise TypeError("%s: variance must be an abi.VarianceParams" % who)
+        p = abi.default_denoise_params() if params is None else abi.DenoiseParams.from_buffer_copy(params)
+        v = abi.default_variance_params() if variance is None else abi.VarianceParams.from_buffer_copy(variance)
+        for k, val in kw.items():
+            if k in abi.DENOISE_FIELDS:
+                setattr(p, k, val)
+            elif k in abi.VARIANCE_FIELDS:
+                setattr(v, k, val)
+            else:
+                raise TypeError("%s: unknown parameter %r" % (who, k))
+        return p, v
+
+    @staticmethod
+    def _variance_plane(who, which):
+        if isinstance(which, str):
+            if which not in abi.VARIANCE_PLANES:
+                raise ValueError("%s: unknown plane %r (seed, filtered)" % (who, which))
+            return abi.VARIANCE_PLANES[which]
+        if isinstance(which, bool) or not isinstance(which, (int, np.integer)) or int(which) not in abi.VARIANCE_PLANES.values():
+            raise ValueError("%s: unknown plane %r (seed, filtered)" % (who, which))
+        return int(which)
+
+    def denoise_variance(self, params=None, variance=None, **kw):
+        """rmr_denoise_variance: the variance-guided filter over the accumulator (left unchanged); needs a
+        valid error estimate (set_error_estimate before the first render, or render_adaptive). Returns
+        the denoised image (H, W, 4). Keywords: denoise's, and sigma_l (4; > 0), var_radius (3; 0..4)."""
+        p, v = self._guided_params("denoise_variance", params, variance, kw)
+        self._chk(self._L.rmr_denoise_variance(self._ctx, C.byref(p), C.byref(v)))
+        return self.read_denoised()
+
+    def read_variance(self, which="filtered"):
+        """One variance plane of the last denoise_variance as an (H, W) float32 array: 'seed' or
+        'filtered' (abi.VARIANCE_*); -1 where the pixel is not v-live."""
+        which = self._variance_plane("read_variance", which)
+        w, h = self.image_size()
+        out = np.zeros((h, w), np.float32)
+        self._chk(self._L.rmr_read_variance(self._ctx, which, _fp(out), out.nbytes))
+        return out
+
+    def variance_device_ptr(self, which="filtered"):
+        """Device pointer of a valid variance plane (W x H floats), None without one."""
+        which = self._variance_plane("variance_device_ptr", which)
+        return self._L.rmr_variance_device_ptr(self._ctx, which)
+
+    def denoise_variance_images(self, A, B, hit, normal, params=None, variance=None, **kw):
+        """rmr_denoise_variance_images (test hook): the seed and the guided passes on four host (h, w, 4)
+        images. Returns (image (h, w, 4), seed (h, w), filtered variance (h, w))."""
+        p, v = self._guided_params("denoise_variance_images", params, variance, kw)
+        imgs = [np.ascontiguousarray(x, np.float32) for x in (A, B, hit, normal)]
+        if imgs[0].ndim != 3 or imgs[0].shape[2] != 4 or any(x.shape != imgs[0].shape for x in imgs):
+            raise ValueError("denoise_variance_images: A, B, hit and normal must be (h, w, 4) images of one shape, got %s"
+                             % ", ".join(str(x.shape) for x in imgs))
+        h, w = imgs[0].shape[:2]
+        out = np.zeros((h, w, 4), np.float32)
+        seed = np.zeros((h, w), np.float32)
+        var = np.zeros((h, w), np.float32)
+        self._chk(self._L.rmr_denoise_variance_images(self._ctx, _fp(imgs[0]), _fp(imgs[1]), _fp(imgs[2]), _fp(imgs[3]),
+                                                       w, h, C.byref(p), C.byref(v), _fp(out), _fp(seed), _fp(var)))
+        return out, seed, var
+
     # -- per-tile error estimate and adaptive sampling --
     def set_error_estimate(self, on=True):
         """rmr_set_error_estimate: while on, every fold also keeps the half image (the mean of the
