@@ -382,6 +382,101 @@ int rmr_denoise_variance_images(rmr_ctx* ctx, const float* a_rgba, const float* 
                                 const float* nrm_rgba, int w, int h, const rmr_denoise_params* p,
                                 const rmr_variance_params* v, float* out_rgba, float* out_seed, float* out_var);
 
+/* ---- temporal reprojection of the preview across camera moves ------------------------------ */
+/* No counterpart in the reference, whose setView starts again from noise. A history image (colour and
+ * an effective sample count per pixel, with the guides and the view it was made with) is re-projected into
+ * the current view through the current guides' hit points, validated against the history's own guides and
+ * blended with the current frame by sample count. The scene is static between scene loads, so the previous
+ * position of a surface point is a projection, not a motion-vector guess. Additive: no other entry point
+ * computes anything else, and a context that never calls rmr_temporal_accumulate allocates nothing for it.
+ *
+ * S: the source image (accumulator or denoised image) with the caller's sample count n_cur; HIT, NORMAL:
+ * the current guides; Hc, Hn, Hhit, Hnrm: the history's colour, count (0 = none) and guides; eye', r00',
+ * r01', r10', r11': the history's view. Host, in double from the float view (rmr_temporal_view_inverse):
+ *   a = r01' - r00', b = r10' - r00', c = (r11' - r10') - a, Minv = [a | b | r00']^-1, k = Minv c,
+ * both rounded to float. The history's guide ray at image coordinates (u, v) is r00' + u a + v b + u v c
+ * (primary_dir with both horizontal jitters equal); c = 0 for rmr_camera_view's views up to rounding.
+ * Per pixel p, every float32 operation rounded on its own except where fma() is written:
+ *  1. p is live iff its guide id >= 0, S.a != 0 and S.rgb is finite (rmr_denoise's rule). A pixel that is
+ *     not live: out = S bit for bit, n_out = 0.
+ *  2. x = HIT.xyz, n = NORMAL.xyz, id = NORMAL.w, t = HIT.w; d = x - eye';
+ *       (U0, V0, w0)_i = fma(Minv_i0, d.x, fma(Minv_i1, d.y, Minv_i2 * d.z))
+ *     lambda (r00' + u a + v b + u v c) = d with U = lambda u, V = lambda v, w = lambda reads
+ *     (U, V, w) = (U0, V0, w0) - T k, T = U V / w: the root of A T^2 - B T + C = 0 next to C / B,
+ *       A = fma(k0, k1, k2), B = fma(U0, k1, fma(V0, k0, w0)), C = U0 * V0
+ *       T = C / B, then three times T = T - fma(fma(A, T, -B), T, C) / fma(A + A, T, -B)
+ *       U = fma(-T, k0, U0), V = fma(-T, k1, V0), w = fma(-T, k2, w0)
+ *       fx = (U / w) * W, fy = (V / w) * H              (pixel q's centre is at q + 0.5)
+ *     No history for p when !(w > 0) or fx or fy is not finite.
+ *     Accuracy: with e = 2^-24, a_i = sum_j |Minv_ij| |d_j|, K_i = |k_i| and, where |A C| <= B^2 / 16,
+ *       Ta = (a_0 a_1 + |T| (a_2 + a_0 K_1 + a_1 K_0) + T^2 (K_0 K_1 + K_2)) / |B|
+ *       |fx - fx*| <= 20 e W ((a_0 + K_0 Ta) + |U / w| (a_2 + K_2 Ta)) / w      (fy: a_1, K_1, V, H)
+ *     against the exact solution fx* of the float view and hit point. Count: each product Minv_ij d_j
+ *     carries 5 roundings (Minv, d, the product, two sums), B 8, C 11, A 3; the Newton steps correct
+ *     themselves, so T carries the residual's 14 over |2 A T - B| >= 0.875 |B|: 16; U, V, w then 16 of
+ *     their own terms; the two quotients' and the scale's roundings bring (16 + 2); 20 leaves room for the
+ *     second-order terms. After the three steps the iteration's own error is below (1/16)^15.
+ *  3. g = (fx, fy) - 0.5, q0 = floor(g), (tx, ty) = g - q0; the taps q = q0 + (i, j), i, j in {0, 1}, in
+ *     the order (0,0) (1,0) (0,1) (1,1), b_q = (i ? tx : 1 - tx) * (j ? ty : 1 - ty). A tap counts iff it
+ *     is on the image, Hn(q) > 0 and Hid(q) == id; its weight is g_q = b_q * (a_q z_q) with rmr_denoise's
+ *       a_q = max(0, fma(n.x, n_q.x, fma(n.y, n_q.y, n.z * n_q.z))) squared normal_pow2 times
+ *       z_q = exp(-|fma(n.x, x_q.x - x.x, fma(n.y, x_q.y - x.y, n.z * (x_q.z - x.z)))|
+ *                 * min(1 / (sigma_z * max(t, FLT_MIN)), FLT_MAX))
+ *     Every discrete test multiplies a b_q that is 0 where the tap set changes: the result is continuous
+ *     in (fx, fy).
+ *  4. G = sum g_q, h = (sum g_q Hc(q).rgb) / G (sums by fma(g_q, value, sum) in tap order),
+ *     m = min(max_history, sum g_q Hn(q)) (not divided by G: a half-trusted history counts for half)
+ *       out.rgb = (m * h + n_cur * S.rgb) / (m + n_cur), out.a = S.a, n_out = min(m + n_cur, max_history)
+ *     No history, !(G > 0), !(m > 0) or h not finite: out = S bit for bit, n_out = min(n_cur, max_history). */
+typedef struct rmr_temporal_params {
+    float   max_history;  /* 64    finite, >= 1: cap of the effective sample count              */
+    float   sigma_z;      /* 0.02  finite, > 0: plane distance, relative to the centre's t      */
+    int32_t normal_pow2;  /* 5     0..7: squarings of the normal term                           */
+} rmr_temporal_params;
+void rmr_default_temporal_params(rmr_temporal_params* p);
+/* RMR_OK when every field is in its range, else RMR_E_INVALID (no context, no GPU). */
+int rmr_check_temporal_params(const rmr_temporal_params* p);
+/* The host's part of the projection (no context, no GPU): out[0..8] = Minv row-major, out[9..11] = k, in
+ * double, of view = eye', r00', r01', r10', r11'. RMR_E_INVALID for a view that is not finite, has a zero
+ * corner ray or whose |det [a | b | r00']| <= 1e-9 |a| |b| |r00'| (corner rays coplanar with the eye). */
+int rmr_temporal_view_inverse(const float view[15], double out[12]);
+/* One step of the stage: S = the accumulator (source RMR_OUTPUT_ACCUM) or the valid denoised image
+ * (RMR_OUTPUT_DENOISED; RMR_E_STATE without one), `samples` = n_cur, finite and > 0; p NULL = the defaults;
+ * RMR_E_INVALID outside the ranges. Renders full-image guides first when they are not valid; RMR_E_STATE
+ * under the equirect and ortho camera models and without a scene. The result becomes the new history (it
+ * is written to the other of two buffer pairs, never in place), and the current guides (a device copy of
+ * the two planes; rmr_guide_device_ptr keeps returning what it returned) and view become the history's.
+ * With no history (the first call, after rmr_temporal_reset, a scene load or rmr_reload, or a history view
+ * rmr_temporal_view_inverse refuses) every Hn is 0, so the call stores S with count min(samples,
+ * max_history) (0 where the pixel is not live). rmr_set_view, rmr_set_params, a camera-model change and
+ * rendering keep the history; rmr_reload also frees the stage's buffers (two colour, two count and two
+ * guide planes, 72 bytes per pixel, allocated at the first call; RMR_E_NOMEM if that fails). The
+ * accumulator, the guides, the denoised image and every other image of the context are not written. Runs on
+ * the context's stream without synchronising, after flushing held rmr_render calls. */
+int rmr_temporal_accumulate(rmr_ctx* ctx, int source, float samples, const rmr_temporal_params* p);
+/* Drop the history (the buffers stay); RMR_OUTPUT_TEMPORAL has no valid image until the next step. */
+int rmr_temporal_reset(rmr_ctx* ctx);
+/* The temporal image as RGBA32F and its counts as W x H floats (both synchronise), and the image's device
+ * pointer (the next step returns the other buffer); RMR_E_STATE / NULL without a valid one. */
+int rmr_read_temporal(rmr_ctx* ctx, float* rgba, size_t bytes);
+int rmr_read_temporal_count(rmr_ctx* ctx, float* out, size_t bytes);
+void* rmr_temporal_device_ptr(rmr_ctx* ctx);
+/* rmr_set_output_source: rmr_save_bmp / rmr_display* read the temporal image. Without a valid one
+ * rmr_set_output_source(RMR_OUTPUT_TEMPORAL) returns RMR_E_STATE and leaves the source as it was, and those
+ * calls return RMR_E_STATE when the image has become invalid since (rmr_temporal_reset, a scene load,
+ * rmr_reload). */
+#define RMR_OUTPUT_TEMPORAL 2
+/* Test hook: the same kernel on host images uploaded for the call (w x h RGBA32F each, h_n w x h floats):
+ * S, RMR_GUIDE_HIT, RMR_GUIDE_NORMAL of the current view, the history's colour, count and guides, and the
+ * history's view. `view`, the current view, is not read (the hit points carry it) and may be NULL. out_n:
+ * w x h floats; out_xy (may be NULL): w x h x 2 floats, (fx, fy) of step 2, NaN where the pixel is not
+ * live or has no projection. Needs no scene and leaves every image of the context as it was.
+ * RMR_E_INVALID for an h_view rmr_temporal_view_inverse refuses. Synchronises. */
+int rmr_temporal_images(rmr_ctx* ctx, const float* s_rgba, const float* hit, const float* nrm, const float view[15],
+                        const float* h_rgba, const float* h_n, const float* h_hit, const float* h_nrm,
+                        const float h_view[15], int w, int h, float samples, const rmr_temporal_params* p,
+                        float* out_rgba, float* out_n, float* out_xy);
+
 /* ---- camera models and caller-supplied rays ------------------------------------------------ */
 /* No counterpart in the reference, whose only camera is main()'s jittered interpolation of the four
  * corner rays from one point, the eye (RM1:569-584). Additive: with RMR_CAMERA_VIEW (the default) every

@@ -37,6 +37,8 @@ EXPORTS = [
     "rmr_query_rejects", "rmr_set_query_grid",
     "rmr_default_variance_params", "rmr_check_variance_params", "rmr_denoise_variance", "rmr_read_variance",
     "rmr_variance_device_ptr", "rmr_denoise_variance_images",
+    "rmr_default_temporal_params", "rmr_check_temporal_params", "rmr_temporal_view_inverse", "rmr_temporal_accumulate",
+    "rmr_temporal_reset", "rmr_read_temporal", "rmr_read_temporal_count", "rmr_temporal_device_ptr", "rmr_temporal_images",
 ]
 
 
@@ -175,10 +177,21 @@ def lib(diag=None):
         "rmr_variance_device_ptr": (vp, [vp, C.c_int]),
         "rmr_denoise_variance_images": (C.c_int, [vp, fp, fp, fp, fp, C.c_int, C.c_int, C.POINTER(abi.DenoiseParams),
                                                   C.POINTER(abi.VarianceParams), fp, fp, fp]),
+        "rmr_default_temporal_params": (None, [C.POINTER(abi.TemporalParams)]),
+        "rmr_check_temporal_params": (C.c_int, [C.POINTER(abi.TemporalParams)]),
+        "rmr_temporal_view_inverse": (C.c_int, [fp, dp]),
+        "rmr_temporal_accumulate": (C.c_int, [vp, C.c_int, C.c_float, C.POINTER(abi.TemporalParams)]),
+        "rmr_temporal_reset": (C.c_int, [vp]),
+        "rmr_read_temporal": (C.c_int, [vp, fp, C.c_size_t]),
+        "rmr_read_temporal_count": (C.c_int, [vp, fp, C.c_size_t]),
+        "rmr_temporal_device_ptr": (vp, [vp]),
+        "rmr_temporal_images": (C.c_int, [vp, fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_float,
+                                          C.POINTER(abi.TemporalParams), fp, fp, fp]),
         # diagnostic library only (rmr_api.cpp RMR_DIAG): ray_exit at given rays; the a-trous passes
         # that run the LDS-tiled form
         "rmr_diag_ray_exit": (C.c_int, [vp, fp, C.c_int, fp, fp, C.c_int, ip]),
         "rmr_diag_denoise_tiled": (C.c_int, [vp, C.c_int]),
+        "rmr_diag_temporal_keep": (C.c_int, [vp, C.c_int]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(L, name):   # (an older build given by path may lack a newer entry point)

@@ -142,6 +142,23 @@ def default_variance_params(**kw):
     return p
 
 
+class TemporalParams(C.Structure):
+    _fields_ = [("max_history", C.c_float), ("sigma_z", C.c_float), ("normal_pow2", C.c_int32)]
+
+
+TEMPORAL_FIELDS = ("max_history", "sigma_z", "normal_pow2")
+
+
+def default_temporal_params(**kw):
+    """rmr_default_temporal_params' values (rmr.h), with overrides."""
+    p = TemporalParams(64.0, 0.02, 5)
+    for k, v in kw.items():
+        if k not in TEMPORAL_FIELDS:
+            raise TypeError("unknown temporal parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("threshold", C.c_float), ("offset", C.c_float), ("min_samples", C.c_uint32),
                 ("pass_samples", C.c_uint32), ("max_samples", C.c_uint32), ("block_tiles", C.c_int32)]
@@ -217,6 +234,8 @@ GUIDE_NORMAL = 2
 GUIDE_PLANES = {"ray": GUIDE_RAY, "hit": GUIDE_HIT, "normal": GUIDE_NORMAL}
 OUTPUT_ACCUM = 0
 OUTPUT_DENOISED = 1
+OUTPUT_TEMPORAL = 2
+OUTPUT_SOURCES = {"accum": OUTPUT_ACCUM, "denoised": OUTPUT_DENOISED, "temporal": OUTPUT_TEMPORAL}
 # variance planes of the variance-guided denoiser (rmr.h)
 VARIANCE_SEED = 0
 VARIANCE_FILTERED = 1

@@ -28,6 +28,7 @@
 #include "rmr_ray_check.h"
 #include "rmr_jit.hpp"
 #include "scene.hpp"
+#include "temporal.hpp"
 
 namespace rmr {
 hipError_t launch_trace(const KParams& P, int variant, int np, bool prog, bool persistent, int grid, hipStream_t s);
@@ -135,6 +136,15 @@ struct rmr_ctx {
     bool dn_guided = false;               // the valid denoised image is rmr_denoise_variance's
     int var_result = 0;                   // d_var[] index of its filtered variance (0: the seed itself)
     int dnv_tiled_steps = kDenoiseVarTiledSteps;
+    // temporal reprojection (rmr_temporal_accumulate): two pairs of history colour (W x H
+    // float4) and count (W x H float) that the steps alternate between, and the history's HIT and NORMAL
+    // planes; allocated at the first call, freed at rmr_reload / rmr_destroy
+    float4* d_tcol[2] = {nullptr, nullptr};
+    float* d_tn[2] = {nullptr, nullptr};
+    float4* d_tguide[2] = {nullptr, nullptr};
+    int t_cur = -1;                       // the pair that holds the history (= the temporal image), -1: none
+    float t_view[15];                     // the view the history was made with
+    bool t_keep = false;                  // diagnostic library (tools/temporal_time.py): a step leaves the history as it is
     // per-tile error estimate and adaptive sampling (rmr_estimate.hip, adaptive.hpp)
     bool est_on = false;                  // every launch's fold is k_fold_half (rmr_set_error_estimate)
     bool est_valid = false;               // d_half holds the odd samples of everything in the accumulator
@@ -313,6 +323,14 @@ void free_guides(rmr_ctx* c) {
     c->dn_result = -1;
 }
 
+// Release the temporal stage's planes (the caller has synced the context's stream).
+void free_temporal(rmr_ctx* c) {
+    for (float4*& b : c->d_tcol) { if (b) (void)hipFree(b); b = nullptr; }
+    for (float*& b : c->d_tn) { if (b) (void)hipFree(b); b = nullptr; }
+    for (float4*& b : c->d_tguide) { if (b) (void)hipFree(b); b = nullptr; }
+    c->t_cur = -1;
+}
+
 // Release the half image and the tile-error map (the caller has synced the context's stream).
 void free_estimate(rmr_ctx* c) {
     if (c->d_half) (void)hipFree(c->d_half);
@@ -435,6 +453,7 @@ int upload_scene(rmr_ctx* c) {
     c->esc_infl_dev = -1.0;
     c->scene_kp = scene_params(c);
     c->guides_valid = false;   // (every scene load comes through here)
+    c->t_cur = -1;             // the temporal history is of the old scene
     c->dn_result = -1;
     c->scene_loaded = true;
     c->jit_ready = false;
@@ -1039,6 +1058,10 @@ int output_image(rmr_ctx* c, const char* who, const float4** out) {
         if (c->dn_result < 0)
             return fail(c, RMR_E_STATE, std::string(who) + ": output source is the denoised image, but none is valid (call rmr_denoise)");
         *out = c->d_dn[c->dn_result];
+    } else if (c->output_source == RMR_OUTPUT_TEMPORAL) {
+        if (c->t_cur < 0)
+            return fail(c, RMR_E_STATE, std::string(who) + ": output source is the temporal image, but none is valid (call rmr_temporal_accumulate)");
+        *out = c->d_tcol[c->t_cur];
     } else {
         *out = c->d_accum;
     }
@@ -1161,6 +1184,7 @@ void rmr_destroy(rmr_ctx* c) {
     for (auto& e : c->tile_cache) (void)hipFree(e.dev);
     if (c->h_times) (void)hipHostFree(c->h_times);
     free_guides(c);
+    free_temporal(c);
     if (c->d_half) (void)hipFree(c->d_half);
     if (c->d_tile_err) (void)hipFree(c->d_tile_err);
     if (c->d_accum && !c->accum_external) (void)hipFree(c->d_accum);
@@ -1289,6 +1313,7 @@ int rmr_reload(rmr_ctx* c) {
         return fail(c, RMR_E_STATE, "bound accumulator cannot be resized");
     const bool resize = (c->pend_W != c->W || c->pend_H != c->H);
     free_guides(c);   // (the stream is idle)
+    free_temporal(c);
     c->W = c->pend_W;
     c->H = c->pend_H;
     if (resize) {
@@ -2155,7 +2180,10 @@ void* rmr_denoised_device_ptr(rmr_ctx* c) {
 int rmr_set_output_source(rmr_ctx* c, int source) {
     if (!c) return RMR_E_INVALID;
     RMR_FLUSH(c);
-    if (source != RMR_OUTPUT_ACCUM && source != RMR_OUTPUT_DENOISED) return fail(c, RMR_E_INVALID, "bad output source");
+    if (source != RMR_OUTPUT_ACCUM && source != RMR_OUTPUT_DENOISED && source != RMR_OUTPUT_TEMPORAL) return fail(c, RMR_E_INVALID, "bad output source");
+    // (refused, the source unchanged, while there is no temporal image to read)
+    if (source == RMR_OUTPUT_TEMPORAL && c->t_cur < 0)
+        return fail(c, RMR_E_STATE, "no valid temporal image (call rmr_temporal_accumulate)");
     c->output_source = source;
     return RMR_OK;
 }
@@ -2452,6 +2480,190 @@ int rmr_denoise_variance_images(rmr_ctx* c, const float* a_rgba, const float* b_
     return RMR_OK;
 }
 
+// ---- temporal reprojection of the preview (rmr_temporal.hip, temporal.cpp) -------------------------
+namespace {
+// The pass over w x h images on s. h_view: the history's view; false when temporal_view_inverse refuses it.
+bool temporal_pass(rmr::TemporalPass& T, const float h_view[15], int w, int h, float samples, const rmr_temporal_params& q) {
+    double inv[12];
+    if (!rmr::temporal_view_inverse(h_view, inv)) return false;
+    T.d.W = w;
+    T.d.H = h;
+    T.d.step = 1;
+    T.d.normal_pow2 = q.normal_pow2;
+    T.d.sigma_z_step = q.sigma_z;
+    T.d.inv_sigma_c2 = 0.0f;
+    for (int i = 0; i < 3; i++) T.eye[i] = h_view[i];
+    for (int i = 0; i < 9; i++) T.minv[i] = (float)inv[i];
+    for (int i = 0; i < 3; i++) T.twist[i] = (float)inv[9 + i];
+    T.Wf = (float)w;
+    T.Hf = (float)h;
+    T.n_cur = samples;
+    T.max_history = q.max_history;
+    return true;
+}
+
+int temporal_params(rmr_ctx* c, const rmr_temporal_params* p, float samples, rmr_temporal_params& q) {
+    rmr_default_temporal_params(&q);
+    if (p) q = *p;
+    if (!rmr::temporal_params_ok(q))
+        return fail(c, RMR_E_INVALID, "bad temporal params (max_history finite >= 1, sigma_z finite > 0, normal_pow2 0..7)");
+    if (!std::isfinite(samples) || !(samples > 0.0f)) return fail(c, RMR_E_INVALID, "samples must be finite and > 0");
+    return RMR_OK;
+}
+}  // namespace
+
+int rmr_temporal_accumulate(rmr_ctx* c, int source, float samples, const rmr_temporal_params* p) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_temporal_params q;
+    int r;
+    if ((r = temporal_params(c, p, samples, q))) return r;
+    if (source != RMR_OUTPUT_ACCUM && source != RMR_OUTPUT_DENOISED)
+        return fail(c, RMR_E_INVALID, "bad source (RMR_OUTPUT_ACCUM or RMR_OUTPUT_DENOISED)");
+    if (!c->scene_loaded) return fail(c, RMR_E_STATE, "no scene loaded (call rmr_load_scene_json / rmr_load_builtin_scene)");
+    if (c->camera.model == RMR_CAMERA_EQUIRECT || c->camera.model == RMR_CAMERA_ORTHO)
+        return fail(c, RMR_E_STATE, "no first-hit guides for the equirect and ortho camera models");
+    if (source == RMR_OUTPUT_DENOISED && c->dn_result < 0)
+        return fail(c, RMR_E_STATE, "no valid denoised image (call rmr_denoise)");
+    if (!c->guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t px = (size_t)c->W * c->H, bytes = px * sizeof(float4);
+    if (!c->d_tcol[0]) {
+        void* b[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        for (int i = 0; i < 6; i++)
+            if (hipMalloc(&b[i], i == 2 || i == 3 ? px * sizeof(float) : bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                for (int k = 0; k < i; k++) (void)hipFree(b[k]);
+                return fail(c, RMR_E_NOMEM, "cannot allocate the temporal planes (72 bytes per pixel)");
+            }
+        c->d_tcol[0] = (float4*)b[0]; c->d_tcol[1] = (float4*)b[1];
+        c->d_tn[0] = (float*)b[2]; c->d_tn[1] = (float*)b[3];
+        c->d_tguide[0] = (float4*)b[4]; c->d_tguide[1] = (float4*)b[5];
+        c->t_cur = -1;
+    }
+    rmr::TemporalPass T{};
+    bool have = c->t_cur >= 0 && temporal_pass(T, c->t_view, c->W, c->H, samples, q);
+    if (!have) {
+        // no history: the same kernel against counts of 0 (every other history plane zeroed, so that what
+        // the skipped taps never read is defined), projected with the current view or, if that is
+        // degenerate too, with the identity
+        static const float kIdent[15] = {0, 0, 0, 0, 0, 1, 1, 0, 1, 0, 1, 1, 1, 1, 1};
+        if (!c->view_set) default_view(c);
+        if (!temporal_pass(T, c->view, c->W, c->H, samples, q)) (void)temporal_pass(T, kIdent, c->W, c->H, samples, q);
+        c->t_cur = 0;
+        HIPCHK(c, hipMemsetAsync(c->d_tcol[0], 0, bytes, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_tn[0], 0, px * sizeof(float), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_tguide[0], 0, bytes, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_tguide[1], 0, bytes, c->stream));
+    }
+    const int from = c->t_cur, to = 1 - from;
+    c->t_cur = -1;   // (until everything below is queued)
+    T.d.in = source == RMR_OUTPUT_DENOISED ? c->d_dn[c->dn_result] : c->d_accum;
+    T.d.hit = c->d_guide[RMR_GUIDE_HIT];
+    T.d.nrm = c->d_guide[RMR_GUIDE_NORMAL];
+    T.d.out = c->d_tcol[to];
+    T.n_out = c->d_tn[to];
+    T.h_col = c->d_tcol[from];
+    T.h_n = c->d_tn[from];
+    T.h_hit = c->d_tguide[0];
+    T.h_nrm = c->d_tguide[1];
+    T.xy_out = nullptr;
+    HIPCHK(c, rmr::launch_temporal(T, c->stream));
+    if (c->t_keep) {   // (timing the kernel alone against one history)
+        c->t_cur = from;
+        return RMR_OK;
+    }
+    // the current guides and view become the history's
+    HIPCHK(c, hipMemcpyAsync(c->d_tguide[0], c->d_guide[RMR_GUIDE_HIT], bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_tguide[1], c->d_guide[RMR_GUIDE_NORMAL], bytes, hipMemcpyDeviceToDevice, c->stream));
+    std::memcpy(c->t_view, c->view, sizeof c->t_view);
+    c->t_cur = to;
+    return RMR_OK;
+}
+
+int rmr_temporal_reset(rmr_ctx* c) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    c->t_cur = -1;
+    return RMR_OK;
+}
+
+int rmr_read_temporal(rmr_ctx* c, float* rgba, size_t bytes) {
+    if (!c || !rgba) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    const size_t need = (size_t)c->W * c->H * sizeof(float4);
+    if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
+    if (c->t_cur < 0) return fail(c, RMR_E_STATE, "no valid temporal image (call rmr_temporal_accumulate)");
+    HIPCHK(c, hipMemcpyAsync(rgba, c->d_tcol[c->t_cur], need, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+int rmr_read_temporal_count(rmr_ctx* c, float* out, size_t bytes) {
+    if (!c || !out) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    const size_t need = (size_t)c->W * c->H * sizeof(float);
+    if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
+    if (c->t_cur < 0) return fail(c, RMR_E_STATE, "no valid temporal image (call rmr_temporal_accumulate)");
+    HIPCHK(c, hipMemcpyAsync(out, c->d_tn[c->t_cur], need, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+void* rmr_temporal_device_ptr(rmr_ctx* c) {
+    if (!c) return nullptr;
+    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
+    return c->t_cur < 0 ? nullptr : (void*)c->d_tcol[c->t_cur];
+}
+
+int rmr_temporal_images(rmr_ctx* c, const float* s_rgba, const float* hit, const float* nrm, const float view[15],
+                        const float* h_rgba, const float* h_n, const float* h_hit, const float* h_nrm,
+                        const float h_view[15], int w, int h, float samples, const rmr_temporal_params* p,
+                        float* out_rgba, float* out_n, float* out_xy) {
+    (void)view;   // (the hit points carry the current view)
+    if (!c || !s_rgba || !hit || !nrm || !h_rgba || !h_n || !h_hit || !h_nrm || !h_view || !out_rgba || !out_n)
+        return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (w <= 0 || h <= 0 || w > 32768 || h > 32768) return fail(c, RMR_E_INVALID, "bad image size");
+    rmr_temporal_params q;
+    int r;
+    if ((r = temporal_params(c, p, samples, q))) return r;
+    rmr::TemporalPass T{};
+    if (!temporal_pass(T, h_view, w, h, samples, q))
+        return fail(c, RMR_E_INVALID, "degenerate history view (rmr_temporal_view_inverse)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t px = (size_t)w * h, bytes = px * sizeof(float4), nbytes = px * sizeof(float);
+    // S, HIT, NORMAL, Hc, Hhit, Hnrm, out | Hn, n_out | xy
+    const float* src[6] = {s_rgba, hit, nrm, h_rgba, h_hit, h_nrm};
+    float4* img[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float* cnt[2] = {nullptr, nullptr};
+    float2* xy = nullptr;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 7 && e == hipSuccess; i++) e = hipMalloc((void**)&img[i], bytes);
+    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void**)&cnt[i], nbytes);
+    if (out_xy && e == hipSuccess) e = hipMalloc((void**)&xy, px * sizeof(float2));
+    for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipMemcpyAsync(img[i], src[i], bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cnt[0], h_n, nbytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        T.d.in = img[0]; T.d.hit = img[1]; T.d.nrm = img[2];
+        T.h_col = img[3]; T.h_hit = img[4]; T.h_nrm = img[5];
+        T.d.out = img[6];
+        T.h_n = cnt[0]; T.n_out = cnt[1];
+        T.xy_out = xy;
+        e = rmr::launch_temporal(T, c->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rgba, img[6], bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_n, cnt[1], nbytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && out_xy) e = hipMemcpyAsync(out_xy, xy, px * sizeof(float2), hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    for (float4* b : img) if (b) (void)hipFree(b);
+    for (float* b : cnt) if (b) (void)hipFree(b);
+    if (xy) (void)hipFree(xy);
+    HIPCHK(c, e);
+    return RMR_OK;
+}
+
 #if RMR_DIAG
 // Diagnostic library only (not in include/rmr.h; tools/denoise_time.py): which a-trous passes run the
 // LDS-tiled form, bit i = the pass of step 2^i (i < 2); the results are the same either way.
@@ -2459,6 +2671,15 @@ int rmr_diag_denoise_tiled(rmr_ctx* c, int mask) {
     if (!c || mask < 0 || mask > 3) return RMR_E_INVALID;
     c->dn_tiled_steps = mask;
     c->dnv_tiled_steps = mask;
+    return RMR_OK;
+}
+
+// Diagnostic library only (not in include/rmr.h; tools/temporal_time.py): while on, rmr_temporal_accumulate
+// runs its kernel against the history it has and leaves that history (image, guides and view) in place,
+// so that repeated calls time the kernel alone on one view pair.
+int rmr_diag_temporal_keep(rmr_ctx* c, int on) {
+    if (!c) return RMR_E_INVALID;
+    c->t_keep = on != 0;
     return RMR_OK;
 }
 

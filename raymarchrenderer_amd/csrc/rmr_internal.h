@@ -171,7 +171,27 @@ struct DenoiseVarPass {
     float* var_out;
     float sigma_l;
 };
+// Temporal reprojection of the preview (rmr_temporal.hip): the source image d.in and
+// the current guides d.hit / d.nrm against a history (colour, effective sample count and the guides it
+// was made with), into d.out / n_out, never the history's own buffers. d.step is 1, d.sigma_z_step is
+// sigma_z and d.inv_sigma_c2 is 0, so rmr_atrous.h's tap_weight is the stage's a_q z_q.
+struct TemporalPass {
+    DenoisePass d;
+    const float4* h_col;
+    const float* h_n;           // 0: no history at that pixel
+    const float4* h_hit;
+    const float4* h_nrm;
+    float* n_out;
+    float2* xy_out;             // the projected coordinates (NaN: none), or null
+    float eye[3];               // the history view's eye
+    float minv[9];              // [r01'-r00' | r10'-r00' | r00']^-1, row-major (temporal.hpp view_inverse)
+    float twist[3];             // that inverse times (r11'-r10') - (r01'-r00')
+    float Wf, Hf;
+    float n_cur;                // the source's sample count
+    float max_history;
+};
 #ifndef __HIPCC_RTC__
+hipError_t launch_temporal(const TemporalPass& T, hipStream_t s);
 hipError_t launch_variance_seed(const VarianceSeed& V, hipStream_t s);
 // tiled: the LDS form (step 1 or 2 only; other steps run the plain form)
 hipError_t launch_atrous_var(const DenoiseVarPass& A, bool tiled, hipStream_t s);

@@ -483,14 +483,84 @@ class Renderer:
         return self._L.rmr_denoised_device_ptr(self._ctx)
 
     def set_output_source(self, source):
-        """What save_bmp / display / display_device read: abi.OUTPUT_ACCUM (default) or
-        abi.OUTPUT_DENOISED (also 'accum' / 'denoised')."""
+        """What save_bmp / display / display_device read: abi.OUTPUT_ACCUM (default), abi.OUTPUT_DENOISED
+        or abi.OUTPUT_TEMPORAL (also 'accum' / 'denoised' / 'temporal'; the last needs a temporal image)."""
         if isinstance(source, str):
-            names = {"accum": abi.OUTPUT_ACCUM, "denoised": abi.OUTPUT_DENOISED}
+            names = abi.OUTPUT_SOURCES
             if source not in names:
-                raise ValueError("set_output_source: unknown source %r (accum, denoised)" % source)
+                raise ValueError("set_output_source: unknown source %r (accum, denoised, temporal)" % source)
             source = names[source]
         self._chk(self._L.rmr_set_output_source(self._ctx, int(source)))
+
+    # -- temporal reprojection of the preview across camera moves --
+    @staticmethod
+    def _temporal_params(who, params, kw):
+        if params is not None and not isinstance(params, abi.TemporalParams):
+            raise TypeError("%s: params must be an abi.TemporalParams" % who)
+        p = abi.default_temporal_params() if params is None else abi.TemporalParams.from_buffer_copy(params)
+        for k, v in kw.items():
+            if k not in abi.TEMPORAL_FIELDS:
+                raise TypeError("%s: unknown parameter %r" % (who, k))
+            setattr(p, k, v)
+        return p
+
+    def temporal_accumulate(self, source="accum", samples=1.0, params=None, **kw):
+        """rmr_temporal_accumulate: re-project the history into the current view and blend it with the
+        source image ('accum' or 'denoised', or abi.OUTPUT_*) of `samples` samples per pixel; the result,
+        returned as (H, W, 4), is the new history. The loop: set_view, reload, render_spp(k), denoise(),
+        temporal_accumulate('denoised', k). Keywords: max_history (64; >= 1), sigma_z (0.02; > 0),
+        normal_pow2 (5; 0..7)."""
+        if isinstance(source, str):
+            if source not in ("accum", "denoised"):
+                raise ValueError("temporal_accumulate: unknown source %r (accum, denoised)" % source)
+            source = abi.OUTPUT_SOURCES[source]
+        p = self._temporal_params("temporal_accumulate", params, kw)
+        self._chk(self._L.rmr_temporal_accumulate(self._ctx, int(source), C.c_float(samples), C.byref(p)))
+        return self.read_temporal()
+
+    def read_temporal(self):
+        w, h = self.image_size()
+        out = np.zeros((h, w, 4), np.float32)
+        self._chk(self._L.rmr_read_temporal(self._ctx, _fp(out), out.nbytes))
+        return out
+
+    def read_temporal_count(self):
+        """The temporal image's effective sample counts as an (H, W) float32 array (0: not live)."""
+        w, h = self.image_size()
+        out = np.zeros((h, w), np.float32)
+        self._chk(self._L.rmr_read_temporal_count(self._ctx, _fp(out), out.nbytes))
+        return out
+
+    def temporal_device_ptr(self):
+        """Device pointer of the valid temporal image (W x H float4), None without one."""
+        return self._L.rmr_temporal_device_ptr(self._ctx)
+
+    def temporal_reset(self):
+        """rmr_temporal_reset: drop the history."""
+        self._chk(self._L.rmr_temporal_reset(self._ctx))
+
+    def temporal_images(self, S, hit, normal, view, h_rgba, h_n, h_hit, h_normal, h_view, samples=1.0, params=None,
+                        **kw):
+        """rmr_temporal_images (test hook): the stage's kernel on host images, (h, w, 4) each and h_n
+        (h, w). Returns (image (h, w, 4), counts (h, w), projected coordinates (h, w, 2))."""
+        p = self._temporal_params("temporal_images", params, kw)
+        imgs = [np.ascontiguousarray(x, np.float32) for x in (S, hit, normal, h_rgba, h_hit, h_normal)]
+        if imgs[0].ndim != 3 or imgs[0].shape[2] != 4 or any(x.shape != imgs[0].shape for x in imgs):
+            raise ValueError("temporal_images: the six images must be (h, w, 4) of one shape, got %s"
+                             % ", ".join(str(x.shape) for x in imgs))
+        h, w = imgs[0].shape[:2]
+        hn = np.ascontiguousarray(h_n, np.float32)
+        if hn.shape != (h, w):
+            raise ValueError("temporal_images: h_n must be (%d, %d), got %s" % (h, w, hn.shape))
+        v = np.ascontiguousarray(view, np.float32).reshape(15)
+        hv = np.ascontiguousarray(h_view, np.float32).reshape(15)
+        out = np.zeros((h, w, 4), np.float32)
+        n = np.zeros((h, w), np.float32)
+        xy = np.zeros((h, w, 2), np.float32)
+        self._chk(self._L.rmr_temporal_images(self._ctx, _fp(imgs[0]), _fp(imgs[1]), _fp(imgs[2]), _fp(v), _fp(imgs[3]),
+                                               _fp(hn), _fp(imgs[4]), _fp(imgs[5]), _fp(hv), w, h, C.c_float(samples),
+                                               C.byref(p), _fp(out), _fp(n), _fp(xy)))
+        return out, n, xy
 
     # -- variance-guided mode of the preview denoiser --
     @staticmethod
@@ -678,6 +748,23 @@ def check_rays(rays):
     """rmr_check_rays (no GPU): True iff rmr_trace_rays would accept the structured array."""
     r = np.ascontiguousarray(rays, np.dtype(abi.RAY_DTYPE)).reshape(-1)
     return lib().rmr_check_rays(r.ctypes.data, len(r)) == abi.RMR_OK
+
+
+def check_temporal_params(params=None, **fields):
+    """rmr_check_temporal_params (no GPU): True iff every field is in its range."""
+    p = params if isinstance(params, abi.TemporalParams) else abi.default_temporal_params(**fields)
+    return lib().rmr_check_temporal_params(C.byref(p)) == abi.RMR_OK
+
+
+def temporal_view_inverse(view):
+    """rmr_temporal_view_inverse (no GPU): (Minv (3, 3), k (3,)) in float64 of a 15-float history view,
+    the host's part of the temporal stage's projection."""
+    v = np.ascontiguousarray(view, np.float32).reshape(15)
+    out = np.zeros(12, np.float64)
+    rc = lib().rmr_temporal_view_inverse(_fp(v), out.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_temporal_view_inverse: degenerate view")
+    return out[:9].reshape(3, 3), out[9:].copy()
 
 
 def encode_bmp(rgba, path):
