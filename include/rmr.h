@@ -477,6 +477,92 @@ int rmr_temporal_images(rmr_ctx* ctx, const float* s_rgba, const float* hit, con
                         const float h_view[15], int w, int h, float samples, const rmr_temporal_params* p,
                         float* out_rgba, float* out_n, float* out_xy);
 
+/* ---- tone mapping and histogram auto-exposure ---------------------------------------------- */
+/* No counterpart in the reference. Additive: with nothing below called, every other entry point reads
+ * the planes it reads today. The stage scales an HDR image (the accumulator, the denoised or the
+ * temporal image) by an exposure, applies a curve per colour channel and leaves the result, values in
+ * [0, 1], in a W x H RGBA32F plane of its own, which rmr_save_bmp / rmr_display* then sRGB-encode as
+ * they encode any other source. The exposure is given, or metered from the image's luminance histogram
+ * on the GPU (no host round trip). DESIGN.md §4.13.
+ *
+ * The rule (csrc/rmr_tonemap_rule.h, compiled by the kernels and by the host functions below). Every
+ * float operation is float32, each product and sum rounded on its own (no fused multiply-add); `/` is
+ * the correctly rounded division.
+ *
+ * Luminance bin of a pixel (r, g, b, a):
+ *   L = (0.2126f r + 0.7152f g) + 0.0722f b
+ *   the pixel is counted when a != 0, r, g, b and L are finite and L >= 0; otherwise it is skipped.
+ *   bin = clamp(((bits(L) & 0x7fffffff) >> 20) - ((127 - 16) << 3), 0, 255)   (the mask: L = -0 is bin 0)
+ *   i.e. 8 bins per octave: bin b in 1..254 covers [2^e (1 + m/8), 2^e (1 + (m+1)/8)), e = (b >> 3) - 16,
+ *   m = b & 7; bin 0 is everything below 2^-16 1.125 (zero and denormals included) and is never metered;
+ *   bin 255 is everything from 2^15 1.875 up.
+ * Metering (double, each operation rounded on its own), n_b = the counts of bins 1..255, N = their sum:
+ *   lo = (double)low_pct N, hi = (double)high_pct N; C = 0, sw = 0, swl = 0; for b = 1..255 in order:
+ *     w = max(0, min(C + n_b, hi) - max(C, lo)); swl += w lc_b; sw += w; C += n_b
+ *   lc_b = e + log2(1 + (m + 0.5) / 8)                       (a table made on the host)
+ *   l_target = (log2((double)key) - swl / sw) + (double)exposure_ev
+ *   l = l_prev + (double)adapt (l_target - l_prev) with a valid previous state, else l = l_target
+ *   N == 0: l = l_prev with a valid previous state, else (double)exposure_ev
+ *   scale = (float)exp2(l); the state is (l, valid) from then on.
+ * Curve, per colour channel c (alpha passes through):
+ *   x = fmaxf(c scale, 0), a -0 product read as +0; so NaN gives 0
+ *   RMR_TONE_LINEAR:   v = x
+ *   RMR_TONE_REINHARD: v = (x (1 + x iw2)) / (1 + x), iw2 = (float)(1.0 / ((double)white white))
+ *   RMR_TONE_ACES:     v = (x (2.51f x + 0.03f)) / (x (2.43f x + 0.59f) + 0.14f)      (Narkowicz's fit)
+ *   result = fmaxf(fminf(v, 1), 0) with fminf's rule for NaN (the other operand): a channel so bright
+ *   that v is inf / inf (+inf, or x^2 past FLT_MAX) gives 1, as every curve's limit is; v >= 0 otherwise. */
+enum { RMR_TONE_LINEAR = 0, RMR_TONE_REINHARD = 1, RMR_TONE_ACES = 2 };
+#define RMR_OUTPUT_TONEMAPPED 3
+typedef struct rmr_tonemap_params {   /* 32 bytes */
+    int32_t curve;          /* RMR_TONE_*;            default RMR_TONE_ACES */
+    int32_t auto_exposure;  /* 0 / 1;                 default 0    */
+    float exposure_ev;      /* finite, |ev| <= 32;    default 0    */
+    float key;              /* finite > 0;            default 0.18 */
+    float low_pct, high_pct;/* 0 <= low < high <= 1;  default 0.10, 0.90 */
+    float adapt;            /* 0 < adapt <= 1;        default 1    */
+    float white;            /* finite > 0;            default 4    */
+} rmr_tonemap_params;
+void rmr_default_tonemap_params(rmr_tonemap_params* p);
+/* RMR_OK, or RMR_E_INVALID for a field outside the ranges above (NaN included) and for NULL. */
+int rmr_check_tonemap_params(const rmr_tonemap_params* p);
+/* The stage: source RMR_OUTPUT_ACCUM, RMR_OUTPUT_DENOISED or RMR_OUTPUT_TEMPORAL (anything else:
+ * RMR_E_INVALID; a source with no valid image: RMR_E_STATE), p NULL = the defaults. With auto_exposure 0
+ * scale = (float)exp2((double)exposure_ev), computed on the host; the meter does not run and the
+ * adaptation state is left alone. With auto_exposure 1 the histogram, the meter and the curve run one
+ * after the other on the GPU and the state becomes this call's l. The planes are allocated at the first
+ * call (RMR_E_NOMEM, with nothing left allocated, when that fails). Queued on the context's stream
+ * without synchronising, after flushing held rmr_render calls. The source image is not changed.
+ * The tonemapped image is valid from then until any point where a denoised image would become invalid
+ * (a render or rmr_write_accum, rmr_set_view, rmr_set_params, a scene load, rmr_reload, rmr_bind_accum,
+ * rmr_denoise, rmr_denoise_variance), or, when it was made from the temporal image, until the next
+ * rmr_temporal_accumulate. */
+int rmr_tonemap(rmr_ctx* ctx, int source, const rmr_tonemap_params* p);
+/* The tonemapped image as RGBA32F (synchronises) and its device pointer; RMR_E_STATE / NULL without a
+ * valid one, never a stale image. */
+int rmr_read_tonemapped(rmr_ctx* ctx, float* rgba, size_t bytes);
+void* rmr_tonemapped_device_ptr(rmr_ctx* ctx);
+/* What the last rmr_tonemap used: l (auto_exposure 0: (double)exposure_ev) and scale. Either pointer may be
+ * NULL. RMR_E_STATE before the first rmr_tonemap (and after rmr_reload). Synchronises. */
+int rmr_read_exposure(rmr_ctx* ctx, double* log2_scale, float* scale);
+/* The luminance histogram of a source (as rmr_tonemap's), by the stage's own kernels: hist[b] = pixels in
+ * bin b, *skipped (may be NULL) = pixels not counted; their sum is W H. Leaves the adaptation state and
+ * the tonemapped image as they are. Synchronises. */
+int rmr_luminance_histogram(rmr_ctx* ctx, int source, uint32_t hist[256], uint64_t* skipped);
+/* Drop the adaptation state: the next auto-exposed rmr_tonemap uses its own l_target. rmr_set_image_size
+ * and rmr_reload do the same. */
+int rmr_tonemap_reset(rmr_ctx* ctx);
+/* rmr_set_output_source(RMR_OUTPUT_TONEMAPPED): rmr_save_bmp / rmr_display* encode the tonemapped image.
+ * Without a valid one the call returns RMR_E_STATE and leaves the source as it was, and those calls
+ * return RMR_E_STATE when the image has become invalid since. */
+/* Context-free, host only (no GPU needed): the rule above on host arrays.
+ * bins[i] = the bin of pixel i of n RGBA pixels, -1: skipped. */
+int rmr_luminance_bins(const float* rgba, size_t n, int32_t* bins);
+/* *l_out = l of the metering rule for a histogram; l_prev NaN: no previous state (+-inf: RMR_E_INVALID).
+ * p NULL = the defaults; RMR_E_INVALID for params rmr_check_tonemap_params refuses. */
+int rmr_exposure_from_histogram(const uint32_t hist[256], const rmr_tonemap_params* p, double l_prev, double* l_out);
+/* out = the curve p->curve (and p->white) of n RGBA pixels at `scale` (used as it is, whatever it is). */
+int rmr_tonemap_pixels(const rmr_tonemap_params* p, float scale, const float* rgba, size_t n, float* out);
+
 /* ---- camera models and caller-supplied rays ------------------------------------------------ */
 /* No counterpart in the reference, whose only camera is main()'s jittered interpolation of the four
  * corner rays from one point, the eye (RM1:569-584). Additive: with RMR_CAMERA_VIEW (the default) every

@@ -7,9 +7,12 @@ reference's Graphics / Camera / Screen host interfaces.
 from . import abi
 from ._lib import RMRError, lib
 from .renderer import (Camera, Graphics, Renderer, Screen, adaptive_select, camera_frame, camera_view,
-                       check_camera_model, check_rays, check_temporal_params, default_camera_view, encode_bmp, encode_pfm, parity_schedule, save_name, temporal_view_inverse, tile_spiral, time_schedule)
+                       check_camera_model, check_rays, check_temporal_params, check_tonemap_params, default_camera_view,
+                       encode_bmp, encode_pfm, exposure_from_histogram, luminance_bins, parity_schedule, save_name,
+                       temporal_view_inverse, tile_spiral, time_schedule, tonemap_pixels)
 
 __all__ = ["abi", "lib", "RMRError", "Renderer", "Graphics", "Camera", "Screen", "camera_view",
            "default_camera_view", "encode_bmp", "encode_pfm", "tile_spiral", "time_schedule", "parity_schedule",
            "save_name", "adaptive_select", "camera_frame", "check_camera_model", "check_rays",
-           "check_temporal_params", "temporal_view_inverse"]
+           "check_temporal_params", "temporal_view_inverse", "check_tonemap_params", "luminance_bins",
+           "exposure_from_histogram", "tonemap_pixels"]

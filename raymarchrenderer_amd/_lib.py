@@ -39,6 +39,9 @@ EXPORTS = [
     "rmr_variance_device_ptr", "rmr_denoise_variance_images",
     "rmr_default_temporal_params", "rmr_check_temporal_params", "rmr_temporal_view_inverse", "rmr_temporal_accumulate",
     "rmr_temporal_reset", "rmr_read_temporal", "rmr_read_temporal_count", "rmr_temporal_device_ptr", "rmr_temporal_images",
+    "rmr_default_tonemap_params", "rmr_check_tonemap_params", "rmr_tonemap", "rmr_read_tonemapped",
+    "rmr_tonemapped_device_ptr", "rmr_read_exposure", "rmr_luminance_histogram", "rmr_tonemap_reset",
+    "rmr_luminance_bins", "rmr_exposure_from_histogram", "rmr_tonemap_pixels",
 ]
 
 
@@ -187,6 +190,19 @@ def lib(diag=None):
         "rmr_temporal_device_ptr": (vp, [vp]),
         "rmr_temporal_images": (C.c_int, [vp, fp, fp, fp, fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_float,
                                           C.POINTER(abi.TemporalParams), fp, fp, fp]),
+        "rmr_default_tonemap_params": (None, [C.POINTER(abi.TonemapParams)]),
+        "rmr_check_tonemap_params": (C.c_int, [C.POINTER(abi.TonemapParams)]),
+        "rmr_tonemap": (C.c_int, [vp, C.c_int, C.POINTER(abi.TonemapParams)]),
+        "rmr_read_tonemapped": (C.c_int, [vp, fp, C.c_size_t]),
+        "rmr_tonemapped_device_ptr": (vp, [vp]),
+        "rmr_read_exposure": (C.c_int, [vp, dp, fp]),
+        "rmr_luminance_histogram": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+        "rmr_tonemap_reset": (C.c_int, [vp]),
+        "rmr_luminance_bins": (C.c_int, [fp, C.c_size_t, C.POINTER(C.c_int32)]),
+        "rmr_exposure_from_histogram": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(abi.TonemapParams), C.c_double, dp]),
+        "rmr_tonemap_pixels": (C.c_int, [C.POINTER(abi.TonemapParams), C.c_float, fp, C.c_size_t, fp]),
+        "rmr_diag_tonemap_fold": (C.c_int, [vp, C.c_int]),
+        "rmr_diag_tonemap_time": (C.c_int, [vp, C.c_int, C.c_int, fp]),
         # diagnostic library only (rmr_api.cpp RMR_DIAG): ray_exit at given rays; the a-trous passes
         # that run the LDS-tiled form
         "rmr_diag_ray_exit": (C.c_int, [vp, fp, C.c_int, fp, fp, C.c_int, ip]),

@@ -159,6 +159,29 @@ def default_temporal_params(**kw):
     return p
 
 
+class TonemapParams(C.Structure):
+    _fields_ = [("curve", C.c_int32), ("auto_exposure", C.c_int32), ("exposure_ev", C.c_float), ("key", C.c_float),
+                ("low_pct", C.c_float), ("high_pct", C.c_float), ("adapt", C.c_float), ("white", C.c_float)]
+
+
+TONEMAP_FIELDS = ("curve", "auto_exposure", "exposure_ev", "key", "low_pct", "high_pct", "adapt", "white")
+# the curves of the tone-mapping stage (rmr.h)
+TONE_LINEAR = 0
+TONE_REINHARD = 1
+TONE_ACES = 2
+TONE_CURVES = {"linear": TONE_LINEAR, "reinhard": TONE_REINHARD, "aces": TONE_ACES}
+
+
+def default_tonemap_params(**kw):
+    """rmr_default_tonemap_params' values (rmr.h), with overrides."""
+    p = TonemapParams(TONE_ACES, 0, 0.0, 0.18, 0.10, 0.90, 1.0, 4.0)
+    for k, v in kw.items():
+        if k not in TONEMAP_FIELDS:
+            raise TypeError("unknown tonemap parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("threshold", C.c_float), ("offset", C.c_float), ("min_samples", C.c_uint32),
                 ("pass_samples", C.c_uint32), ("max_samples", C.c_uint32), ("block_tiles", C.c_int32)]
@@ -235,7 +258,9 @@ GUIDE_PLANES = {"ray": GUIDE_RAY, "hit": GUIDE_HIT, "normal": GUIDE_NORMAL}
 OUTPUT_ACCUM = 0
 OUTPUT_DENOISED = 1
 OUTPUT_TEMPORAL = 2
-OUTPUT_SOURCES = {"accum": OUTPUT_ACCUM, "denoised": OUTPUT_DENOISED, "temporal": OUTPUT_TEMPORAL}
+OUTPUT_TONEMAPPED = 3
+OUTPUT_SOURCES = {"accum": OUTPUT_ACCUM, "denoised": OUTPUT_DENOISED, "temporal": OUTPUT_TEMPORAL,
+                  "tonemapped": OUTPUT_TONEMAPPED}
 # variance planes of the variance-guided denoiser (rmr.h)
 VARIANCE_SEED = 0
 VARIANCE_FILTERED = 1

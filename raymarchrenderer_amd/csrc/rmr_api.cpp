@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,6 +30,7 @@
 #include "rmr_jit.hpp"
 #include "scene.hpp"
 #include "temporal.hpp"
+#include "tonemap.hpp"
 
 namespace rmr {
 hipError_t launch_trace(const KParams& P, int variant, int np, bool prog, bool persistent, int grid, hipStream_t s);
@@ -145,6 +147,21 @@ struct rmr_ctx {
     int t_cur = -1;                       // the pair that holds the history (= the temporal image), -1: none
     float t_view[15];                     // the view the history was made with
     bool t_keep = false;                  // diagnostic library (tools/temporal_time.py): a step leaves the history as it is
+    // tone mapping and auto-exposure (rmr_tonemap): the tonemapped plane (W x H float4),
+    // k_lum_hist's [kToneSlabRows][257] slab, the state and the meter's table of bin centres; allocated
+    // at the first call, freed at rmr_reload / rmr_destroy
+    float4* d_tm = nullptr;
+    uint32_t* d_tm_slab = nullptr;
+    rmr::ToneState* d_tm_state = nullptr;
+    double* d_tm_lc = nullptr;
+    double tm_lc[255];                    // the table's host copy (the source of its queued upload)
+    bool tm_valid = false;                // d_tm holds the image of tm_source as it is now
+    int tm_source = RMR_OUTPUT_ACCUM;
+    int tm_used = 0;                      // what the last rmr_tonemap used: 0 none, 1 tm_ev / tm_scale, 2 the state
+    double tm_ev = 0.0;
+    float tm_scale = 1.0f;
+    bool tm_fold = false;                 // diagnostic library (tools/tonemap_time.py): k_lum_hist folds equal bins
+                                          // inside the wave (measured and not kept: DESIGN.md §4.13, Appendix A)
     // per-tile error estimate and adaptive sampling (rmr_estimate.hip, adaptive.hpp)
     bool est_on = false;                  // every launch's fold is k_fold_half (rmr_set_error_estimate)
     bool est_valid = false;               // d_half holds the odd samples of everything in the accumulator
@@ -320,7 +337,7 @@ void free_guides(rmr_ctx* c) {
     for (float4*& b : c->d_dn) { if (b) (void)hipFree(b); b = nullptr; }
     for (float*& b : c->d_var) { if (b) (void)hipFree(b); b = nullptr; }
     c->guides_valid = false;
-    c->dn_result = -1;
+    c->dn_result = -1; c->tm_valid = false;
 }
 
 // Release the temporal stage's planes (the caller has synced the context's stream).
@@ -329,6 +346,21 @@ void free_temporal(rmr_ctx* c) {
     for (float*& b : c->d_tn) { if (b) (void)hipFree(b); b = nullptr; }
     for (float4*& b : c->d_tguide) { if (b) (void)hipFree(b); b = nullptr; }
     c->t_cur = -1;
+}
+
+// Release the tone-mapping stage's buffers, the adaptation state with them (the caller has synced the
+// context's stream).
+void free_tonemap(rmr_ctx* c) {
+    if (c->d_tm) (void)hipFree(c->d_tm);
+    if (c->d_tm_slab) (void)hipFree(c->d_tm_slab);
+    if (c->d_tm_state) (void)hipFree(c->d_tm_state);
+    if (c->d_tm_lc) (void)hipFree(c->d_tm_lc);
+    c->d_tm = nullptr;
+    c->d_tm_slab = nullptr;
+    c->d_tm_state = nullptr;
+    c->d_tm_lc = nullptr;
+    c->tm_valid = false;
+    c->tm_used = 0;
 }
 
 // Release the half image and the tile-error map (the caller has synced the context's stream).
@@ -454,7 +486,7 @@ int upload_scene(rmr_ctx* c) {
     c->scene_kp = scene_params(c);
     c->guides_valid = false;   // (every scene load comes through here)
     c->t_cur = -1;             // the temporal history is of the old scene
-    c->dn_result = -1;
+    c->dn_result = -1; c->tm_valid = false;
     c->scene_loaded = true;
     c->jit_ready = false;
     c->jit_rays_ready = false;
@@ -950,7 +982,7 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
     }
     const TileXY* d_tiles = nullptr;
     if (!rl) {
-        c->dn_result = -1;   // the accumulator changes: the denoised image is of the old one
+        c->dn_result = -1; c->tm_valid = false;   // the accumulator changes: the denoised image is of the old one
         c->rendered = true;
         if ((r = tile_list(c, tiles, &d_tiles))) return r;
     }
@@ -1062,6 +1094,10 @@ int output_image(rmr_ctx* c, const char* who, const float4** out) {
         if (c->t_cur < 0)
             return fail(c, RMR_E_STATE, std::string(who) + ": output source is the temporal image, but none is valid (call rmr_temporal_accumulate)");
         *out = c->d_tcol[c->t_cur];
+    } else if (c->output_source == RMR_OUTPUT_TONEMAPPED) {
+        if (!c->tm_valid)
+            return fail(c, RMR_E_STATE, std::string(who) + ": output source is the tonemapped image, but none is valid (call rmr_tonemap)");
+        *out = c->d_tm;
     } else {
         *out = c->d_accum;
     }
@@ -1185,6 +1221,7 @@ void rmr_destroy(rmr_ctx* c) {
     if (c->h_times) (void)hipHostFree(c->h_times);
     free_guides(c);
     free_temporal(c);
+    free_tonemap(c);
     if (c->d_half) (void)hipFree(c->d_half);
     if (c->d_tile_err) (void)hipFree(c->d_tile_err);
     if (c->d_accum && !c->accum_external) (void)hipFree(c->d_accum);
@@ -1221,6 +1258,9 @@ int rmr_set_image_size(rmr_ctx* c, int w, int h) {
     if (w <= 0 || h <= 0 || w > 32768 || h > 32768) return fail(c, RMR_E_INVALID, "bad image size");
     c->pend_W = w;
     c->pend_H = h;
+    // (the auto-exposure's adaptation state is of the old size's images)
+    if (c->d_tm_state) HIPCHK(c, hipSetDevice(c->device));
+    if (c->d_tm_state) HIPCHK(c, hipMemsetAsync(&c->d_tm_state->valid, 0, sizeof(uint32_t), c->stream));
     return RMR_OK;
 }
 
@@ -1237,7 +1277,7 @@ int rmr_set_params(rmr_ctx* c, const rmr_params* p) {
     if (p->max_steps < 0 || p->max_bounces < 0 || !(p->max_dist > 0.0f)) return fail(c, RMR_E_INVALID, "bad params");
     c->params = *p;
     c->guides_valid = false;
-    c->dn_result = -1;
+    c->dn_result = -1; c->tm_valid = false;
     return RMR_OK;
 }
 
@@ -1257,7 +1297,7 @@ int rmr_set_view(rmr_ctx* c, const float eye[3], const float r00[3], const float
     }
     c->view_set = true;
     c->guides_valid = false;
-    c->dn_result = -1;
+    c->dn_result = -1; c->tm_valid = false;
     return RMR_OK;
 }
 
@@ -1314,6 +1354,7 @@ int rmr_reload(rmr_ctx* c) {
     const bool resize = (c->pend_W != c->W || c->pend_H != c->H);
     free_guides(c);   // (the stream is idle)
     free_temporal(c);
+    free_tonemap(c);
     c->W = c->pend_W;
     c->H = c->pend_H;
     if (resize) {
@@ -1342,7 +1383,7 @@ int rmr_render(rmr_ctx* c, float time, float min_x, float min_y, float max_x, fl
     }
     // deferred (rmr_set_call_batching): the errors the launch would give now come at the call
     if (const int r = launch_precheck(c)) return r;
-    c->dn_result = -1;
+    c->dn_result = -1; c->tm_valid = false;
     c->rendered = true;
     rmr::DeferredCall* same = nullptr;
     bool overlap = false;
@@ -1423,7 +1464,7 @@ int rmr_write_accum(rmr_ctx* c, const float* rgba, size_t bytes) {
     RMR_FLUSH(c);
     const size_t need = (size_t)c->W * c->H * sizeof(float4);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
-    c->dn_result = -1;
+    c->dn_result = -1; c->tm_valid = false;
     c->rendered = true;    // (the accumulator has contents the half image knows nothing of)
     c->est_valid = false;
     HIPCHK(c, hipMemcpyAsync(c->d_accum, rgba, need, hipMemcpyHostToDevice, c->stream));
@@ -1448,7 +1489,7 @@ int rmr_bind_accum(rmr_ctx* c, void* ptr, size_t bytes) {
     // (an external buffer is only swapped: launches already queued keep the pointer they captured)
     c->d_accum = (float4*)ptr;
     c->accum_external = true;
-    c->dn_result = -1;
+    c->dn_result = -1; c->tm_valid = false;
     c->est_valid = false;
     return RMR_OK;
 }
@@ -2130,7 +2171,7 @@ int rmr_denoise(rmr_ctx* c, const rmr_denoise_params* p) {
     if (!denoise_params_ok(q))
         return fail(c, RMR_E_INVALID, "bad denoise params (iterations 0..8, normal_pow2 0..7, sigma_z finite > 0, sigma_c finite >= 0)");
     int r;
-    c->dn_result = -1;
+    c->dn_result = -1; c->tm_valid = false;
     c->dn_guided = false;
     if (!c->guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
     HIPCHK(c, hipSetDevice(c->device));
@@ -2180,10 +2221,14 @@ void* rmr_denoised_device_ptr(rmr_ctx* c) {
 int rmr_set_output_source(rmr_ctx* c, int source) {
     if (!c) return RMR_E_INVALID;
     RMR_FLUSH(c);
-    if (source != RMR_OUTPUT_ACCUM && source != RMR_OUTPUT_DENOISED && source != RMR_OUTPUT_TEMPORAL) return fail(c, RMR_E_INVALID, "bad output source");
+    if (source != RMR_OUTPUT_ACCUM && source != RMR_OUTPUT_DENOISED && source != RMR_OUTPUT_TEMPORAL &&
+        source != RMR_OUTPUT_TONEMAPPED)
+        return fail(c, RMR_E_INVALID, "bad output source");
     // (refused, the source unchanged, while there is no temporal image to read)
     if (source == RMR_OUTPUT_TEMPORAL && c->t_cur < 0)
         return fail(c, RMR_E_STATE, "no valid temporal image (call rmr_temporal_accumulate)");
+    if (source == RMR_OUTPUT_TONEMAPPED && !c->tm_valid)
+        return fail(c, RMR_E_STATE, "no valid tonemapped image (call rmr_tonemap)");
     c->output_source = source;
     return RMR_OK;
 }
@@ -2403,7 +2448,7 @@ int rmr_denoise_variance(rmr_ctx* c, const rmr_denoise_params* p, const rmr_vari
     if (!c->est_on || !c->est_valid || !c->d_half)
         return fail(c, RMR_E_STATE, "the error estimate is not valid: call rmr_set_error_estimate before the first "
                                     "render since rmr_reload, or render with rmr_render_adaptive");
-    c->dn_result = -1;
+    c->dn_result = -1; c->tm_valid = false;
     c->dn_guided = false;
     if (!c->guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
     HIPCHK(c, hipSetDevice(c->device));
@@ -2558,6 +2603,7 @@ int rmr_temporal_accumulate(rmr_ctx* c, int source, float samples, const rmr_tem
     }
     const int from = c->t_cur, to = 1 - from;
     c->t_cur = -1;   // (until everything below is queued)
+    if (c->tm_source == RMR_OUTPUT_TEMPORAL) c->tm_valid = false;   // (a tonemapped image of the old temporal image)
     T.d.in = source == RMR_OUTPUT_DENOISED ? c->d_dn[c->dn_result] : c->d_accum;
     T.d.hit = c->d_guide[RMR_GUIDE_HIT];
     T.d.nrm = c->d_guide[RMR_GUIDE_NORMAL];
@@ -2664,7 +2710,219 @@ int rmr_temporal_images(rmr_ctx* c, const float* s_rgba, const float* hit, const
     return RMR_OK;
 }
 
+// ---- tone mapping and histogram auto-exposure (rmr_tonemap.hip, tonemap.cpp) -----------------------
+static_assert(sizeof(rmr_tonemap_params) == 32, "rmr_tonemap_params is 32 bytes (include/rmr.h)");
+namespace {
+// The image a stage source names, with the existing readers' messages.
+int tone_source(rmr_ctx* c, int source, const float4** src) {
+    if (source == RMR_OUTPUT_ACCUM) {
+        *src = c->d_accum;
+    } else if (source == RMR_OUTPUT_DENOISED) {
+        if (c->dn_result < 0) return fail(c, RMR_E_STATE, "no valid denoised image (call rmr_denoise)");
+        *src = c->d_dn[c->dn_result];
+    } else if (source == RMR_OUTPUT_TEMPORAL) {
+        if (c->t_cur < 0) return fail(c, RMR_E_STATE, "no valid temporal image (call rmr_temporal_accumulate)");
+        *src = c->d_tcol[c->t_cur];
+    } else {
+        return fail(c, RMR_E_INVALID, "bad source (RMR_OUTPUT_ACCUM, RMR_OUTPUT_DENOISED or RMR_OUTPUT_TEMPORAL)");
+    }
+    return RMR_OK;
+}
+
+// The stage's buffers, at first use: all four or none.
+int ensure_tonemap(rmr_ctx* c) {
+    if (c->d_tm) return RMR_OK;
+    const size_t sizes[4] = {(size_t)c->W * c->H * sizeof(float4), (size_t)rmr::kToneSlabRows * rmr::kToneWords * sizeof(uint32_t),
+                             sizeof(rmr::ToneState), 255 * sizeof(double)};
+    void* b[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int i = 0; i < 4; i++)
+        if (hipMalloc(&b[i], sizes[i]) != hipSuccess) {
+            (void)hipGetLastError();
+            for (int k = 0; k < i; k++) (void)hipFree(b[k]);
+            return fail(c, RMR_E_NOMEM, "cannot allocate the tonemapped plane (16 bytes per pixel) and the histogram slab");
+        }
+    // the table and the zeroed state go through the context's stream, ahead of the kernels that read them
+    // (the host copy of the table lives in the context, so the queued copy's source outlives this call)
+    rmr::tonemap_lc_table(c->tm_lc);
+    hipError_t e = hipMemcpyAsync(b[3], c->tm_lc, sizeof c->tm_lc, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(b[2], 0, sizeof(rmr::ToneState), c->stream);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        for (void* p : b) (void)hipFree(p);
+        HIPCHK(c, e);
+    }
+    c->d_tm = (float4*)b[0];
+    c->d_tm_slab = (uint32_t*)b[1];
+    c->d_tm_state = (rmr::ToneState*)b[2];
+    c->d_tm_lc = (double*)b[3];
+    c->tm_valid = false;
+    c->tm_used = 0;
+    return RMR_OK;
+}
+
+// k_lum_hist and k_meter over src on the context's stream.
+int tone_meter(rmr_ctx* c, const float4* src, const rmr_tonemap_params& q, bool run_meter) {
+    const size_t px = (size_t)c->W * c->H;
+    const int blocks = rmr::lum_hist_blocks(px);
+    HIPCHK(c, rmr::launch_lum_hist(src, px, c->d_tm_slab, blocks, c->tm_fold, c->stream));
+    HIPCHK(c, rmr::launch_meter(c->d_tm_slab, blocks, c->d_tm_state, c->d_tm_lc, rmr::tonemap_meter(q), run_meter, c->stream));
+    return RMR_OK;
+}
+}  // namespace
+
+int rmr_tonemap(rmr_ctx* c, int source, const rmr_tonemap_params* p) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_tonemap_params q;
+    rmr_default_tonemap_params(&q);
+    if (p) q = *p;
+    if (!rmr::tonemap_params_ok(q))
+        return fail(c, RMR_E_INVALID, "bad tonemap params (curve 0..2, auto_exposure 0 / 1, |exposure_ev| <= 32, key > 0, "
+                                      "0 <= low_pct < high_pct <= 1, 0 < adapt <= 1, white > 0)");
+    const float4* src = nullptr;
+    int r;
+    if ((r = tone_source(c, source, &src))) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((r = ensure_tonemap(c))) return r;
+    c->tm_valid = false;   // (until everything below is queued)
+    const size_t px = (size_t)c->W * c->H;
+    const float iw2 = rmr::tonemap_iw2(q);
+    if (q.auto_exposure) {
+        if ((r = tone_meter(c, src, q, true))) return r;
+        HIPCHK(c, rmr::launch_tonemap(src, c->d_tm, px, c->d_tm_state, 0.0f, q.curve, iw2, c->stream));
+        c->tm_used = 2;
+    } else {
+        c->tm_ev = (double)q.exposure_ev;
+        c->tm_scale = (float)std::exp2(c->tm_ev);
+        HIPCHK(c, rmr::launch_tonemap(src, c->d_tm, px, nullptr, c->tm_scale, q.curve, iw2, c->stream));
+        c->tm_used = 1;
+    }
+    c->tm_source = source;
+    c->tm_valid = true;
+    return RMR_OK;
+}
+
+int rmr_read_tonemapped(rmr_ctx* c, float* rgba, size_t bytes) {
+    if (!c || !rgba) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    const size_t need = (size_t)c->W * c->H * sizeof(float4);
+    if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
+    if (!c->tm_valid) return fail(c, RMR_E_STATE, "no valid tonemapped image (call rmr_tonemap)");
+    HIPCHK(c, hipMemcpyAsync(rgba, c->d_tm, need, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+void* rmr_tonemapped_device_ptr(rmr_ctx* c) {
+    if (!c) return nullptr;
+    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
+    return c->tm_valid ? (void*)c->d_tm : nullptr;
+}
+
+int rmr_read_exposure(rmr_ctx* c, double* log2_scale, float* scale) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (c->tm_used == 0) return fail(c, RMR_E_STATE, "no exposure yet (call rmr_tonemap)");
+    double l = c->tm_ev;
+    float s = c->tm_scale;
+    if (c->tm_used == 2) {
+        // (rmr_tonemap_reset clears the state's valid word only: l and scale stay what the last call used)
+        struct { double l; float scale; uint32_t valid; } head;
+        static_assert(offsetof(rmr::ToneState, scale) == 8 && offsetof(rmr::ToneState, valid) == 12, "ToneState's head");
+        HIPCHK(c, hipMemcpyAsync(&head, c->d_tm_state, sizeof head, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        l = head.l;
+        s = head.scale;
+    }
+    if (log2_scale) *log2_scale = l;
+    if (scale) *scale = s;
+    return RMR_OK;
+}
+
+int rmr_luminance_histogram(rmr_ctx* c, int source, uint32_t hist[256], uint64_t* skipped) {
+    if (!c || !hist) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    const float4* src = nullptr;
+    int r;
+    if ((r = tone_source(c, source, &src))) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((r = ensure_tonemap(c))) return r;
+    rmr_tonemap_params q;
+    rmr_default_tonemap_params(&q);
+    if ((r = tone_meter(c, src, q, false))) return r;
+    unsigned long long sk = 0;
+    HIPCHK(c, hipMemcpyAsync(hist, c->d_tm_state->hist, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&sk, &c->d_tm_state->skipped, sizeof sk, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (skipped) *skipped = (uint64_t)sk;
+    return RMR_OK;
+}
+
+int rmr_tonemap_reset(rmr_ctx* c) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!c->d_tm_state) return RMR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemsetAsync(&c->d_tm_state->valid, 0, sizeof(uint32_t), c->stream));
+    return RMR_OK;
+}
+
 #if RMR_DIAG
+// Diagnostic library only (not in include/rmr.h; tools/tonemap_time.py): whether k_lum_hist folds equal
+// bins inside the wave before the LDS add; the counts are the same either way.
+int rmr_diag_tonemap_fold(rmr_ctx* c, int on) {
+    if (!c) return RMR_E_INVALID;
+    c->tm_fold = on != 0;
+    return RMR_OK;
+}
+
+// Diagnostic library only (not in include/rmr.h; tools/tonemap_time.py): *ms = the GPU's time per launch of
+// n back-to-back launches of one thing on the accumulator: 0 k_lum_hist, 1 k_meter (over the slab the last
+// k_lum_hist left), 2 k_tonemap with the state's scale, 3 a device-to-device copy of the accumulator into
+// the tonemapped plane (the yardstick), 4 the three kernels as an auto-exposed rmr_tonemap queues them.
+// So that the time is the GPU's and not the host's enqueue rate, the stream is first kept busy (32 k_meter
+// launches, about 0.9 ms) while the host queues the first event, the n launches and the second event
+// behind it; n <= 64 keeps the host ahead. Synchronises. The tonemapped image is invalid afterwards.
+int rmr_diag_tonemap_time(rmr_ctx* c, int which, int n, float* ms) {
+    if (!c || !ms || which < 0 || which > 4 || n < 1 || n > 64) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r;
+    if ((r = ensure_tonemap(c))) return r;
+    c->tm_valid = false;
+    const size_t px = (size_t)c->W * c->H;
+    const int blocks = rmr::lum_hist_blocks(px);
+    rmr_tonemap_params q;
+    rmr_default_tonemap_params(&q);
+    const rmr::ToneMeter M = rmr::tonemap_meter(q);
+    const float iw2 = rmr::tonemap_iw2(q);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    HIPCHK(c, hipEventCreate(&ev[0]));
+    hipError_t e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = rmr::launch_lum_hist(c->d_accum, px, c->d_tm_slab, blocks, c->tm_fold, c->stream);
+    for (int i = 0; i < 32 && e == hipSuccess; i++)
+        e = rmr::launch_meter(c->d_tm_slab, blocks, c->d_tm_state, c->d_tm_lc, M, true, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
+    for (int i = 0; i < n && e == hipSuccess; i++) {
+        if (which == 0 || which == 4) e = rmr::launch_lum_hist(c->d_accum, px, c->d_tm_slab, blocks, c->tm_fold, c->stream);
+        if ((which == 1 || which == 4) && e == hipSuccess)
+            e = rmr::launch_meter(c->d_tm_slab, blocks, c->d_tm_state, c->d_tm_lc, M, true, c->stream);
+        if ((which == 2 || which == 4) && e == hipSuccess)
+            e = rmr::launch_tonemap(c->d_accum, c->d_tm, px, c->d_tm_state, 0.0f, q.curve, iw2, c->stream);
+        if (which == 3) e = hipMemcpyAsync(c->d_tm, c->d_accum, px * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    float t = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&t, ev[0], ev[1]);
+    (void)hipEventDestroy(ev[0]);
+    if (ev[1]) (void)hipEventDestroy(ev[1]);
+    HIPCHK(c, e);
+    *ms = t / (float)n;
+    return RMR_OK;
+}
+
 // Diagnostic library only (not in include/rmr.h; tools/denoise_time.py): which a-trous passes run the
 // LDS-tiled form, bit i = the pass of step 2^i (i < 2); the results are the same either way.
 int rmr_diag_denoise_tiled(rmr_ctx* c, int mask) {

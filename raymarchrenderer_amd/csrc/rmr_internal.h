@@ -190,7 +190,26 @@ struct TemporalPass {
     float n_cur;                // the source's sample count
     float max_history;
 };
+// Tone mapping and auto-exposure (rmr_tonemap.hip): what k_meter leaves in device
+// memory, the adaptation state (l, scale, valid) and the summed histogram of the last metered plane.
+struct ToneState {
+    double l;                   // log2 of the scale
+    float scale;                // (float)exp2(l): k_tonemap reads this word
+    uint32_t valid;             // 0: no previous state
+    uint32_t hist[256];
+    unsigned long long skipped;
+};
+constexpr int kToneSlabRows = 512;   // most blocks k_lum_hist runs: rows of the [rows][257] slab
+struct ToneMeter;                    // rmr_tonemap_rule.h
 #ifndef __HIPCC_RTC__
+int lum_hist_blocks(size_t n);
+// fold: equal bins are folded inside the wave before the LDS add (the same counts either way)
+hipError_t launch_lum_hist(const float4* in, size_t n, uint32_t* slab, int blocks, bool fold, hipStream_t s);
+hipError_t launch_meter(const uint32_t* slab, int rows, ToneState* st, const double* lc, const ToneMeter& M, bool run_meter,
+                        hipStream_t s);
+// st: the state whose scale is applied, or null for `scale` itself
+hipError_t launch_tonemap(const float4* in, float4* out, size_t n, const ToneState* st, float scale, int curve, float iw2,
+                          hipStream_t s);
 hipError_t launch_temporal(const TemporalPass& T, hipStream_t s);
 hipError_t launch_variance_seed(const VarianceSeed& V, hipStream_t s);
 // tiled: the LDS form (step 1 or 2 only; other steps run the plain form)

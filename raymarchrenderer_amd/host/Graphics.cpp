@@ -207,6 +207,22 @@ void Graphics::setOutputSource(int source) {
     if (!need_ctx("setOutputSource") || !no_group("setOutputSource")) return;
     check(rmr_set_output_source(g_ctx, source), "setOutputSource");
 }
+void Graphics::Tonemap(int source, const rmr_tonemap_params& p) {
+    if (!need_ctx("Tonemap") || !no_group("Tonemap")) return;
+    check(rmr_tonemap(g_ctx, source, &p), "Tonemap");
+}
+bool Graphics::readExposure(double* log2_scale, float* scale) {
+    if (!need_ctx("readExposure") || !no_group("readExposure")) return false;
+    return check(rmr_read_exposure(g_ctx, log2_scale, scale), "readExposure");
+}
+bool Graphics::LuminanceHistogram(int source, uint32_t hist[256], uint64_t* skipped) {
+    if (!need_ctx("LuminanceHistogram") || !no_group("LuminanceHistogram")) return false;
+    return check(rmr_luminance_histogram(g_ctx, source, hist, skipped), "LuminanceHistogram");
+}
+void Graphics::TonemapReset() {
+    if (!need_ctx("TonemapReset") || !no_group("TonemapReset")) return;
+    check(rmr_tonemap_reset(g_ctx), "TonemapReset");
+}
 bool Graphics::RenderAdaptive(const float* times, const rmr_adaptive_params& p, rmr_adaptive_result* result) {
     if (!need_ctx("RenderAdaptive") || !no_group("RenderAdaptive")) return false;
     rmr_adaptive_result res{};

@@ -73,6 +73,14 @@ public:
     static void setErrorEstimate(bool on);
     static void DenoiseVariance(int iterations = 5, float sigma_l = 4.0f);
     static void setOutputSource(int source);
+    // Tone mapping and auto-exposure (rmr_tonemap): the source image (RMR_OUTPUT_ACCUM / _DENOISED /
+    // _TEMPORAL) through p's exposure and curve into the tonemapped image, which
+    // setOutputSource(RMR_OUTPUT_TONEMAPPED) then shows and saves. Single-context mode only, like Denoise.
+    static void Tonemap(int source, const rmr_tonemap_params& p);
+    // What the last Tonemap used (rmr_read_exposure); false (status in lastStatus) on failure.
+    static bool readExposure(double* log2_scale, float* scale);
+    static bool LuminanceHistogram(int source, uint32_t hist[256], uint64_t* skipped);
+    static void TonemapReset();
     // Adaptive sampling (rmr_render_adaptive): after a Reload, render until every decision block's tile
     // error is at most p.threshold, at most p.max_samples samples per pixel (times[n] seeds sample n).
     // Single-context mode only, like Denoise. Returns false (status in lastStatus) on failure.

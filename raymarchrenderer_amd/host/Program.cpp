@@ -58,6 +58,8 @@ struct Options {
     bool print_tiles = false, print_view = false;  // host-only diagnostics (no GPU needed)
     rmr_params params;
     int denoise = -1;               // --denoise [N]: a-trous iterations, -1 = no denoise
+    bool tonemap = false;           // --tonemap / --exposure: the tone-mapping stage runs last, with `tone`
+    rmr_tonemap_params tone{};
     double variance_guided = -1.0;  // --variance-guided [SIGMA_L]: the guided filter's sigma_l, < 0 = the plain filter
     std::string aov;                // --aov PREFIX: guide planes as PREFIX_*.pfm
     double adaptive = -1.0;         // --adaptive T: the tile-error threshold, < 0 = uniform sampling
@@ -436,6 +438,11 @@ void usage() {
         "  --variance-guided [SIGMA_L]  with --denoise: the variance-guided filter (luminance weight of\n"
         "                      SIGMA_L standard deviations, default 4; safe at any sample count); keeps the\n"
         "                      error estimate on from the first sample; --aov adds PREFIX_variance.pfm\n"
+        "  --tonemap linear|reinhard[:WHITE]|aces   after the render (and --denoise): tone-map the image with\n"
+        "                      that curve (reinhard's white point, default 4) and write --out from the result\n"
+        "  --exposure EV|auto[:KEY]   the stage's exposure: EV stops (scale 2^EV, |EV| <= 32), or metered from\n"
+        "                      the luminance histogram so that the image's log-average goes to KEY (default\n"
+        "                      0.18); alone it implies --tonemap aces; not with --gpus / --devices\n"
         "  --aov PREFIX        first-hit planes as float PFM: PREFIX_normal.pfm, PREFIX_position.pfm,\n"
         "                      PREFIX_ray.pfm, PREFIX_depth_id.pfm (R = t, G = material id or -1, B = 0)\n"
         "  --adaptive T        adaptive sampling: render until every block's tile error is <= T, at most\n"
@@ -472,8 +479,23 @@ bool camera_model_arg(const std::string& v, rmr_camera_model& m) {
     return false;
 }
 
+// "NAME" or "NAME:NUMBER" (the whole of v): false for anything else. has_num: the number was given.
+bool name_and_number(const std::string& v, const char* name, float& num, bool& has_num) {
+    const size_t n = std::strlen(name);
+    has_num = false;
+    if (v.compare(0, n, name) != 0) return false;
+    if (v.size() == n) return true;
+    if (v[n] != ':') return false;
+    char* end = nullptr;
+    const char* t = v.c_str() + n + 1;
+    num = std::strtof(t, &end);
+    has_num = true;
+    return end != t && *end == '\0';
+}
+
 bool parse(int argc, char** argv, Options& o) {
     rmr_default_params(&o.params);
+    rmr_default_tonemap_params(&o.tone);
     rmr_default_camera_model(&o.model);
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -526,6 +548,31 @@ bool parse(int argc, char** argv, Options& o) {
                     !std::isfinite((float)o.variance_guided) || !((float)o.variance_guided > 0.0f))
                     return false;
             }
+        } else if (a == "--tonemap") {
+            const std::string v = next("--tonemap");
+            float white = 0.0f;
+            bool has = false;
+            if (v == "linear") o.tone.curve = RMR_TONE_LINEAR;
+            else if (v == "aces") o.tone.curve = RMR_TONE_ACES;
+            else if (name_and_number(v, "reinhard", white, has)) {
+                o.tone.curve = RMR_TONE_REINHARD;
+                if (has) o.tone.white = white;
+            } else return false;
+            o.tonemap = true;
+        } else if (a == "--exposure") {
+            const std::string v = next("--exposure");
+            float key = 0.0f;
+            bool has = false;
+            if (name_and_number(v, "auto", key, has)) {
+                o.tone.auto_exposure = 1;
+                if (has) o.tone.key = key;
+            } else {
+                char* end = nullptr;
+                o.tone.auto_exposure = 0;
+                o.tone.exposure_ev = std::strtof(v.c_str(), &end);
+                if (end == v.c_str() || *end != '\0') return false;
+            }
+            o.tonemap = true;
         } else if (a == "--aov") {
             o.aov = next("--aov");
             if (o.aov.empty()) return false;
@@ -577,6 +624,10 @@ bool parse(int argc, char** argv, Options& o) {
         std::fprintf(stderr, "--camera: thinlens needs APERTURE >= 0 and FOCUS > 0, ortho WIDTH > 0 and HEIGHT > 0\n");
         return false;
     }
+    if (rmr_check_tonemap_params(&o.tone) != RMR_OK) {
+        std::fprintf(stderr, "--tonemap / --exposure: reinhard needs WHITE > 0, auto KEY > 0, and |EV| <= 32\n");
+        return false;
+    }
     if (o.adaptive >= 0 && (o.min_samples < 2 || o.pass_samples < 1 || o.samples < o.min_samples)) {
         std::fprintf(stderr, "--adaptive: --min-samples >= 2, --pass-samples >= 1 and --samples >= --min-samples\n");
         return false;
@@ -610,6 +661,10 @@ int main(int argc, char** argv) {
     }
     if (o.variance_guided > 0 && (o.denoise < 0 || !o.devices.empty() || !o.resume.empty() || o.per_sample)) {
         std::fprintf(stderr, "--variance-guided: needs --denoise; not with --gpus / --devices, --resume or --per-sample\n");
+        return 2;
+    }
+    if (o.tonemap && (!o.devices.empty() || o.interactive)) {
+        std::fprintf(stderr, "--tonemap / --exposure: not with --gpus / --devices or --interactive\n");
         return 2;
     }
     if (o.model.model != RMR_CAMERA_VIEW && !o.devices.empty()) {
@@ -658,6 +713,17 @@ int main(int argc, char** argv) {
         else Graphics::Denoise(o.denoise);
         if (Graphics::lastStatus() != RMR_OK) return 1;
         Graphics::setOutputSource(RMR_OUTPUT_DENOISED);
+    }
+    if (o.tonemap) {   // last: the image --out would have been written from, through the exposure and the curve
+        Graphics::Tonemap(o.denoise >= 0 ? RMR_OUTPUT_DENOISED : RMR_OUTPUT_ACCUM, o.tone);
+        if (Graphics::lastStatus() != RMR_OK) return 1;
+        Graphics::setOutputSource(RMR_OUTPUT_TONEMAPPED);
+        if (Graphics::lastStatus() != RMR_OK) return 1;
+        if (o.tone.auto_exposure && !o.quiet) {
+            double l = 0.0;
+            float scale = 0.0f;
+            if (Graphics::readExposure(&l, &scale)) std::printf("exposure: %+.3f stops (scale %.6g)\n", l, scale);
+        }
     }
     save(o);
     int rc = Graphics::lastStatus() == RMR_OK ? 0 : 1;

@@ -484,11 +484,12 @@ class Renderer:
 
     def set_output_source(self, source):
         """What save_bmp / display / display_device read: abi.OUTPUT_ACCUM (default), abi.OUTPUT_DENOISED
-        or abi.OUTPUT_TEMPORAL (also 'accum' / 'denoised' / 'temporal'; the last needs a temporal image)."""
+        abi.OUTPUT_TEMPORAL or abi.OUTPUT_TONEMAPPED (also 'accum' / 'denoised' / 'temporal' / 'tonemapped';
+        the last two need a temporal / tonemapped image)."""
         if isinstance(source, str):
             names = abi.OUTPUT_SOURCES
             if source not in names:
-                raise ValueError("set_output_source: unknown source %r (accum, denoised, temporal)" % source)
+                raise ValueError("set_output_source: unknown source %r (accum, denoised, temporal, tonemapped)" % source)
             source = names[source]
         self._chk(self._L.rmr_set_output_source(self._ctx, int(source)))
 
@@ -538,6 +539,73 @@ class Renderer:
     def temporal_reset(self):
         """rmr_temporal_reset: drop the history."""
         self._chk(self._L.rmr_temporal_reset(self._ctx))
+
+    # -- tone mapping and histogram auto-exposure --
+    @staticmethod
+    def _stage_source(who, source):
+        if isinstance(source, str):
+            if source not in ("accum", "denoised", "temporal"):
+                raise ValueError("%s: unknown source %r (accum, denoised, temporal)" % (who, source))
+            source = abi.OUTPUT_SOURCES[source]
+        return int(source)
+
+    def tonemap(self, source="accum", curve="aces", exposure=0.0, params=None, **kw):
+        """rmr_tonemap: scale the source image ('accum', 'denoised' or 'temporal', or abi.OUTPUT_*) by an
+        exposure and apply a curve ('linear', 'reinhard', 'aces', or abi.TONE_*); the result, values in
+        [0, 1] returned as (H, W, 4), is what set_output_source('tonemapped') shows. exposure: a number of
+        stops (scale 2^ev), or 'auto': metered on the GPU from the image's luminance histogram (then
+        exposure_ev, if given, is added to the metered value). Keywords: key (0.18), low_pct / high_pct
+        (0.10 / 0.90: the metered part of the histogram), adapt (1; the share of the way from the previous
+        exposure to the metered one, for a loop), white (4; reinhard's white point), exposure_ev."""
+        if params is not None and not isinstance(params, abi.TonemapParams):
+            raise TypeError("tonemap: params must be an abi.TonemapParams")
+        p = abi.default_tonemap_params() if params is None else abi.TonemapParams.from_buffer_copy(params)
+        if params is None:
+            if isinstance(curve, str):
+                if curve not in abi.TONE_CURVES:
+                    raise ValueError("tonemap: unknown curve %r (linear, reinhard, aces)" % curve)
+                curve = abi.TONE_CURVES[curve]
+            p.curve = int(curve)
+            if isinstance(exposure, str):
+                if exposure != "auto":
+                    raise ValueError("tonemap: exposure is a number of stops or 'auto', got %r" % exposure)
+                p.auto_exposure = 1
+            else:
+                p.exposure_ev = float(exposure)
+        for k, v in kw.items():
+            if k not in abi.TONEMAP_FIELDS:
+                raise TypeError("tonemap: unknown parameter %r" % k)
+            setattr(p, k, v)
+        self._chk(self._L.rmr_tonemap(self._ctx, self._stage_source("tonemap", source), C.byref(p)))
+        return self.read_tonemapped()
+
+    def read_tonemapped(self):
+        w, h = self.image_size()
+        out = np.zeros((h, w, 4), np.float32)
+        self._chk(self._L.rmr_read_tonemapped(self._ctx, _fp(out), out.nbytes))
+        return out
+
+    def tonemapped_device_ptr(self):
+        """Device pointer of the valid tonemapped image (W x H float4), None without one."""
+        return self._L.rmr_tonemapped_device_ptr(self._ctx)
+
+    def read_exposure(self):
+        """(log2_scale, scale) the last tonemap used."""
+        l, s = C.c_double(0.0), C.c_float(0.0)
+        self._chk(self._L.rmr_read_exposure(self._ctx, C.byref(l), C.byref(s)))
+        return l.value, np.float32(s.value)
+
+    def luminance_histogram(self, source="accum"):
+        """rmr_luminance_histogram: (hist (256,) uint32, skipped) of a source image, by the stage's kernels."""
+        hist = np.zeros(256, np.uint32)
+        skipped = C.c_uint64(0)
+        self._chk(self._L.rmr_luminance_histogram(self._ctx, self._stage_source("luminance_histogram", source),
+                                                  hist.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(skipped)))
+        return hist, int(skipped.value)
+
+    def tonemap_reset(self):
+        """rmr_tonemap_reset: drop the auto-exposure's adaptation state."""
+        self._chk(self._L.rmr_tonemap_reset(self._ctx))
 
     def temporal_images(self, S, hit, normal, view, h_rgba, h_n, h_hit, h_normal, h_view, samples=1.0, params=None,
                         **kw):
@@ -754,6 +822,46 @@ def check_temporal_params(params=None, **fields):
     """rmr_check_temporal_params (no GPU): True iff every field is in its range."""
     p = params if isinstance(params, abi.TemporalParams) else abi.default_temporal_params(**fields)
     return lib().rmr_check_temporal_params(C.byref(p)) == abi.RMR_OK
+
+
+def check_tonemap_params(params=None, **fields):
+    """rmr_check_tonemap_params (no GPU): True iff every field is in its range."""
+    p = params if isinstance(params, abi.TonemapParams) else abi.default_tonemap_params(**fields)
+    return lib().rmr_check_tonemap_params(C.byref(p)) == abi.RMR_OK
+
+
+def luminance_bins(rgba):
+    """rmr_luminance_bins (no GPU): the luminance bin (0..255, -1: skipped) of each RGBA pixel, (n,) int32."""
+    a = np.ascontiguousarray(rgba, np.float32).reshape(-1, 4)
+    out = np.zeros(len(a), np.int32)
+    rc = lib().rmr_luminance_bins(_fp(a), len(a), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_luminance_bins")
+    return out
+
+
+def exposure_from_histogram(hist, l_prev=None, params=None, **fields):
+    """rmr_exposure_from_histogram (no GPU): l (log2 of the scale) the meter gives for a 256-bin histogram;
+    l_prev: the previous state, None for none."""
+    p = params if isinstance(params, abi.TonemapParams) else abi.default_tonemap_params(**fields)
+    h = np.ascontiguousarray(hist, np.uint32).reshape(256)
+    out = C.c_double(0.0)
+    rc = lib().rmr_exposure_from_histogram(h.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(p),
+                                           C.c_double(float("nan") if l_prev is None else l_prev), C.byref(out))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_exposure_from_histogram: bad params")
+    return out.value
+
+
+def tonemap_pixels(rgba, scale, params=None, **fields):
+    """rmr_tonemap_pixels (no GPU): the curve of RGBA pixels at `scale`, in the shape given."""
+    p = params if isinstance(params, abi.TonemapParams) else abi.default_tonemap_params(**fields)
+    a = np.ascontiguousarray(rgba, np.float32)
+    out = np.zeros_like(a)
+    rc = lib().rmr_tonemap_pixels(C.byref(p), C.c_float(scale), _fp(a), a.size // 4, _fp(out))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_tonemap_pixels: bad params")
+    return out
 
 
 def temporal_view_inverse(view):
