@@ -563,6 +563,72 @@ int rmr_exposure_from_histogram(const uint32_t hist[256], const rmr_tonemap_para
 /* out = the curve p->curve (and p->white) of n RGBA pixels at `scale` (used as it is, whatever it is). */
 int rmr_tonemap_pixels(const rmr_tonemap_params* p, float scale, const float* rgba, size_t n, float* out);
 
+/* ---- HDR bloom ahead of tone mapping --------------------------------------------------------- */
+/* No counterpart in the reference. Additive: with nothing below called, every other entry point reads
+ * the planes it reads today. The stage spreads the part of an HDR image (the accumulator, the denoised
+ * or the temporal image) above a threshold over a Gaussian-like pyramid, adds the spread part back to
+ * the source and leaves the sum in a W x H RGBA32F plane of its own, RMR_OUTPUT_BLOOM, which rmr_tonemap,
+ * rmr_luminance_histogram, rmr_save_bmp and rmr_display* read like any other source. The source image
+ * is not written. DESIGN.md §4.14.
+ *
+ * The rule (csrc/rmr_bloom_rule.h, compiled by the kernels and by rmr_bloom_pixels). Every operation is
+ * float32 and rounded on its own (no fused multiply-add); `/` is the correctly rounded division; every
+ * select is a comparison.
+ *
+ * Sizes: w_0 = W, h_0 = H, w_k = (w_{k-1} + 1) >> 1, h_k likewise; a level may be 1 x 1.
+ * Bright part P(p) of a source pixel (r, g, b, a):
+ *   a == 0, or one of r, g, b not finite: the pixel is invalid and P = (0, 0, 0)
+ *   c = (x > 0 ? x : +0) per channel        (either zero and every negative read as +0: P has no -0)
+ *   L = (0.2126f c.r + 0.7152f c.g) + 0.0722f c.b;  L not finite: P = 0
+ *   e = L - T;  !(e > 0): P = 0;  clamp > 0 and e > clamp: e = clamp
+ *   f = e / L;  P = c f per channel
+ * Down, one dimension, n values to m = (n + 1) >> 1, cl clamping an index to [0, n-1], i = 2j:
+ *   d_j = ((a[cl(i-1)] + a[cl(i+2)]) + 3 (a[cl(i)] + a[cl(i+1)])) 0.125f
+ * Down, two dimensions: along x of every row, then along y of the result.
+ * Up, one dimension, m values to n, cl clamping to [0, m-1], j = i >> 1:
+ *   u_i = (3 b[j] + b[cl(i odd ? j+1 : j-1)]) 0.25f
+ * Up, two dimensions: along x, then along y.
+ * Pyramid: B_1 = down(P(S)), B_k = down(B_{k-1}) for k = 2..N; U_N = B_N,
+ *   U_k = B_k + s up(U_{k+1}) for k = N-1..1 (the product rounded, then the sum); G = up(U_1), W x H.
+ *   gain = (float)((double)I / sum), sum = p_0 + p_1 + ... + p_{N-1} added in that order in double,
+ *   p_0 = 1, p_j = p_{j-1} (double)s; computed on the host.
+ * Result: a valid pixel gets out.rgb = S.rgb + gain G (the product rounded, then the sum) and out.a = S.a;
+ * an invalid pixel is copied bit for bit. */
+#define RMR_OUTPUT_BLOOM 4
+typedef struct rmr_bloom_params {   /* 32 bytes */
+    int32_t levels;         /* N, 1..8;               default 5   */
+    float threshold;        /* T, finite >= 0;        default 1   */
+    float clamp;            /* finite >= 0, 0 = off;  default 0   */
+    float scatter;          /* s, 0 <= s <= 1;        default 0.7 */
+    float intensity;        /* I, finite >= 0;        default 0.2 */
+    int32_t reserved[3];    /* must be 0 */
+} rmr_bloom_params;
+void rmr_default_bloom_params(rmr_bloom_params* p);
+/* RMR_OK, or RMR_E_INVALID for a field outside the ranges above (NaN included) and for NULL. */
+int rmr_check_bloom_params(const rmr_bloom_params* p);
+/* The stage: source RMR_OUTPUT_ACCUM, RMR_OUTPUT_DENOISED or RMR_OUTPUT_TEMPORAL (anything else,
+ * RMR_OUTPUT_TONEMAPPED and RMR_OUTPUT_BLOOM included: RMR_E_INVALID; a source with no valid image:
+ * RMR_E_STATE), p NULL = the defaults. The pyramid (about a third of a plane) and the result plane are
+ * allocated at the first call, both or neither (RMR_E_NOMEM); rmr_reload (which is where a size given to
+ * rmr_set_image_size takes effect) and rmr_destroy free them. Queued on the context's stream without synchronising, after flushing held
+ * rmr_render calls.
+ * The bloom image is valid from then until any point where a tonemapped image would become invalid (a
+ * render, rmr_write_accum, rmr_bind_accum, rmr_set_view, rmr_set_params, a scene load, rmr_reload,
+ * rmr_denoise, rmr_denoise_variance), or, when it was made from the temporal image, until the next
+ * rmr_temporal_accumulate. A tonemapped image made from the bloom image becomes invalid when the bloom
+ * image does, and at the next rmr_bloom; rmr_bloom leaves a tonemapped image of any other source and the
+ * exposure adaptation state alone. */
+int rmr_bloom(rmr_ctx* ctx, int source, const rmr_bloom_params* p);
+/* The bloom image as RGBA32F (synchronises) and its device pointer; RMR_E_STATE / NULL without a valid
+ * one, never a stale image. rmr_tonemap and rmr_luminance_histogram accept RMR_OUTPUT_BLOOM as a source
+ * (RMR_E_STATE without a valid image); rmr_set_output_source(RMR_OUTPUT_BLOOM) is refused (RMR_E_STATE,
+ * the source unchanged) while there is none, as RMR_OUTPUT_TONEMAPPED is. */
+int rmr_read_bloom(rmr_ctx* ctx, float* rgba, size_t bytes);
+void* rmr_bloom_device_ptr(rmr_ctx* ctx);
+/* Context-free, host only (no GPU needed): the whole rule on a w x h RGBA32F host image; p NULL = the
+ * defaults. RMR_E_INVALID for NULL images, w or h < 1 and params rmr_check_bloom_params refuses. */
+int rmr_bloom_pixels(const rmr_bloom_params* p, const float* rgba, int w, int h, float* out);
+
 /* ---- camera models and caller-supplied rays ------------------------------------------------ */
 /* No counterpart in the reference, whose only camera is main()'s jittered interpolation of the four
  * corner rays from one point, the eye (RM1:569-584). Additive: with RMR_CAMERA_VIEW (the default) every

@@ -42,6 +42,8 @@ EXPORTS = [
     "rmr_default_tonemap_params", "rmr_check_tonemap_params", "rmr_tonemap", "rmr_read_tonemapped",
     "rmr_tonemapped_device_ptr", "rmr_read_exposure", "rmr_luminance_histogram", "rmr_tonemap_reset",
     "rmr_luminance_bins", "rmr_exposure_from_histogram", "rmr_tonemap_pixels",
+    "rmr_default_bloom_params", "rmr_check_bloom_params", "rmr_bloom", "rmr_read_bloom", "rmr_bloom_device_ptr",
+    "rmr_bloom_pixels",
 ]
 
 
@@ -201,6 +203,14 @@ def lib(diag=None):
         "rmr_luminance_bins": (C.c_int, [fp, C.c_size_t, C.POINTER(C.c_int32)]),
         "rmr_exposure_from_histogram": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(abi.TonemapParams), C.c_double, dp]),
         "rmr_tonemap_pixels": (C.c_int, [C.POINTER(abi.TonemapParams), C.c_float, fp, C.c_size_t, fp]),
+        "rmr_default_bloom_params": (None, [C.POINTER(abi.BloomParams)]),
+        "rmr_check_bloom_params": (C.c_int, [C.POINTER(abi.BloomParams)]),
+        "rmr_bloom": (C.c_int, [vp, C.c_int, C.POINTER(abi.BloomParams)]),
+        "rmr_read_bloom": (C.c_int, [vp, fp, C.c_size_t]),
+        "rmr_bloom_device_ptr": (vp, [vp]),
+        "rmr_bloom_pixels": (C.c_int, [C.POINTER(abi.BloomParams), fp, C.c_int, C.c_int, fp]),
+        "rmr_diag_bloom_tail": (C.c_int, [vp, C.c_int]),
+        "rmr_diag_bloom_time": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp]),
         "rmr_diag_tonemap_fold": (C.c_int, [vp, C.c_int]),
         "rmr_diag_tonemap_time": (C.c_int, [vp, C.c_int, C.c_int, fp]),
         # diagnostic library only (rmr_api.cpp RMR_DIAG): ray_exit at given rays; the a-trous passes

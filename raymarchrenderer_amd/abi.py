@@ -159,6 +159,24 @@ def default_temporal_params(**kw):
     return p
 
 
+class BloomParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("threshold", C.c_float), ("clamp", C.c_float), ("scatter", C.c_float),
+                ("intensity", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+BLOOM_FIELDS = ("levels", "threshold", "clamp", "scatter", "intensity")
+
+
+def default_bloom_params(**kw):
+    """rmr_default_bloom_params' values (rmr.h), with overrides."""
+    p = BloomParams(5, 1.0, 0.0, 0.7, 0.2)
+    for k, v in kw.items():
+        if k not in BLOOM_FIELDS:
+            raise TypeError("unknown bloom parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
 class TonemapParams(C.Structure):
     _fields_ = [("curve", C.c_int32), ("auto_exposure", C.c_int32), ("exposure_ev", C.c_float), ("key", C.c_float),
                 ("low_pct", C.c_float), ("high_pct", C.c_float), ("adapt", C.c_float), ("white", C.c_float)]
@@ -259,8 +277,9 @@ OUTPUT_ACCUM = 0
 OUTPUT_DENOISED = 1
 OUTPUT_TEMPORAL = 2
 OUTPUT_TONEMAPPED = 3
+OUTPUT_BLOOM = 4
 OUTPUT_SOURCES = {"accum": OUTPUT_ACCUM, "denoised": OUTPUT_DENOISED, "temporal": OUTPUT_TEMPORAL,
-                  "tonemapped": OUTPUT_TONEMAPPED}
+                  "tonemapped": OUTPUT_TONEMAPPED, "bloom": OUTPUT_BLOOM}
 # variance planes of the variance-guided denoiser (rmr.h)
 VARIANCE_SEED = 0
 VARIANCE_FILTERED = 1

@@ -31,6 +31,7 @@
 #include "scene.hpp"
 #include "temporal.hpp"
 #include "tonemap.hpp"
+#include "bloom.hpp"
 
 namespace rmr {
 hipError_t launch_trace(const KParams& P, int variant, int np, bool prog, bool persistent, int grid, hipStream_t s);
@@ -162,6 +163,14 @@ struct rmr_ctx {
     float tm_scale = 1.0f;
     bool tm_fold = false;                 // diagnostic library (tools/tonemap_time.py): k_lum_hist folds equal bins
                                           // inside the wave (measured and not kept: DESIGN.md §4.13, Appendix A)
+    // HDR bloom (rmr_bloom): the result plane (W x H float4) and the pyramid, one
+    // allocation of eight levels (about a third of a plane); allocated at the first call, both or neither,
+    // freed at rmr_reload / rmr_destroy
+    float4* d_bl = nullptr;
+    float4* d_bl_pyr = nullptr;
+    bool bl_valid = false;                // d_bl holds the bloom of bl_source as it is now
+    int bl_source = RMR_OUTPUT_ACCUM;
+    int bl_tail = rmr::kBloomTailDefault; // the most pixels the tail kernel's levels hold together (diagnostic library: 0 = off)
     // per-tile error estimate and adaptive sampling (rmr_estimate.hip, adaptive.hpp)
     bool est_on = false;                  // every launch's fold is k_fold_half (rmr_set_error_estimate)
     bool est_valid = false;               // d_half holds the odd samples of everything in the accumulator
@@ -337,7 +346,7 @@ void free_guides(rmr_ctx* c) {
     for (float4*& b : c->d_dn) { if (b) (void)hipFree(b); b = nullptr; }
     for (float*& b : c->d_var) { if (b) (void)hipFree(b); b = nullptr; }
     c->guides_valid = false;
-    c->dn_result = -1; c->tm_valid = false;
+    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
 }
 
 // Release the temporal stage's planes (the caller has synced the context's stream).
@@ -361,6 +370,15 @@ void free_tonemap(rmr_ctx* c) {
     c->d_tm_lc = nullptr;
     c->tm_valid = false;
     c->tm_used = 0;
+}
+
+// Release the bloom stage's planes (the caller has synced the context's stream).
+void free_bloom(rmr_ctx* c) {
+    if (c->d_bl) (void)hipFree(c->d_bl);
+    if (c->d_bl_pyr) (void)hipFree(c->d_bl_pyr);
+    c->d_bl = nullptr;
+    c->d_bl_pyr = nullptr;
+    c->bl_valid = false;
 }
 
 // Release the half image and the tile-error map (the caller has synced the context's stream).
@@ -486,7 +504,7 @@ int upload_scene(rmr_ctx* c) {
     c->scene_kp = scene_params(c);
     c->guides_valid = false;   // (every scene load comes through here)
     c->t_cur = -1;             // the temporal history is of the old scene
-    c->dn_result = -1; c->tm_valid = false;
+    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
     c->scene_loaded = true;
     c->jit_ready = false;
     c->jit_rays_ready = false;
@@ -982,7 +1000,7 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
     }
     const TileXY* d_tiles = nullptr;
     if (!rl) {
-        c->dn_result = -1; c->tm_valid = false;   // the accumulator changes: the denoised image is of the old one
+        c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;   // the accumulator changes: the denoised image is of the old one
         c->rendered = true;
         if ((r = tile_list(c, tiles, &d_tiles))) return r;
     }
@@ -1098,6 +1116,10 @@ int output_image(rmr_ctx* c, const char* who, const float4** out) {
         if (!c->tm_valid)
             return fail(c, RMR_E_STATE, std::string(who) + ": output source is the tonemapped image, but none is valid (call rmr_tonemap)");
         *out = c->d_tm;
+    } else if (c->output_source == RMR_OUTPUT_BLOOM) {
+        if (!c->bl_valid)
+            return fail(c, RMR_E_STATE, std::string(who) + ": output source is the bloom image, but none is valid (call rmr_bloom)");
+        *out = c->d_bl;
     } else {
         *out = c->d_accum;
     }
@@ -1222,6 +1244,7 @@ void rmr_destroy(rmr_ctx* c) {
     free_guides(c);
     free_temporal(c);
     free_tonemap(c);
+    free_bloom(c);
     if (c->d_half) (void)hipFree(c->d_half);
     if (c->d_tile_err) (void)hipFree(c->d_tile_err);
     if (c->d_accum && !c->accum_external) (void)hipFree(c->d_accum);
@@ -1277,7 +1300,7 @@ int rmr_set_params(rmr_ctx* c, const rmr_params* p) {
     if (p->max_steps < 0 || p->max_bounces < 0 || !(p->max_dist > 0.0f)) return fail(c, RMR_E_INVALID, "bad params");
     c->params = *p;
     c->guides_valid = false;
-    c->dn_result = -1; c->tm_valid = false;
+    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
     return RMR_OK;
 }
 
@@ -1297,7 +1320,7 @@ int rmr_set_view(rmr_ctx* c, const float eye[3], const float r00[3], const float
     }
     c->view_set = true;
     c->guides_valid = false;
-    c->dn_result = -1; c->tm_valid = false;
+    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
     return RMR_OK;
 }
 
@@ -1355,6 +1378,7 @@ int rmr_reload(rmr_ctx* c) {
     free_guides(c);   // (the stream is idle)
     free_temporal(c);
     free_tonemap(c);
+    free_bloom(c);
     c->W = c->pend_W;
     c->H = c->pend_H;
     if (resize) {
@@ -1383,7 +1407,7 @@ int rmr_render(rmr_ctx* c, float time, float min_x, float min_y, float max_x, fl
     }
     // deferred (rmr_set_call_batching): the errors the launch would give now come at the call
     if (const int r = launch_precheck(c)) return r;
-    c->dn_result = -1; c->tm_valid = false;
+    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
     c->rendered = true;
     rmr::DeferredCall* same = nullptr;
     bool overlap = false;
@@ -1464,7 +1488,7 @@ int rmr_write_accum(rmr_ctx* c, const float* rgba, size_t bytes) {
     RMR_FLUSH(c);
     const size_t need = (size_t)c->W * c->H * sizeof(float4);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
-    c->dn_result = -1; c->tm_valid = false;
+    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
     c->rendered = true;    // (the accumulator has contents the half image knows nothing of)
     c->est_valid = false;
     HIPCHK(c, hipMemcpyAsync(c->d_accum, rgba, need, hipMemcpyHostToDevice, c->stream));
@@ -1489,7 +1513,7 @@ int rmr_bind_accum(rmr_ctx* c, void* ptr, size_t bytes) {
     // (an external buffer is only swapped: launches already queued keep the pointer they captured)
     c->d_accum = (float4*)ptr;
     c->accum_external = true;
-    c->dn_result = -1; c->tm_valid = false;
+    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
     c->est_valid = false;
     return RMR_OK;
 }
@@ -2171,7 +2195,7 @@ int rmr_denoise(rmr_ctx* c, const rmr_denoise_params* p) {
     if (!denoise_params_ok(q))
         return fail(c, RMR_E_INVALID, "bad denoise params (iterations 0..8, normal_pow2 0..7, sigma_z finite > 0, sigma_c finite >= 0)");
     int r;
-    c->dn_result = -1; c->tm_valid = false;
+    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
     c->dn_guided = false;
     if (!c->guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
     HIPCHK(c, hipSetDevice(c->device));
@@ -2222,13 +2246,15 @@ int rmr_set_output_source(rmr_ctx* c, int source) {
     if (!c) return RMR_E_INVALID;
     RMR_FLUSH(c);
     if (source != RMR_OUTPUT_ACCUM && source != RMR_OUTPUT_DENOISED && source != RMR_OUTPUT_TEMPORAL &&
-        source != RMR_OUTPUT_TONEMAPPED)
+        source != RMR_OUTPUT_TONEMAPPED && source != RMR_OUTPUT_BLOOM)
         return fail(c, RMR_E_INVALID, "bad output source");
     // (refused, the source unchanged, while there is no temporal image to read)
     if (source == RMR_OUTPUT_TEMPORAL && c->t_cur < 0)
         return fail(c, RMR_E_STATE, "no valid temporal image (call rmr_temporal_accumulate)");
     if (source == RMR_OUTPUT_TONEMAPPED && !c->tm_valid)
         return fail(c, RMR_E_STATE, "no valid tonemapped image (call rmr_tonemap)");
+    if (source == RMR_OUTPUT_BLOOM && !c->bl_valid)
+        return fail(c, RMR_E_STATE, "no valid bloom image (call rmr_bloom)");
     c->output_source = source;
     return RMR_OK;
 }
@@ -2448,7 +2474,7 @@ int rmr_denoise_variance(rmr_ctx* c, const rmr_denoise_params* p, const rmr_vari
     if (!c->est_on || !c->est_valid || !c->d_half)
         return fail(c, RMR_E_STATE, "the error estimate is not valid: call rmr_set_error_estimate before the first "
                                     "render since rmr_reload, or render with rmr_render_adaptive");
-    c->dn_result = -1; c->tm_valid = false;
+    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
     c->dn_guided = false;
     if (!c->guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
     HIPCHK(c, hipSetDevice(c->device));
@@ -2604,6 +2630,10 @@ int rmr_temporal_accumulate(rmr_ctx* c, int source, float samples, const rmr_tem
     const int from = c->t_cur, to = 1 - from;
     c->t_cur = -1;   // (until everything below is queued)
     if (c->tm_source == RMR_OUTPUT_TEMPORAL) c->tm_valid = false;   // (a tonemapped image of the old temporal image)
+    if (c->bl_source == RMR_OUTPUT_TEMPORAL) {                      // (and a bloom image of it, with what was tonemapped from that)
+        if (c->bl_valid && c->tm_source == RMR_OUTPUT_BLOOM) c->tm_valid = false;
+        c->bl_valid = false;
+    }
     T.d.in = source == RMR_OUTPUT_DENOISED ? c->d_dn[c->dn_result] : c->d_accum;
     T.d.hit = c->d_guide[RMR_GUIDE_HIT];
     T.d.nrm = c->d_guide[RMR_GUIDE_NORMAL];
@@ -2714,8 +2744,11 @@ int rmr_temporal_images(rmr_ctx* c, const float* s_rgba, const float* hit, const
 static_assert(sizeof(rmr_tonemap_params) == 32, "rmr_tonemap_params is 32 bytes (include/rmr.h)");
 namespace {
 // The image a stage source names, with the existing readers' messages.
-int tone_source(rmr_ctx* c, int source, const float4** src) {
-    if (source == RMR_OUTPUT_ACCUM) {
+int tone_source(rmr_ctx* c, int source, const float4** src, bool bloom_too = false) {
+    if (bloom_too && source == RMR_OUTPUT_BLOOM) {
+        if (!c->bl_valid) return fail(c, RMR_E_STATE, "no valid bloom image (call rmr_bloom)");
+        *src = c->d_bl;
+    } else if (source == RMR_OUTPUT_ACCUM) {
         *src = c->d_accum;
     } else if (source == RMR_OUTPUT_DENOISED) {
         if (c->dn_result < 0) return fail(c, RMR_E_STATE, "no valid denoised image (call rmr_denoise)");
@@ -2724,7 +2757,8 @@ int tone_source(rmr_ctx* c, int source, const float4** src) {
         if (c->t_cur < 0) return fail(c, RMR_E_STATE, "no valid temporal image (call rmr_temporal_accumulate)");
         *src = c->d_tcol[c->t_cur];
     } else {
-        return fail(c, RMR_E_INVALID, "bad source (RMR_OUTPUT_ACCUM, RMR_OUTPUT_DENOISED or RMR_OUTPUT_TEMPORAL)");
+        return fail(c, RMR_E_INVALID, bloom_too ? "bad source (RMR_OUTPUT_ACCUM, RMR_OUTPUT_DENOISED, RMR_OUTPUT_TEMPORAL or RMR_OUTPUT_BLOOM)"
+                                                : "bad source (RMR_OUTPUT_ACCUM, RMR_OUTPUT_DENOISED or RMR_OUTPUT_TEMPORAL)");
     }
     return RMR_OK;
 }
@@ -2781,7 +2815,7 @@ int rmr_tonemap(rmr_ctx* c, int source, const rmr_tonemap_params* p) {
                                       "0 <= low_pct < high_pct <= 1, 0 < adapt <= 1, white > 0)");
     const float4* src = nullptr;
     int r;
-    if ((r = tone_source(c, source, &src))) return r;
+    if ((r = tone_source(c, source, &src, true))) return r;
     HIPCHK(c, hipSetDevice(c->device));
     if ((r = ensure_tonemap(c))) return r;
     c->tm_valid = false;   // (until everything below is queued)
@@ -2844,7 +2878,7 @@ int rmr_luminance_histogram(rmr_ctx* c, int source, uint32_t hist[256], uint64_t
     RMR_FLUSH(c);
     const float4* src = nullptr;
     int r;
-    if ((r = tone_source(c, source, &src))) return r;
+    if ((r = tone_source(c, source, &src, true))) return r;
     HIPCHK(c, hipSetDevice(c->device));
     if ((r = ensure_tonemap(c))) return r;
     rmr_tonemap_params q;
@@ -2867,7 +2901,146 @@ int rmr_tonemap_reset(rmr_ctx* c) {
     return RMR_OK;
 }
 
+// ---- HDR bloom ahead of tone mapping (rmr_bloom.hip, bloom.cpp) -------------------------------------
+static_assert(sizeof(rmr_bloom_params) == 32, "rmr_bloom_params is 32 bytes (include/rmr.h)");
+namespace {
+// The result plane and the pyramid (all eight levels, so that every `levels` finds room), at first use:
+// both or neither.
+int ensure_bloom(rmr_ctx* c) {
+    if (c->d_bl) return RMR_OK;
+    const rmr::BloomLevels L = rmr::bloom_levels(c->W, c->H, rmr::kBloomMaxLevels);
+    void *plane = nullptr, *pyr = nullptr;
+    if (hipMalloc(&plane, (size_t)c->W * c->H * sizeof(float4)) != hipSuccess ||
+        hipMalloc(&pyr, L.total * sizeof(float4)) != hipSuccess) {
+        (void)hipGetLastError();
+        if (plane) (void)hipFree(plane);
+        return fail(c, RMR_E_NOMEM, "cannot allocate the bloom plane (16 bytes per pixel) and its pyramid (a third of that)");
+    }
+    c->d_bl = (float4*)plane;
+    c->d_bl_pyr = (float4*)pyr;
+    c->bl_valid = false;
+    return RMR_OK;
+}
+
+// The stage's launches for src and q on the context's stream; what: 0 everything, 1 k_bloom_down0 alone,
+// 2 k_bloom_compose alone (over the pyramid as it is).
+hipError_t bloom_queue(rmr_ctx* c, const float4* src, const rmr_bloom_params& q, int what) {
+    const int N = q.levels;
+    const rmr::BloomLevels L = rmr::bloom_levels(c->W, c->H, rmr::kBloomMaxLevels);
+    float4* pyr = c->d_bl_pyr;
+    const float gain = rmr::bloom_gain(q.intensity, q.scatter, N);
+    hipError_t e = hipSuccess;
+    if (what == 1) return rmr::launch_bloom_down0(src, L.w[0], L.h[0], q.threshold, q.clamp, pyr + L.off[1], c->stream);
+    if (what == 2) return rmr::launch_bloom_compose(src, L.w[0], L.h[0], pyr + L.off[1], gain, c->d_bl, c->stream);
+    rmr::BloomTail t;
+    const bool tail = c->bl_tail > 0 && rmr::bloom_tail_plan(L.w, L.h, N, c->bl_tail, q.threshold, q.clamp, q.scatter, &t);
+    const int last_down = tail ? t.k0 - 1 : N;   // the levels the per-level kernels write
+    if (last_down >= 1) e = rmr::launch_bloom_down0(src, L.w[0], L.h[0], q.threshold, q.clamp, pyr + L.off[1], c->stream);
+    for (int k = 2; k <= last_down && e == hipSuccess; k++)
+        e = rmr::launch_bloom_down(pyr + L.off[k - 1], L.w[k - 1], L.h[k - 1], pyr + L.off[k], c->stream);
+    if (tail && e == hipSuccess)
+        e = rmr::launch_bloom_tail(t.k0 == 1 ? src : pyr + L.off[t.k0 - 1], pyr + L.off[t.k0], t, c->stream);
+    for (int k = (tail ? t.k0 - 1 : N - 1); k >= 1 && e == hipSuccess; k--)
+        e = rmr::launch_bloom_up(pyr + L.off[k], L.w[k], L.h[k], pyr + L.off[k + 1], q.scatter, c->stream);
+    if (e == hipSuccess) e = rmr::launch_bloom_compose(src, L.w[0], L.h[0], pyr + L.off[1], gain, c->d_bl, c->stream);
+    return e;
+}
+}  // namespace
+
+int rmr_bloom(rmr_ctx* c, int source, const rmr_bloom_params* p) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_bloom_params q;
+    rmr_default_bloom_params(&q);
+    if (p) q = *p;
+    if (!rmr::bloom_params_ok(q))
+        return fail(c, RMR_E_INVALID, "bad bloom params (levels 1..8, threshold >= 0, clamp >= 0, 0 <= scatter <= 1, "
+                                      "intensity >= 0, reserved 0)");
+    const float4* src = nullptr;
+    int r;
+    if ((r = tone_source(c, source, &src))) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((r = ensure_bloom(c))) return r;
+    c->bl_valid = false;   // (until everything below is queued)
+    if (c->tm_source == RMR_OUTPUT_BLOOM) c->tm_valid = false;   // (a tonemapped image of the old bloom image)
+    HIPCHK(c, bloom_queue(c, src, q, 0));
+    c->bl_source = source;
+    c->bl_valid = true;
+    return RMR_OK;
+}
+
+int rmr_read_bloom(rmr_ctx* c, float* rgba, size_t bytes) {
+    if (!c || !rgba) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    const size_t need = (size_t)c->W * c->H * sizeof(float4);
+    if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
+    if (!c->bl_valid) return fail(c, RMR_E_STATE, "no valid bloom image (call rmr_bloom)");
+    HIPCHK(c, hipMemcpyAsync(rgba, c->d_bl, need, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+void* rmr_bloom_device_ptr(rmr_ctx* c) {
+    if (!c) return nullptr;
+    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
+    return c->bl_valid ? (void*)c->d_bl : nullptr;
+}
+
 #if RMR_DIAG
+// Diagnostic library only (not in include/rmr.h; tools/bloom_time.py, tests/test_gpu_bloom.py): the most
+// pixels the tail kernel's levels hold together, 0 = per-level launches only, -1 = the default. The
+// results are the same either way.
+int rmr_diag_bloom_tail(rmr_ctx* c, int max_pixels) {
+    if (!c || max_pixels < -1) return RMR_E_INVALID;
+    c->bl_tail = max_pixels < 0 ? rmr::kBloomTailDefault : max_pixels;
+    return RMR_OK;
+}
+
+// Diagnostic library only (not in include/rmr.h; tools/bloom_time.py): *ms = the GPU's time per round of n
+// back-to-back rounds of one thing on the accumulator: 0 the whole stage at `levels` as rmr_bloom queues it,
+// 1 k_bloom_down0, 2 k_bloom_compose, 3 a device-to-device copy of the accumulator into the bloom plane (the
+// yardstick). Queued behind a busy stream and between two events, as rmr_diag_tonemap_time does (32 k_meter
+// launches; n <= 64 keeps the host ahead). Synchronises. The bloom image is invalid afterwards.
+int rmr_diag_bloom_time(rmr_ctx* c, int which, int levels, int n, float* ms) {
+    if (!c || !ms || which < 0 || which > 3 || levels < 1 || levels > rmr::kBloomMaxLevels || n < 1 || n > 64) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r;
+    if ((r = ensure_tonemap(c))) return r;
+    if ((r = ensure_bloom(c))) return r;
+    c->bl_valid = false;
+    if (c->tm_source == RMR_OUTPUT_BLOOM) c->tm_valid = false;
+    const size_t px = (size_t)c->W * c->H;
+    const int blocks = rmr::lum_hist_blocks(px);
+    rmr_tonemap_params tq;
+    rmr_default_tonemap_params(&tq);
+    const rmr::ToneMeter M = rmr::tonemap_meter(tq);
+    rmr_bloom_params q;
+    rmr_default_bloom_params(&q);
+    q.levels = levels;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    HIPCHK(c, hipEventCreate(&ev[0]));
+    hipError_t e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = rmr::launch_lum_hist(c->d_accum, px, c->d_tm_slab, blocks, false, c->stream);
+    for (int i = 0; i < 32 && e == hipSuccess; i++)
+        e = rmr::launch_meter(c->d_tm_slab, blocks, c->d_tm_state, c->d_tm_lc, M, false, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
+    for (int i = 0; i < n && e == hipSuccess; i++) {
+        if (which == 3) e = hipMemcpyAsync(c->d_bl, c->d_accum, px * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
+        else e = bloom_queue(c, c->d_accum, q, which);
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    float t = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&t, ev[0], ev[1]);
+    (void)hipEventDestroy(ev[0]);
+    if (ev[1]) (void)hipEventDestroy(ev[1]);
+    HIPCHK(c, e);
+    *ms = t / (float)n;
+    return RMR_OK;
+}
+
 // Diagnostic library only (not in include/rmr.h; tools/tonemap_time.py): whether k_lum_hist folds equal
 // bins inside the wave before the LDS add; the counts are the same either way.
 int rmr_diag_tonemap_fold(rmr_ctx* c, int on) {

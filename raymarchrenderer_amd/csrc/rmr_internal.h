@@ -201,6 +201,17 @@ struct ToneState {
 };
 constexpr int kToneSlabRows = 512;   // most blocks k_lum_hist runs: rows of the [rows][257] slab
 struct ToneMeter;                    // rmr_tonemap_rule.h
+constexpr int kBloomTailThreads = 1024;
+constexpr int kBloomTailPixels = 12288;   // 12 B each: 144 KiB of the CU's 160 KiB of LDS
+// The levels the tail takes by default, in pixels of all of them together (measured, DESIGN.md §4.14: from
+// 60x34 down the tail beats the per-level launches, from 120x68 down it loses to them).
+constexpr int kBloomTailDefault = 4096;
+struct BloomTail {
+    int k0, count;              // the levels k0 .. k0 + count - 1 (count >= 2)
+    int w_in, h_in;             // the size of level k0 - 1, the tail's input
+    int from_source;            // k0 = 1: the input is the source image, read through the bright part
+    float threshold, clamp, scatter;
+};
 #ifndef __HIPCC_RTC__
 int lum_hist_blocks(size_t n);
 // fold: equal bins are folded inside the wave before the LDS add (the same counts either way)
@@ -210,6 +221,22 @@ hipError_t launch_meter(const uint32_t* slab, int rows, ToneState* st, const dou
 // st: the state whose scale is applied, or null for `scale` itself
 hipError_t launch_tonemap(const float4* in, float4* out, size_t n, const ToneState* st, float scale, int curve, float iw2,
                           hipStream_t s);
+// HDR bloom (rmr_bloom.hip). down0: P of the w x h source and the first down, into the
+// bloom_half(w) x bloom_half(h) level `out`; down: one level to the next; up: U_k = B_k + s up(U_{k+1}) in
+// place on the w x h level `bk`, `uk1` being bloom_half(w) x bloom_half(h); compose: out = src + gain up(u1)
+// with the copy rule, u1 being bloom_half(w) x bloom_half(h).
+// The tail: the levels k0 .. k0 + count - 1 (the last one the pyramid's last), downs and ups, by one block in
+// LDS; `in` is level k0 - 1 (the source image when k0 = 1), `out` level k0, which receives U_k0.
+// bloom_tail_plan: the tail of a pyramid of `levels` levels of sizes w[k] x h[k], k0 being the first level
+// from which all of them hold at most max_pixels pixels (and kBloomTailPixels) together; false where that is
+// fewer than two levels.
+hipError_t launch_bloom_tail(const float4* in, float4* out, const BloomTail& t, hipStream_t s);
+bool bloom_tail_plan(const int* w, const int* h, int levels, int max_pixels, float threshold, float clamp, float scatter,
+                     BloomTail* t);
+hipError_t launch_bloom_down0(const float4* src, int w, int h, float threshold, float clamp, float4* out, hipStream_t s);
+hipError_t launch_bloom_down(const float4* in, int w, int h, float4* out, hipStream_t s);
+hipError_t launch_bloom_up(float4* bk, int w, int h, const float4* uk1, float scatter, hipStream_t s);
+hipError_t launch_bloom_compose(const float4* src, int w, int h, const float4* u1, float gain, float4* out, hipStream_t s);
 hipError_t launch_temporal(const TemporalPass& T, hipStream_t s);
 hipError_t launch_variance_seed(const VarianceSeed& V, hipStream_t s);
 // tiled: the LDS form (step 1 or 2 only; other steps run the plain form)

@@ -207,6 +207,10 @@ void Graphics::setOutputSource(int source) {
     if (!need_ctx("setOutputSource") || !no_group("setOutputSource")) return;
     check(rmr_set_output_source(g_ctx, source), "setOutputSource");
 }
+void Graphics::Bloom(int source, const rmr_bloom_params& p) {
+    if (!need_ctx("Bloom") || !no_group("Bloom")) return;
+    check(rmr_bloom(g_ctx, source, &p), "Bloom");
+}
 void Graphics::Tonemap(int source, const rmr_tonemap_params& p) {
     if (!need_ctx("Tonemap") || !no_group("Tonemap")) return;
     check(rmr_tonemap(g_ctx, source, &p), "Tonemap");

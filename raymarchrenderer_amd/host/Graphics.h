@@ -73,8 +73,13 @@ public:
     static void setErrorEstimate(bool on);
     static void DenoiseVariance(int iterations = 5, float sigma_l = 4.0f);
     static void setOutputSource(int source);
+    // HDR bloom (rmr_bloom): the part of the source image (RMR_OUTPUT_ACCUM / _DENOISED / _TEMPORAL) above
+    // p's threshold, spread over a pyramid and added back, into the bloom image, which Tonemap reads as
+    // RMR_OUTPUT_BLOOM and setOutputSource(RMR_OUTPUT_BLOOM) shows and saves. Single-context mode only, like
+    // Denoise.
+    static void Bloom(int source, const rmr_bloom_params& p);
     // Tone mapping and auto-exposure (rmr_tonemap): the source image (RMR_OUTPUT_ACCUM / _DENOISED /
-    // _TEMPORAL) through p's exposure and curve into the tonemapped image, which
+    // _TEMPORAL / _BLOOM) through p's exposure and curve into the tonemapped image, which
     // setOutputSource(RMR_OUTPUT_TONEMAPPED) then shows and saves. Single-context mode only, like Denoise.
     static void Tonemap(int source, const rmr_tonemap_params& p);
     // What the last Tonemap used (rmr_read_exposure); false (status in lastStatus) on failure.

@@ -60,6 +60,8 @@ struct Options {
     int denoise = -1;               // --denoise [N]: a-trous iterations, -1 = no denoise
     bool tonemap = false;           // --tonemap / --exposure: the tone-mapping stage runs last, with `tone`
     rmr_tonemap_params tone{};
+    bool bloom = false;             // --bloom [THRESHOLD[:INTENSITY]]: the bloom stage runs before the tone mapping
+    rmr_bloom_params bloom_p{};
     double variance_guided = -1.0;  // --variance-guided [SIGMA_L]: the guided filter's sigma_l, < 0 = the plain filter
     std::string aov;                // --aov PREFIX: guide planes as PREFIX_*.pfm
     double adaptive = -1.0;         // --adaptive T: the tile-error threshold, < 0 = uniform sampling
@@ -438,6 +440,10 @@ void usage() {
         "  --variance-guided [SIGMA_L]  with --denoise: the variance-guided filter (luminance weight of\n"
         "                      SIGMA_L standard deviations, default 4; safe at any sample count); keeps the\n"
         "                      error estimate on from the first sample; --aov adds PREFIX_variance.pfm\n"
+        "  --bloom [THRESHOLD[:INTENSITY]]  after the render (and --denoise), before --tonemap: spread the part of\n"
+        "                      the image above THRESHOLD (scene units, default 1) over a five-level pyramid and\n"
+        "                      add INTENSITY (default 0.2) of it back; --tonemap then reads the bloom image, and\n"
+        "                      without --tonemap --out is written from it; not with --gpus / --devices\n"
         "  --tonemap linear|reinhard[:WHITE]|aces   after the render (and --denoise): tone-map the image with\n"
         "                      that curve (reinhard's white point, default 4) and write --out from the result\n"
         "  --exposure EV|auto[:KEY]   the stage's exposure: EV stops (scale 2^EV, |EV| <= 32), or metered from\n"
@@ -496,6 +502,7 @@ bool name_and_number(const std::string& v, const char* name, float& num, bool& h
 bool parse(int argc, char** argv, Options& o) {
     rmr_default_params(&o.params);
     rmr_default_tonemap_params(&o.tone);
+    rmr_default_bloom_params(&o.bloom_p);
     rmr_default_camera_model(&o.model);
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -547,6 +554,20 @@ bool parse(int argc, char** argv, Options& o) {
                 if (end == v || *end != '\0' || !std::isfinite(o.variance_guided) || !(o.variance_guided > 0) ||
                     !std::isfinite((float)o.variance_guided) || !((float)o.variance_guided > 0.0f))
                     return false;
+            }
+        } else if (a == "--bloom") {   // the value is optional: taken when the next argument is no option
+            o.bloom = true;
+            if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {
+                const char* v = argv[++i];
+                char* end = nullptr;
+                o.bloom_p.threshold = std::strtof(v, &end);
+                if (end == v) return false;
+                if (*end == ':') {
+                    const char* w = end + 1;
+                    o.bloom_p.intensity = std::strtof(w, &end);
+                    if (end == w) return false;
+                }
+                if (*end != '\0') return false;
             }
         } else if (a == "--tonemap") {
             const std::string v = next("--tonemap");
@@ -628,6 +649,10 @@ bool parse(int argc, char** argv, Options& o) {
         std::fprintf(stderr, "--tonemap / --exposure: reinhard needs WHITE > 0, auto KEY > 0, and |EV| <= 32\n");
         return false;
     }
+    if (rmr_check_bloom_params(&o.bloom_p) != RMR_OK) {
+        std::fprintf(stderr, "--bloom: THRESHOLD and INTENSITY are finite and >= 0\n");
+        return false;
+    }
     if (o.adaptive >= 0 && (o.min_samples < 2 || o.pass_samples < 1 || o.samples < o.min_samples)) {
         std::fprintf(stderr, "--adaptive: --min-samples >= 2, --pass-samples >= 1 and --samples >= --min-samples\n");
         return false;
@@ -665,6 +690,10 @@ int main(int argc, char** argv) {
     }
     if (o.tonemap && (!o.devices.empty() || o.interactive)) {
         std::fprintf(stderr, "--tonemap / --exposure: not with --gpus / --devices or --interactive\n");
+        return 2;
+    }
+    if (o.bloom && (!o.devices.empty() || o.interactive)) {
+        std::fprintf(stderr, "--bloom: not with --gpus / --devices or --interactive\n");
         return 2;
     }
     if (o.model.model != RMR_CAMERA_VIEW && !o.devices.empty()) {
@@ -714,8 +743,16 @@ int main(int argc, char** argv) {
         if (Graphics::lastStatus() != RMR_OK) return 1;
         Graphics::setOutputSource(RMR_OUTPUT_DENOISED);
     }
+    int shown = o.denoise >= 0 ? RMR_OUTPUT_DENOISED : RMR_OUTPUT_ACCUM;   // the image --out is written from
+    if (o.bloom) {
+        Graphics::Bloom(shown, o.bloom_p);
+        if (Graphics::lastStatus() != RMR_OK) return 1;
+        shown = RMR_OUTPUT_BLOOM;
+        Graphics::setOutputSource(shown);
+        if (Graphics::lastStatus() != RMR_OK) return 1;
+    }
     if (o.tonemap) {   // last: the image --out would have been written from, through the exposure and the curve
-        Graphics::Tonemap(o.denoise >= 0 ? RMR_OUTPUT_DENOISED : RMR_OUTPUT_ACCUM, o.tone);
+        Graphics::Tonemap(shown, o.tone);
         if (Graphics::lastStatus() != RMR_OK) return 1;
         Graphics::setOutputSource(RMR_OUTPUT_TONEMAPPED);
         if (Graphics::lastStatus() != RMR_OK) return 1;

@@ -484,12 +484,12 @@ class Renderer:
 
     def set_output_source(self, source):
         """What save_bmp / display / display_device read: abi.OUTPUT_ACCUM (default), abi.OUTPUT_DENOISED
-        abi.OUTPUT_TEMPORAL or abi.OUTPUT_TONEMAPPED (also 'accum' / 'denoised' / 'temporal' / 'tonemapped';
-        the last two need a temporal / tonemapped image)."""
+        abi.OUTPUT_TEMPORAL, abi.OUTPUT_TONEMAPPED or abi.OUTPUT_BLOOM (also 'accum' / 'denoised' / 'temporal' /
+        'tonemapped' / 'bloom'; the last three need a temporal / tonemapped / bloom image)."""
         if isinstance(source, str):
             names = abi.OUTPUT_SOURCES
             if source not in names:
-                raise ValueError("set_output_source: unknown source %r (accum, denoised, temporal, tonemapped)" % source)
+                raise ValueError("set_output_source: unknown source %r (accum, denoised, temporal, tonemapped, bloom)" % source)
             source = names[source]
         self._chk(self._L.rmr_set_output_source(self._ctx, int(source)))
 
@@ -542,15 +542,17 @@ class Renderer:
 
     # -- tone mapping and histogram auto-exposure --
     @staticmethod
-    def _stage_source(who, source):
+    def _stage_source(who, source, names=("accum", "denoised", "temporal")):
         if isinstance(source, str):
-            if source not in ("accum", "denoised", "temporal"):
-                raise ValueError("%s: unknown source %r (accum, denoised, temporal)" % (who, source))
+            if source not in names:
+                raise ValueError("%s: unknown source %r (%s)" % (who, source, ", ".join(names)))
             source = abi.OUTPUT_SOURCES[source]
         return int(source)
 
+    _BLOOM_TOO = ("accum", "denoised", "temporal", "bloom")
+
     def tonemap(self, source="accum", curve="aces", exposure=0.0, params=None, **kw):
-        """rmr_tonemap: scale the source image ('accum', 'denoised' or 'temporal', or abi.OUTPUT_*) by an
+        """rmr_tonemap: scale the source image ('accum', 'denoised', 'temporal' or 'bloom', or abi.OUTPUT_*) by an
         exposure and apply a curve ('linear', 'reinhard', 'aces', or abi.TONE_*); the result, values in
         [0, 1] returned as (H, W, 4), is what set_output_source('tonemapped') shows. exposure: a number of
         stops (scale 2^ev), or 'auto': metered on the GPU from the image's luminance histogram (then
@@ -576,7 +578,7 @@ class Renderer:
             if k not in abi.TONEMAP_FIELDS:
                 raise TypeError("tonemap: unknown parameter %r" % k)
             setattr(p, k, v)
-        self._chk(self._L.rmr_tonemap(self._ctx, self._stage_source("tonemap", source), C.byref(p)))
+        self._chk(self._L.rmr_tonemap(self._ctx, self._stage_source("tonemap", source, self._BLOOM_TOO), C.byref(p)))
         return self.read_tonemapped()
 
     def read_tonemapped(self):
@@ -599,13 +601,41 @@ class Renderer:
         """rmr_luminance_histogram: (hist (256,) uint32, skipped) of a source image, by the stage's kernels."""
         hist = np.zeros(256, np.uint32)
         skipped = C.c_uint64(0)
-        self._chk(self._L.rmr_luminance_histogram(self._ctx, self._stage_source("luminance_histogram", source),
+        self._chk(self._L.rmr_luminance_histogram(self._ctx, self._stage_source("luminance_histogram", source, self._BLOOM_TOO),
                                                   hist.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(skipped)))
         return hist, int(skipped.value)
 
     def tonemap_reset(self):
         """rmr_tonemap_reset: drop the auto-exposure's adaptation state."""
         self._chk(self._L.rmr_tonemap_reset(self._ctx))
+
+    # -- HDR bloom ahead of tone mapping --
+    def bloom(self, source="accum", levels=5, threshold=1.0, clamp=0.0, scatter=0.7, intensity=0.2, params=None):
+        """rmr_bloom: spread the part of the source image ('accum', 'denoised' or 'temporal', or abi.OUTPUT_*)
+        above `threshold` (scene units) over a pyramid of `levels` levels and add it back, `intensity` of it in
+        all; scatter: the weight of each coarser level against the finer one; clamp (0 = off): the most a
+        pixel's excess over the threshold counts (fireflies). The sum, returned as (H, W, 4), is what
+        tonemap('bloom') and set_output_source('bloom') read. params: an abi.BloomParams instead of the
+        keywords."""
+        if params is not None and not isinstance(params, abi.BloomParams):
+            raise TypeError("bloom: params must be an abi.BloomParams")
+        if params is None:
+            p = abi.default_bloom_params(levels=int(levels), threshold=threshold, clamp=clamp, scatter=scatter,
+                                         intensity=intensity)
+        else:
+            p = abi.BloomParams.from_buffer_copy(params)
+        self._chk(self._L.rmr_bloom(self._ctx, self._stage_source("bloom", source), C.byref(p)))
+        return self.read_bloom()
+
+    def read_bloom(self):
+        w, h = self.image_size()
+        out = np.zeros((h, w, 4), np.float32)
+        self._chk(self._L.rmr_read_bloom(self._ctx, _fp(out), out.nbytes))
+        return out
+
+    def bloom_device_ptr(self):
+        """Device pointer of the valid bloom image (W x H float4), None without one."""
+        return self._L.rmr_bloom_device_ptr(self._ctx)
 
     def temporal_images(self, S, hit, normal, view, h_rgba, h_n, h_hit, h_normal, h_view, samples=1.0, params=None,
                         **kw):
@@ -822,6 +852,25 @@ def check_temporal_params(params=None, **fields):
     """rmr_check_temporal_params (no GPU): True iff every field is in its range."""
     p = params if isinstance(params, abi.TemporalParams) else abi.default_temporal_params(**fields)
     return lib().rmr_check_temporal_params(C.byref(p)) == abi.RMR_OK
+
+
+def check_bloom_params(params=None, **fields):
+    """rmr_check_bloom_params (no GPU): True iff every field is in its range."""
+    p = params if isinstance(params, abi.BloomParams) else abi.default_bloom_params(**fields)
+    return lib().rmr_check_bloom_params(C.byref(p)) == abi.RMR_OK
+
+
+def bloom_pixels(rgba, params=None, **fields):
+    """rmr_bloom_pixels (no GPU): the whole bloom rule on an (H, W, 4) image."""
+    p = params if isinstance(params, abi.BloomParams) else abi.default_bloom_params(**fields)
+    a = np.ascontiguousarray(rgba, np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("bloom_pixels: an (H, W, 4) image, got shape %r" % (a.shape,))
+    out = np.zeros_like(a)
+    rc = lib().rmr_bloom_pixels(C.byref(p), _fp(a), a.shape[1], a.shape[0], _fp(out))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_bloom_pixels: bad params or image")
+    return out
 
 
 def check_tonemap_params(params=None, **fields):
