@@ -189,6 +189,12 @@ int rmr_get_section_cycles(rmr_ctx* ctx, uint64_t out[4]);
  * [14] map evals in shading batches (certified getNormal probes, rmr_trace.h cert_normals; part of [0]),
  * [4..7] the section cycles above (or the RMR_JIT_AMBCOUNT fallback counts, tools/amb_rate.py). */
 int rmr_get_counters(rmr_ctx* ctx, uint64_t out[16]);
+/* The first n of the whole counter block (n <= 32). [0..15] as above; [16] events the lane-slot kernels
+ * deposited into another lane's empty slot (the overflow deposit, rmr_trace.h RMR_SLOT_OVERFLOW);
+ * [17..30] the profiling build's counters, each in a slot of its own (rmr_internal.h kCntProf*: refill
+ * claim / ray cycles, uncertified hits, lanes per full map() batch, and the lane-slot schedule's passes,
+ * park steps, lost lane-iterations by cause and events per batch); zeros in every other build. */
+int rmr_get_counters_n(rmr_ctx* ctx, uint64_t* out, int n);
 /* Select kernel implementation (0 = persistent wavefront kernel, 1 = one launch-thread per path). */
 int rmr_set_kernel(rmr_ctx* ctx, int kernel);
 /* envTex of skyColor (RM1:78-113, RM2:84-107; the reference loads veranda_1k.hdr through SOIL as

@@ -592,6 +592,7 @@ int ensure_jit(rmr_ctx* c, bool rays = false) {
     k.slots = facts.slots;
     k.park_t = facts.park_t();
     k.slot_t = facts.slot_t();
+    k.slot_t_small = facts.slot_t_small();
     c->jit_loaded.push_back(k);
     jk = k;
     ready = true;
@@ -1084,7 +1085,11 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
         }
         if (use_jit && jk.slots) {
             const int park = c->park_threshold > 0 ? c->park_threshold : jk.park_t;
-            P.shade_threshold = park | ((c->slot_threshold > 0 ? c->slot_threshold : jk.slot_t) << 8);
+            // the class's batch threshold by the launch's size (JitFacts::slot_t_small): claims per wave
+            const bool small = P.n_units < (uint64_t)gp.grid * (uint64_t)(jk.block / 64) * (uint64_t)jk.chunk *
+                                               (uint64_t)rmr::JitFacts::kSlotSmallClaims;
+            const int batch = c->slot_threshold > 0 ? c->slot_threshold : (small ? jk.slot_t_small : jk.slot_t);
+            P.shade_threshold = park | (batch << 8);
             P.refill_threshold = refill_for(c->refill_threshold, park);
         }
         if ((r = submit_launch(c, P, S, use_jit, gp.grid, rays ? c->d_rays : nullptr, !rl))) return r;
@@ -1197,8 +1202,8 @@ int rmr_create(rmr_ctx** out, int device) {
     c->own_stream = true;
     rmr_default_params(&c->params);
     if (hipMalloc((void**)&c->d_queue, rmr::kQueueBytes) != hipSuccess ||
-        hipMalloc((void**)&c->d_counters, 16 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(c->d_counters, 0, 16 * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc((void**)&c->d_counters, rmr::kCounterSlots * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(c->d_counters, 0, rmr::kCounterSlots * sizeof(unsigned long long)) != hipSuccess ||
         hipMemset(c->d_queue, 0, rmr::kQueueBytes) != hipSuccess) {   // then each fold zeroes it
         rmr_destroy(c);
         return RMR_E_HIP;
@@ -1614,6 +1619,17 @@ int rmr_get_counters(rmr_ctx* c, uint64_t out[16]) {
     return RMR_OK;
 }
 
+int rmr_get_counters_n(rmr_ctx* c, uint64_t* out, int n) {
+    if (!c || !out || n < 0 || n > rmr::kCounterSlots) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    int r = rmr_sync(c);
+    if (r) return r;
+    unsigned long long cnt[rmr::kCounterSlots];
+    HIPCHK(c, hipMemcpy(cnt, c->d_counters, (size_t)n * sizeof cnt[0], hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) out[i] = cnt[i];
+    return RMR_OK;
+}
+
 int rmr_reset_stats(rmr_ctx* c) {
     if (!c) return RMR_E_INVALID;
     RMR_FLUSH(c);
@@ -1622,7 +1638,7 @@ int rmr_reset_stats(rmr_ctx* c) {
     const double fpm = c->stats.flops_per_map;
     c->stats = rmr_stats{};
     c->stats.flops_per_map = fpm;
-    HIPCHK(c, hipMemset(c->d_counters, 0, 16 * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemset(c->d_counters, 0, rmr::kCounterSlots * sizeof(unsigned long long)));
     return RMR_OK;
 }
 

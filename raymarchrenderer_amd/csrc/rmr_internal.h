@@ -54,6 +54,27 @@ struct BvhNode {
 constexpr size_t kQueueBytes = 8192;
 constexpr int kQueueWordStride = 32;   // 32-bit words between two partition counters
 
+// The kernels' raw device counters (KParams::counters; rmr_get_counters_n): kCounterSlots 64-bit words.
+// [0..15] as rmr.h documents them (the flop-count and other diagnostic builds use 9..15 as well). From
+// 16 up every counter has a slot of its own:
+constexpr int kCounterSlots = 32;
+constexpr int kCntOverflow = 16;         // lane-slot kernels: events deposited into another lane's empty slot
+// RMR_PROFILE builds (rmr_trace.h trace_main), zero otherwise:
+constexpr int kCntProfClaim = 17;        // refill: cycles in work-queue claims
+constexpr int kCntProfRays = 18;         // refill: cycles in the chunk's primary rays
+constexpr int kCntProfUhits = 19;        // lane-slot kernels: hits the certificate did not cover
+constexpr int kCntProfUhitsCheap = 20;   //   those that end their path
+constexpr int kCntProfFullLanes = 21;    // cache kernels: lanes in the full map() batches
+constexpr int kCntProfOuter = 22;        // lane-slot kernels: outer-loop passes
+constexpr int kCntProfPark = 23;         //   park steps
+constexpr int kCntProfParkOvf = 24;      //   park steps with an overflow deposit
+constexpr int kCntProfLostFin = 25;      //   map-loop lane-iterations of lanes whose march ended (awaiting the park step)
+constexpr int kCntProfLostWait = 26;     //   map-loop lane-iterations of lanes waiting in registers on a full slot
+constexpr int kCntProfBatchEv = 27;      //   events in the shading batches (batches: counter 2)
+constexpr int kCntProfLostIdle = 28;     //   map-loop lane-iterations of idle lanes while the queue has work
+constexpr int kCntProfLostIdleExh = 29;  //   the same once the wave found the queue used up (the drain)
+constexpr int kCntProfReadyWait = 30;    //   ready rays waiting in a slot whose lane marches, summed over map-loop iterations
+
 struct KParams {
     // ---- scene tables (device pointers, read-only) ----
     const rmr_prim* prims;

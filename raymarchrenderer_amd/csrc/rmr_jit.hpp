@@ -43,6 +43,7 @@ struct JitKernel {
                                 // RMR_CHUNK; the nearest-primitive cache kernels: RMR_CHUNK_CACHE)
     bool slots = false;         // the lane-slot schedule (rmr_trace.h RMR_LANE_SLOTS)
     int park_t = 0, slot_t = 0; // its default thresholds (JitFacts)
+    int slot_t_small = 0;       // ... the batch threshold of launches under kSlotSmallClaims claims per wave
 };
 
 // What jit_source decided about the kernel class (the launch settings follow from these, not from
@@ -54,11 +55,22 @@ struct JitFacts {
     // the lane-slot schedule (rmr_trace.h RMR_LANE_SLOTS): the class can run it (RM1's certified
     // sphere/box kernels) / this source has it on
     bool slots_ok = false, slots = false;
+    bool overflow = false;   // ... with the park step's overflow deposit (rmr_trace.h RMR_SLOT_OVERFLOW)
     int chunk() const { return (cache || slots) ? 64 : 128; }   // rmr_trace.h RMR_CHUNK_CACHE / RMR_CHUNK_SLOTS / RMR_CHUNK
     // lane slots: finished marches per park step, slot events per shading batch (Cornell-5 1080p 64 spp:
     // flat over 8-10 / 28-40, +10% and more outside 6-12 / 24-48)
     int park_t() const { return 8; }
-    int slot_t() const { return 32; }
+    // With the overflow deposit a lane no longer waits on its own full slot, and the batch pays up to
+    // 48 events (same process, 64 spp: (8, 32) -1.9%, (8, 40) -2.9%, (8, 48) -3.3% against (8, 32) without
+    // it; at 56 the wave runs out of empty slots, +7.7%; profiles/slot_overflow_sweep.log)
+    int slot_t() const { return overflow ? 48 : 32; }
+    // Launches that give a wave fewer than kSlotSmallClaims work claims keep 32: the end of the launch,
+    // where batches fire only once no lane is active, is a larger share of them, and a larger batch makes
+    // it longer (same process, overflow on, (8, 32) / (8, 48) against the parent: 480x270 1 spp +0.6 / +4.5%,
+    // 640x360 4 spp -8.6 / -1.6%, 1080p 1 spp -9.6 / -6.3%, 4 spp -4.4 / -3.9%, 8 spp -5.1 / -4.8%, 16 spp
+    // -2.6 / -3.4%, 32 spp -2.0 / -3.1%, 64 spp -1.9 / -3.3%; profiles/slot_overflow_sweep.log)
+    int slot_t_small() const { return 32; }
+    static constexpr int kSlotSmallClaims = 64;
     // default shading batch: general maps without material programs, whose map() dwarfs the shading
     // (the Mandelbulb): 10 (C3: 8 / 12 within 0.6%, 6 / 16 +3%, profiles/r05_c3_shade_ab.log); node-program materials, the cache kernels and the certified
     // sphere/box kernels (their batches run the certified probes): 20; otherwise 16 (rmr_api.cpp)

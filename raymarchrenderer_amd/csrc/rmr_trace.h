@@ -27,6 +27,7 @@
 #endif
 #include "rmr_math.h"
 #include "rmr_internal.h"
+#include "rmr_slot_rule.h"
 
 namespace rmr {
 
@@ -2352,8 +2353,10 @@ RMR_D void cold_get(float (*s)[256], int t, Lane& L) {
 // rm1_after_material's ni stays 0; no RM2 / RM3 fields), inline maps (cw < 256).
 constexpr int kSlotWords = 17;
 // (BP, batch probes: an uncertified hit has no normal yet either, ctr = 0; words 3-5 stay unused)
+// (tu: the slot whose word 16 names the path — the lane's own; t differs from it where the event goes
+// into another lane's empty slot, RMR_SLOT_OVERFLOW. Word 16 of slot t stays its owner's.)
 template <bool BP = false>
-RMR_D void slot_put_event(float (*s)[256], int t, const Lane& L, V3 hp) {
+RMR_D void slot_put_event(float (*s)[256], int t, const Lane& L, V3 hp, int tu) {
     s[0][t] = hp.x; s[1][t] = hp.y; s[2][t] = hp.z;
     if constexpr (!BP) {
         if (L.ctr >= 0) { s[3][t] = L.nrm.x; s[4][t] = L.nrm.y; s[5][t] = L.nrm.z; }
@@ -2361,7 +2364,7 @@ RMR_D void slot_put_event(float (*s)[256], int t, const Lane& L, V3 hp) {
     s[6][t] = L.color.x; s[7][t] = L.color.y; s[8][t] = L.color.z;
     s[9][t] = L.rc;
     s[10][t] = L.gxt; s[11][t] = L.gyt;
-    s[12][t] = s[16][t];
+    s[12][t] = s[16][tu];
     // (ctr = -1 - cw of a certified hit, march_update PACKW; 6 after an uncertified hit's probes, 0
     // for an uncertified hit whose probes the batch runs)
     s[13][t] = __int_as_float((L.bounces << 9) | (L.ctr < 0 ? (((-1 - L.ctr) & 0xff) << 1) | 1 : 0));
@@ -2565,6 +2568,14 @@ static_assert(RMR_QUEUE_PARTS >= 1 && RMR_QUEUE_PARTS <= 64 && RMR_QUEUE_PARTS *
 #ifndef RMR_BATCH_PROBES
 #define RMR_BATCH_PROBES 0
 #endif
+// Overflow deposit (lane-slot kernels only; the hipRTC source asks for it with the lane slots, rmr_jit.cpp):
+// a lane whose march ended in a continuing hit while its own slot still holds an event puts the event
+// into an empty slot of the wave (rmr_slot_rule.h) and goes idle, instead of waiting in registers through
+// the next stretch of the map loop. The batch shades slot i in lane i, whoever produced the event; the
+// ready ray stays in that slot, so a path may change lanes. Nothing in a sample depends on its lane.
+#ifndef RMR_SLOT_OVERFLOW
+#define RMR_SLOT_OVERFLOW 0
+#endif
 // the primary ray's first march step with the chunk's rays (chunk_ray EYEC; lane-slot kernels only)
 #ifndef RMR_EYE_CHUNK
 #define RMR_EYE_CHUNK 1   // (0: as a march_update of the fresh lanes at every refill, A/B)
@@ -2594,13 +2605,14 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
     mbs.fin = false;
     // per-wave event counters, 32-bit (wave-uniform: SGPRs; 64-bit ones cost the cache kernels
     // scratch round trips), flushed to the 64-bit global counters before any can pass 2^31
-    WCount maps = 0, iters = 0, shades = 0, fulls = 0, shaded = 0, bmaps = 0;
+    WCount maps = 0, iters = 0, shades = 0, fulls = 0, shaded = 0, bmaps = 0, ovfs = 0;
     // lane slots: RM1 HO kernels with the certifying inline map, persistent (launched without
     // separateChannels and without an env map only: the host picks the code object, rmr_api.cpp)
     constexpr bool SLOTS = RMR_LANE_SLOTS && PERSIST && VAR == RMR_VARIANT_RM1 && CERT && MAP::kCert && !MAP::kCache &&
                            !MAP::kStepped && !RAYS;
     constexpr bool BP = SLOTS && RMR_BATCH_PROBES;   // uncertified hits' probes in the shading batch
     constexpr bool EYEC = SLOTS && RMR_EYE_CHUNK;    // the eye step with the chunk's rays
+    constexpr bool OVF = SLOTS && RMR_SLOT_OVERFLOW;   // events of lanes with a full slot into empty slots
     constexpr uint32_t CHUNK = MAP::kCache ? RMR_CHUNK_CACHE : (SLOTS ? RMR_CHUNK_SLOTS : RMR_CHUNK);
     const uint32_t n_units = (uint32_t)P.n_units;   // < 2^32 per launch (host chunking)
     // units per claim: the LDS ray buffer's CHUNK, or fewer for a small launch (the host's chunk_units)
@@ -2666,6 +2678,13 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
     uint64_t full_lanes = 0;           // cache kernels: lanes in the full map() batches
     uint64_t cyc_claim = 0, cyc_rays = 0;   // refill: work-queue claims (atomics), chunk primary rays
     uint64_t uhits = 0, uhits_cheap = 0;    // lane-slot kernels: uncertified hits, those ending their path
+    // lane-slot kernels: outer-loop passes, park steps, those with an overflow deposit; lane-iterations
+    // of the map loop spent by lanes whose march has ended (awaiting the park step) and by lanes that
+    // wait in registers on their full slot; events in the shading batches
+    uint64_t n_outer = 0, n_park = 0, n_park_ovf = 0, lost_fin = 0, lost_wait = 0, batch_ev = 0;
+    // ... by idle lanes (those of a wave whose queue is used up apart), and ready rays that wait in their
+    // slot while the slot's lane marches, per map-loop iteration
+    uint64_t lost_idle = 0, lost_idle_exh = 0, ready_wait = 0;
     const uint64_t c_begin = __builtin_amdgcn_s_memtime();
 #define RMR_STAMP(v) const uint64_t v = __builtin_amdgcn_s_memtime()
 #else
@@ -3025,7 +3044,18 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
             uint32_t lmaps = 0, liters = 0;
             // lane slots: PK more finished marches than the lanes that wait in registers for their slot
             const int TL = SLOTS ? __popcll(__ballot(is_shade(L.phase))) + PK : T;
+#ifdef RMR_PROFILE
+            const uint64_t wait0 = __ballot(is_shade(L.phase));   // (lane slots: they wait on a full slot)
+            uint64_t sm0 = wait0;
+#endif
             for (;;) {
+#ifdef RMR_PROFILE
+                lost_wait += (uint64_t)__popcll(wait0);
+                lost_fin += (uint64_t)__popcll(sm0 & ~wait0);
+                if (exhausted) lost_idle_exh += (uint64_t)__popcll(__ballot(L.phase == PH_IDLE));
+                else lost_idle += (uint64_t)__popcll(__ballot(L.phase == PH_IDLE));
+                if constexpr (SLOTS) ready_wait += (uint64_t)__popcll(__ballot(sst == 2));
+#endif
                 if (is_active(L.phase)) {
                     // (BP: every active lane marches; its point has no probe offset)
                     const V3 p = BP ? vfma(L.d, L.t, L.o) : RMR_MARCH_POINT(L);
@@ -3052,6 +3082,9 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                 liters++;
                 const uint64_t sm = __ballot(is_shade(L.phase));
                 am = __ballot(is_active(L.phase));
+#ifdef RMR_PROFILE
+                sm0 = sm;
+#endif
                 if (!am || __popcll(sm) >= TL) break;
             }
             maps += (WCount)__builtin_amdgcn_readfirstlane(lmaps);
@@ -3059,12 +3092,18 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
         }
         RMR_STAMP(c2);
         if constexpr (SLOTS) {
+#ifdef RMR_PROFILE
+            n_outer++;
+#endif
             for (;;) {
                 // (the lane's slot index from lane_now: a value kept across the loop would cost a register)
                 const int st = (wv << 6) + (int)lane_now();
                 // ---- park step: the lanes whose march ended ----
                 const bool sh = is_shade(L.phase);
                 if (__ballot(sh)) {
+#ifdef RMR_PROFILE
+                    n_park++;
+#endif
                     // events without shading work store their sample at once, with shade()'s own
                     // expressions (chan < 0, no env map): a miss (color x sky); a hit that ends its path
                     // — any material but a diffuse one (emission: color x c x gray1; none: color x 0), or
@@ -3119,7 +3158,7 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                             const bool swap = sst == 2;
                             SlotRay r{};
                             if (swap) r = slot_read_ray(s_slot, st);
-                            slot_put_event<BP>(s_slot, st, L, vfma(L.d, L.t, L.o));
+                            slot_put_event<BP>(s_slot, st, L, vfma(L.d, L.t, L.o), st);
                             L.phase = PH_IDLE;
                             if (swap) slot_start_ray(s_slot, st, L, r);
                             L.e = v3s(-0.0f);
@@ -3127,11 +3166,52 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                         }
                         nev += (uint32_t)__popcll(__ballot(park));
                     }
+                    // ---- overflow deposit (rmr_slot_rule.h): a lane that still holds a continuing hit
+                    // has an event in its own slot; the k-th such lane puts its event into the k-th slot
+                    // that is empty after the parks above and goes idle. Owners of the target slots
+                    // publish their lane by rank in s_tab (idle outside the batch). ----
+                    if constexpr (OVF) {
+                        const bool cand = is_shade(L.phase);   // (sst == 1: every other ended march parked above)
+                        const uint64_t cm = __ballot(cand);
+                        if (cm) {
+                            const bool free_ = sst == 0;
+                            const uint64_t em = __ballot(free_);
+                            if (em) {
+                                const int n = slot_deposits(cm, em);
+                                const int rk_e = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
+                                if (slot_in_step(free_, rk_e, n)) {
+                                    s_tab[wv][rk_e] = st & 63;
+                                    sst = 1;
+                                }
+                                __builtin_amdgcn_wave_barrier();
+                                const int rk_c = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u));
+                                const bool give = slot_in_step(cand, rk_c, n);
+#ifdef RMR_PROFILE
+                                uhits += (uint64_t)__popcll(__ballot(give && L.ctr >= 0));   // (consumed here)
+#endif
+                                if (give) {
+                                    const int tg = (wv << 6) + (s_tab[wv][rk_c] & 63);
+                                    slot_put_event<BP>(s_slot, tg, L, vfma(L.d, L.t, L.o), st);
+                                    L.phase = PH_IDLE;
+                                    L.e = v3s(-0.0f);
+                                }
+                                __builtin_amdgcn_wave_barrier();   // (s_tab is rewritten by the batch)
+                                nev += (uint32_t)n;
+                                ovfs += (WCount)n;
+#ifdef RMR_PROFILE
+                                n_park_ovf++;
+#endif
+                            }
+                        }
+                    }
                 }
                 // ---- batch: every slot event shaded at once; the marching state stays in registers ----
                 if (!(nev && ((int)nev >= T2 || __ballot(is_active(L.phase)) == 0))) break;
                 shades++;
                 shaded += (WCount)nev;
+#ifdef RMR_PROFILE
+                batch_ev += (uint64_t)nev;
+#endif
                 nev = 0;
                 const bool ev = sst == 1;
                 Lane E;
@@ -3243,8 +3323,10 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                 atomicAdd(P.counters + 8, (unsigned long long)shaded);   // lane-level shading events
                 // map() evaluations of the shading batches (certified getNormal probes; in [0] too)
                 if (CERT) atomicAdd(P.counters + 14, (unsigned long long)bmaps);
+                // events deposited into another lane's empty slot (RMR_SLOT_OVERFLOW)
+                if (OVF) atomicAdd(P.counters + kCntOverflow, (unsigned long long)ovfs);
             }
-            maps = iters = shades = fulls = shaded = bmaps = 0;
+            maps = iters = shades = fulls = shaded = bmaps = ovfs = 0;
         }
         if (last) break;
     }
@@ -3263,13 +3345,22 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
         atomicAdd(P.counters + 6, (unsigned long long)cyc[2]);
         if (MAP::kCache) {
             atomicAdd(P.counters + 9, (unsigned long long)cyc[3]);
-            atomicAdd(P.counters + 10, (unsigned long long)full_lanes);
+            atomicAdd(P.counters + kCntProfFullLanes, (unsigned long long)full_lanes);
         }
-        atomicAdd(P.counters + 11, (unsigned long long)cyc_claim);
-        atomicAdd(P.counters + 12, (unsigned long long)cyc_rays);
+        atomicAdd(P.counters + kCntProfClaim, (unsigned long long)cyc_claim);
+        atomicAdd(P.counters + kCntProfRays, (unsigned long long)cyc_rays);
         if (SLOTS) {
-            atomicAdd(P.counters + 13, (unsigned long long)uhits);
-            atomicAdd(P.counters + 15, (unsigned long long)uhits_cheap);
+            atomicAdd(P.counters + kCntProfUhits, (unsigned long long)uhits);
+            atomicAdd(P.counters + kCntProfUhitsCheap, (unsigned long long)uhits_cheap);
+            atomicAdd(P.counters + kCntProfOuter, (unsigned long long)n_outer);
+            atomicAdd(P.counters + kCntProfPark, (unsigned long long)n_park);
+            atomicAdd(P.counters + kCntProfParkOvf, (unsigned long long)n_park_ovf);
+            atomicAdd(P.counters + kCntProfLostFin, (unsigned long long)lost_fin);
+            atomicAdd(P.counters + kCntProfLostWait, (unsigned long long)lost_wait);
+            atomicAdd(P.counters + kCntProfBatchEv, (unsigned long long)batch_ev);
+            atomicAdd(P.counters + kCntProfLostIdle, (unsigned long long)lost_idle);
+            atomicAdd(P.counters + kCntProfLostIdleExh, (unsigned long long)lost_idle_exh);
+            atomicAdd(P.counters + kCntProfReadyWait, (unsigned long long)ready_wait);
         }
         atomicAdd(P.counters + 7, (unsigned long long)(__builtin_amdgcn_s_memtime() - c_begin));
 #endif

@@ -799,9 +799,10 @@ class Renderer:
         self._chk(self._L.rmr_reset_stats(self._ctx))
 
     def counters(self):
-        """The kernels' 16 raw device counters (rmr_get_counters; rmr_trace.h documents the slots)."""
-        raw = (C.c_uint64 * 16)()
-        self._chk(self._L.rmr_get_counters(self._ctx, raw))
+        """The kernels' 32 raw device counters (rmr_get_counters_n; rmr.h and rmr_internal.h document the
+        slots: 0-15 as ever, 16 the overflow deposits, 17-30 the profiling build's own)."""
+        raw = (C.c_uint64 * 32)()
+        self._chk(self._L.rmr_get_counters_n(self._ctx, raw, 32))
         return [int(v) for v in raw]
 
 

@@ -11,6 +11,7 @@ VARIANT = [LABEL=]SPEC[;SPEC...], SPEC one of
     cull:N          rmr_set_culling flags
     shade:T         rmr_set_tuning shading threshold (T + 256 R: refill threshold R)
     slots:off | slots:P,T2   lane-slot kernels: the schedule off, or its park / batch thresholds
+    overflow:on | overflow:off   lane-slot kernels: the park step's overflow deposit (RMR_JIT_OVERFLOW)
 e.g.  python tools/abrun.py --cases c2,c4 base="lib:tools/librmr_base.so" new="lib:raymarchrenderer_amd/librmr_diag.so"
       python tools/abrun.py --cases glass,default w6="opts:-DRMR_PROG_WAVES=6" w7="opts:-DRMR_PROG_WAVES=7" def=""
 
@@ -70,6 +71,10 @@ def parse_variant(text):
         elif kind == "slots":   # rmr_set_tuning's upper bits (rmr.h)
             p, _, t2 = val.partition(",")
             v["shade"] = (v["shade"] or 0) | 1 << 23 | ((127 << 16) if val == "off" else (int(p) << 16 | int(t2 or 0) << 24))
+        elif kind == "overflow":   # rmr_jit.cpp: part of the generated source
+            if val not in ("on", "off"):
+                raise SystemExit("overflow:on or overflow:off, not %r" % item)
+            v["env"]["RMR_JIT_OVERFLOW"] = "1" if val == "on" else "0"
         else:
             raise SystemExit("unknown variant spec %r" % item)
     return v
@@ -93,7 +98,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--W", type=int, default=0)
     ap.add_argument("--H", type=int, default=0)
-    ap.add_argument("--raw", action="store_true", help="also print the 16 raw kernel counters (diagnostic builds)")
+    ap.add_argument("--raw", action="store_true", help="also print the 32 raw kernel counters (diagnostic builds)")
     a = ap.parse_args()
     vs = [parse_variant(t) for t in a.variants]
     keys = sorted({k for v in vs for k in v["env"]})
@@ -139,20 +144,32 @@ def main():
                 "map_evals": int(st[i].map_evals), "map_iters": int(st[i].map_iters),
                 "shade_batches": int(st[i].shade_batches),
                 "lanes_per_batch": round(cnt[i][8] / max(1, st[i].shade_batches), 2),
+                "overflow_deposits": cnt[i][16],
                 "bitwise_equal_to_first": bool(np.array_equal(img[i].view(np.uint32), img[0].view(np.uint32))),
             }
             if a.raw:
                 out[v["label"]]["raw"] = cnt[i]
             if "-DRMR_PROFILE" in v["env"].get("RMR_JIT_OPTS", ""):
-                # section cycles of the profiling build (rmr_trace.h RMR_PROFILE: counters 4-7, 9),
+                # section cycles of the profiling build (rmr_trace.h RMR_PROFILE: counters 4-7, 9, and its
+                # own slots from 17 up, rmr_internal.h kCntProf*),
                 # as fractions of the waves' cycles (the s_memtime stamps themselves cost ~10%)
                 c, tot = cnt[i], max(1, cnt[i][7])
                 out[v["label"]]["sections"] = {"refill": round(c[4] / tot, 4), "map_loop": round(c[5] / tot, 4),
                                                "shade": round(c[6] / tot, 4), "cache_full_maps": round(c[9] / tot, 4),
                                                # parts of refill: work-queue claims, the chunk's primary rays
-                                               "refill_claims": round(c[11] / tot, 4), "refill_rays": round(c[12] / tot, 4)}
-                if c[3]:   # cache kernels: lanes per full map() batch (counter 10 of the profiling build)
-                    out[v["label"]]["lanes_per_full_batch"] = round(c[10] / c[3], 2)
+                                               "refill_claims": round(c[17] / tot, 4), "refill_rays": round(c[18] / tot, 4)}
+                if c[3]:   # cache kernels: lanes per full map() batch
+                    out[v["label"]]["lanes_per_full_batch"] = round(c[21] / c[3], 2)
+                if c[22]:   # lane-slot kernels: the schedule's own counts, per map-loop iteration / per batch
+                    it, nb = max(1, c[1]), max(1, c[2])
+                    out[v["label"]]["schedule"] = {
+                        "outer_passes": c[22], "park_steps": c[23], "park_steps_overflow": c[24], "batches": c[2],
+                        "events_per_batch": round(c[27] / nb, 2),
+                        "lanes_per_map_iter": round((c[0] - c[14]) / it, 2),
+                        "lanes_awaiting_park_per_iter": round(c[25] / it, 3),
+                        "lanes_waiting_full_slot_per_iter": round(c[26] / it, 3),
+                        "lanes_idle_per_iter": round(c[28] / it, 3), "lanes_idle_drain_per_iter": round(c[29] / it, 3),
+                        "ready_rays_waiting_per_iter": round(c[30] / it, 3)}
         print(json.dumps(out), flush=True)
     for r in ctx:
         r.close()
