@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <initializer_list>
 #include <new>
 #include <sstream>
 #include <string>
@@ -32,6 +33,7 @@
 #include "temporal.hpp"
 #include "tonemap.hpp"
 #include "bloom.hpp"
+#include "stage_state.hpp"
 
 namespace rmr {
 hipError_t launch_trace(const KParams& P, int variant, int np, bool prog, bool persistent, int grid, hipStream_t s);
@@ -125,19 +127,17 @@ struct rmr_ctx {
     void* d_qout = nullptr;
     size_t qin_cap = 0, qout_cap = 0;     // bytes
     int query_grid = 0;                   // rmr_set_query_grid: 0 = one thread per ray / point
+    // which of the output stages' images below are valid: the one place that says so (stage_state.hpp)
+    rmr::StageState st;
     // first-hit guides and the preview denoiser (rmr_render_guides / rmr_denoise): three guide planes and
     // two filter images of W x H float4, allocated at first use, freed at rmr_reload / rmr_destroy
     float4* d_guide[3] = {nullptr, nullptr, nullptr};
     float4* d_dn[2] = {nullptr, nullptr};
-    bool guides_valid = false;            // one rmr_render_guides covered the image with the current view / scene / params
-    int dn_result = -1;                   // d_dn[] index of the valid denoised image, -1: none
     int output_source = RMR_OUTPUT_ACCUM; // what rmr_save_bmp / rmr_display* read
     int dn_tiled_steps = kDenoiseTiledSteps;   // bit i: pass i (step 2^i, i < 2) runs the LDS-tiled form
     // variance-guided mode (rmr_denoise_variance): the seed plane and two filter planes of
     // W x H floats, allocated at the first call, freed with the guide planes
     float* d_var[3] = {nullptr, nullptr, nullptr};
-    bool dn_guided = false;               // the valid denoised image is rmr_denoise_variance's
-    int var_result = 0;                   // d_var[] index of its filtered variance (0: the seed itself)
     int dnv_tiled_steps = kDenoiseVarTiledSteps;
     // temporal reprojection (rmr_temporal_accumulate): two pairs of history colour (W x H
     // float4) and count (W x H float) that the steps alternate between, and the history's HIT and NORMAL
@@ -145,7 +145,6 @@ struct rmr_ctx {
     float4* d_tcol[2] = {nullptr, nullptr};
     float* d_tn[2] = {nullptr, nullptr};
     float4* d_tguide[2] = {nullptr, nullptr};
-    int t_cur = -1;                       // the pair that holds the history (= the temporal image), -1: none
     float t_view[15];                     // the view the history was made with
     bool t_keep = false;                  // diagnostic library (tools/temporal_time.py): a step leaves the history as it is
     // tone mapping and auto-exposure (rmr_tonemap): the tonemapped plane (W x H float4),
@@ -156,8 +155,6 @@ struct rmr_ctx {
     rmr::ToneState* d_tm_state = nullptr;
     double* d_tm_lc = nullptr;
     double tm_lc[255];                    // the table's host copy (the source of its queued upload)
-    bool tm_valid = false;                // d_tm holds the image of tm_source as it is now
-    int tm_source = RMR_OUTPUT_ACCUM;
     int tm_used = 0;                      // what the last rmr_tonemap used: 0 none, 1 tm_ev / tm_scale, 2 the state
     double tm_ev = 0.0;
     float tm_scale = 1.0f;
@@ -168,8 +165,6 @@ struct rmr_ctx {
     // freed at rmr_reload / rmr_destroy
     float4* d_bl = nullptr;
     float4* d_bl_pyr = nullptr;
-    bool bl_valid = false;                // d_bl holds the bloom of bl_source as it is now
-    int bl_source = RMR_OUTPUT_ACCUM;
     int bl_tail = rmr::kBloomTailDefault; // the most pixels the tail kernel's levels hold together (diagnostic library: 0 = off)
     // per-tile error estimate and adaptive sampling (rmr_estimate.hip, adaptive.hpp)
     bool est_on = false;                  // every launch's fold is k_fold_half (rmr_set_error_estimate)
@@ -318,6 +313,63 @@ int dev_upload(rmr_ctx* c, T** dst, const T* src, size_t n) {
     return RMR_OK;
 }
 
+// All of a stage's device buffers or none: on a failure what was allocated is freed, every pointer of the
+// list is null again and the error is RMR_E_NOMEM with `msg`.
+struct Buf {
+    void** p;
+    size_t bytes;
+    template <class T>
+    Buf(T** q, size_t b = 0) : p((void**)q), bytes(b) {}
+};
+int alloc_all(rmr_ctx* c, std::initializer_list<Buf> list, const char* msg) {
+    for (const Buf* a = list.begin(); a != list.end(); ++a) {
+        if (hipMalloc(a->p, a->bytes) == hipSuccess) continue;
+        (void)hipGetLastError();
+        *a->p = nullptr;
+        for (const Buf* k = list.begin(); k != a; ++k) { (void)hipFree(*k->p); *k->p = nullptr; }
+        return fail(c, RMR_E_NOMEM, msg);
+    }
+    return RMR_OK;
+}
+void free_all(std::initializer_list<Buf> list) {
+    for (const Buf& b : list) { if (*b.p) (void)hipFree(*b.p); *b.p = nullptr; }
+}
+
+// The end of every rmr_read_*: `bytes` from the device to the caller's buffer on the context's stream, done
+// when the call returns.
+int read_back(rmr_ctx* c, void* dst, const void* src, size_t bytes) {
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+// Device scratch of one call of a host-image entry point (rmr_*_images): buffers, copies and launches on
+// one stream until the first error, which it keeps and after which every request does nothing; done() waits
+// for the stream whatever happened; the buffers go with the object.
+struct Scratch {
+    hipStream_t s;
+    hipError_t e = hipSuccess;
+    std::vector<void*> bufs;
+    explicit Scratch(hipStream_t stream) : s(stream) {}
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { for (void* b : bufs) (void)hipFree(b); }
+    template <class T>
+    T* get(size_t bytes) {
+        void* b = nullptr;
+        if (e == hipSuccess && (e = hipMalloc(&b, bytes)) == hipSuccess) bufs.push_back(b);
+        return (T*)b;
+    }
+    void up(void* dst, const void* src, size_t bytes) { if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s); }
+    void down(void* dst, const void* src, size_t bytes) { if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s); }
+    template <class F>
+    void run(F launch) { if (e == hipSuccess) e = launch(); }
+    hipError_t done() {
+        const hipError_t es = hipStreamSynchronize(s);
+        return e == hipSuccess ? es : e;
+    }
+};
+
 int alloc_accum(rmr_ctx* c) {
     if (!c->accum_external && c->d_accum) { (void)hipFree(c->d_accum); c->d_accum = nullptr; }
     c->accum_external = false;
@@ -342,51 +394,35 @@ int free_slots(rmr_ctx* c);
 
 // Release the guide planes and the filter images (the caller has synced the context's stream).
 void free_guides(rmr_ctx* c) {
-    for (float4*& b : c->d_guide) { if (b) (void)hipFree(b); b = nullptr; }
-    for (float4*& b : c->d_dn) { if (b) (void)hipFree(b); b = nullptr; }
-    for (float*& b : c->d_var) { if (b) (void)hipFree(b); b = nullptr; }
-    c->guides_valid = false;
-    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
+    free_all({&c->d_guide[0], &c->d_guide[1], &c->d_guide[2], &c->d_dn[0], &c->d_dn[1],
+              &c->d_var[0], &c->d_var[1], &c->d_var[2]});
+    c->st.guides_freed();
 }
 
 // Release the temporal stage's planes (the caller has synced the context's stream).
 void free_temporal(rmr_ctx* c) {
-    for (float4*& b : c->d_tcol) { if (b) (void)hipFree(b); b = nullptr; }
-    for (float*& b : c->d_tn) { if (b) (void)hipFree(b); b = nullptr; }
-    for (float4*& b : c->d_tguide) { if (b) (void)hipFree(b); b = nullptr; }
-    c->t_cur = -1;
+    free_all({&c->d_tcol[0], &c->d_tcol[1], &c->d_tn[0], &c->d_tn[1],
+              &c->d_tguide[0], &c->d_tguide[1]});
+    c->st.temporal_reset();
 }
 
 // Release the tone-mapping stage's buffers, the adaptation state with them (the caller has synced the
 // context's stream).
 void free_tonemap(rmr_ctx* c) {
-    if (c->d_tm) (void)hipFree(c->d_tm);
-    if (c->d_tm_slab) (void)hipFree(c->d_tm_slab);
-    if (c->d_tm_state) (void)hipFree(c->d_tm_state);
-    if (c->d_tm_lc) (void)hipFree(c->d_tm_lc);
-    c->d_tm = nullptr;
-    c->d_tm_slab = nullptr;
-    c->d_tm_state = nullptr;
-    c->d_tm_lc = nullptr;
-    c->tm_valid = false;
+    free_all({&c->d_tm, &c->d_tm_slab, &c->d_tm_state, &c->d_tm_lc});
+    c->st.tonemap_begin();
     c->tm_used = 0;
 }
 
 // Release the bloom stage's planes (the caller has synced the context's stream).
 void free_bloom(rmr_ctx* c) {
-    if (c->d_bl) (void)hipFree(c->d_bl);
-    if (c->d_bl_pyr) (void)hipFree(c->d_bl_pyr);
-    c->d_bl = nullptr;
-    c->d_bl_pyr = nullptr;
-    c->bl_valid = false;
+    free_all({&c->d_bl, &c->d_bl_pyr});
+    c->st.bloom_reset();
 }
 
 // Release the half image and the tile-error map (the caller has synced the context's stream).
 void free_estimate(rmr_ctx* c) {
-    if (c->d_half) (void)hipFree(c->d_half);
-    if (c->d_tile_err) (void)hipFree(c->d_tile_err);
-    c->d_half = nullptr;
-    c->d_tile_err = nullptr;
+    free_all({&c->d_half, &c->d_tile_err});
     c->est_valid = false;
 }
 
@@ -397,14 +433,14 @@ int enable_estimate(rmr_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->d_half) {
         const size_t tiles = (size_t)((c->W + 7) / 8) * ((c->H + 7) / 8);
-        if (hipMalloc((void**)&c->d_half, (size_t)c->W * c->H * sizeof(float4)) != hipSuccess ||
-            hipMalloc((void**)&c->d_tile_err, tiles * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            free_estimate(c);
-            c->est_on = false;
-            return fail(c, RMR_E_NOMEM, "cannot allocate the half image (W x H x 16 bytes)");
-        }
+        const int r = alloc_all(c, {{&c->d_half, (size_t)c->W * c->H * sizeof(float4)},
+                                    {&c->d_tile_err, tiles * sizeof(float)}},
+                                "cannot allocate the half image (W x H x 16 bytes)");
         c->est_valid = false;
+        if (r) {
+            c->est_on = false;
+            return r;
+        }
     }
     c->est_on = true;
     if (c->est_valid) return RMR_OK;
@@ -502,9 +538,7 @@ int upload_scene(rmr_ctx* c) {
     a.grid.list = {};
     c->esc_infl_dev = -1.0;
     c->scene_kp = scene_params(c);
-    c->guides_valid = false;   // (every scene load comes through here)
-    c->t_cur = -1;             // the temporal history is of the old scene
-    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
+    c->st.scene_loaded();   // (every scene load comes through here)
     c->scene_loaded = true;
     c->jit_ready = false;
     c->jit_rays_ready = false;
@@ -1001,7 +1035,7 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
     }
     const TileXY* d_tiles = nullptr;
     if (!rl) {
-        c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;   // the accumulator changes: the denoised image is of the old one
+        c->st.accum_changed();   // the denoised image is of the old one
         c->rendered = true;
         if ((r = tile_list(c, tiles, &d_tiles))) return r;
     }
@@ -1107,27 +1141,30 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
 
 using rmr::rect_tiles;
 
+// The device image of a source StageState::readable found valid, in buffer i.
+const float4* source_image(const rmr_ctx* c, int source, int i) {
+    switch (source) {
+    case RMR_OUTPUT_DENOISED: return c->d_dn[i];
+    case RMR_OUTPUT_TEMPORAL: return c->d_tcol[i];
+    case RMR_OUTPUT_TONEMAPPED: return c->d_tm;
+    case RMR_OUTPUT_BLOOM: return c->d_bl;
+    default: return c->d_accum;
+    }
+}
+// The words the refusals of a source that is not valid are made of: the image's name and the call that makes it.
+const char* const kSourceName[5] = {"", "denoised", "temporal", "tonemapped", "bloom"};
+const char* const kSourceCall[5] = {"", "rmr_denoise", "rmr_temporal_accumulate", "rmr_tonemap", "rmr_bloom"};
+int no_valid(rmr_ctx* c, int source) {
+    return fail(c, RMR_E_STATE, std::string("no valid ") + kSourceName[source] + " image (call " + kSourceCall[source] + ")");
+}
+
 // The image rmr_save_bmp / rmr_display* read (rmr_set_output_source).
 int output_image(rmr_ctx* c, const char* who, const float4** out) {
-    if (c->output_source == RMR_OUTPUT_DENOISED) {
-        if (c->dn_result < 0)
-            return fail(c, RMR_E_STATE, std::string(who) + ": output source is the denoised image, but none is valid (call rmr_denoise)");
-        *out = c->d_dn[c->dn_result];
-    } else if (c->output_source == RMR_OUTPUT_TEMPORAL) {
-        if (c->t_cur < 0)
-            return fail(c, RMR_E_STATE, std::string(who) + ": output source is the temporal image, but none is valid (call rmr_temporal_accumulate)");
-        *out = c->d_tcol[c->t_cur];
-    } else if (c->output_source == RMR_OUTPUT_TONEMAPPED) {
-        if (!c->tm_valid)
-            return fail(c, RMR_E_STATE, std::string(who) + ": output source is the tonemapped image, but none is valid (call rmr_tonemap)");
-        *out = c->d_tm;
-    } else if (c->output_source == RMR_OUTPUT_BLOOM) {
-        if (!c->bl_valid)
-            return fail(c, RMR_E_STATE, std::string(who) + ": output source is the bloom image, but none is valid (call rmr_bloom)");
-        *out = c->d_bl;
-    } else {
-        *out = c->d_accum;
-    }
+    const int src = c->output_source, i = c->st.readable(src);
+    if (i < 0)
+        return fail(c, RMR_E_STATE, std::string(who) + ": output source is the " + kSourceName[src] + " image, but none is valid (call " +
+                                        kSourceCall[src] + ")");
+    *out = source_image(c, src, i);
     return RMR_OK;
 }
 
@@ -1151,6 +1188,44 @@ int flush_calls(rmr_ctx* c) {
     }
     return RMR_OK;
 }
+
+// The *_device_ptr getters' flush: false when the deferred calls could not be launched (the getter returns null).
+bool flushed(rmr_ctx* c) { return c->deferred.empty() || flush_calls(c) == RMR_OK; }
+
+#if RMR_DIAG
+// Diagnostic library only (rmr_diag_tonemap_time, rmr_diag_bloom_time):
+// *ms = the GPU's time per round of n back-to-back rounds on the context's stream, between two events. So that
+// the time is the GPU's and not the host's enqueue rate, the stream is first kept busy (k_lum_hist over the
+// accumulator, then 32 k_meter launches, about 0.9 ms; fold and run_meter: their arguments) while the host
+// queues the first event, the rounds and the second event behind it; n <= 64 keeps the host ahead. The tone
+// stage's buffers are there (ensure_tonemap). Synchronises.
+template <class Round>
+int timed_rounds(rmr_ctx* c, bool fold, bool run_meter, int n, float* ms, Round round) {
+    const size_t px = (size_t)c->W * c->H;
+    const int blocks = rmr::lum_hist_blocks(px);
+    rmr_tonemap_params tq;
+    rmr_default_tonemap_params(&tq);
+    const rmr::ToneMeter M = rmr::tonemap_meter(tq);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    HIPCHK(c, hipEventCreate(&ev[0]));
+    hipError_t e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = rmr::launch_lum_hist(c->d_accum, px, c->d_tm_slab, blocks, fold, c->stream);
+    for (int i = 0; i < 32 && e == hipSuccess; i++)
+        e = rmr::launch_meter(c->d_tm_slab, blocks, c->d_tm_state, c->d_tm_lc, M, run_meter, c->stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
+    for (int i = 0; i < n && e == hipSuccess; i++) e = round();
+    if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = es;
+    float t = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&t, ev[0], ev[1]);
+    (void)hipEventDestroy(ev[0]);
+    if (ev[1]) (void)hipEventDestroy(ev[1]);
+    HIPCHK(c, e);
+    *ms = t / (float)n;
+    return RMR_OK;
+}
+#endif
 
 }  // namespace
 
@@ -1250,8 +1325,7 @@ void rmr_destroy(rmr_ctx* c) {
     free_temporal(c);
     free_tonemap(c);
     free_bloom(c);
-    if (c->d_half) (void)hipFree(c->d_half);
-    if (c->d_tile_err) (void)hipFree(c->d_tile_err);
+    free_estimate(c);
     if (c->d_accum && !c->accum_external) (void)hipFree(c->d_accum);
     for (auto& k : c->jit_loaded)
         if (k.module) (void)hipModuleUnload(k.module);
@@ -1304,8 +1378,7 @@ int rmr_set_params(rmr_ctx* c, const rmr_params* p) {
     RMR_FLUSH(c);
     if (p->max_steps < 0 || p->max_bounces < 0 || !(p->max_dist > 0.0f)) return fail(c, RMR_E_INVALID, "bad params");
     c->params = *p;
-    c->guides_valid = false;
-    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
+    c->st.inputs_changed();
     return RMR_OK;
 }
 
@@ -1324,8 +1397,7 @@ int rmr_set_view(rmr_ctx* c, const float eye[3], const float r00[3], const float
         c->view[9 + i] = r10[i]; c->view[12 + i] = r11[i];
     }
     c->view_set = true;
-    c->guides_valid = false;
-    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
+    c->st.inputs_changed();
     return RMR_OK;
 }
 
@@ -1412,7 +1484,7 @@ int rmr_render(rmr_ctx* c, float time, float min_x, float min_y, float max_x, fl
     }
     // deferred (rmr_set_call_batching): the errors the launch would give now come at the call
     if (const int r = launch_precheck(c)) return r;
-    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
+    c->st.accum_changed();
     c->rendered = true;
     rmr::DeferredCall* same = nullptr;
     bool overlap = false;
@@ -1483,9 +1555,7 @@ int rmr_read_accum(rmr_ctx* c, float* rgba, size_t bytes) {
     RMR_FLUSH(c);
     const size_t need = (size_t)c->W * c->H * sizeof(float4);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
-    HIPCHK(c, hipMemcpyAsync(rgba, c->d_accum, need, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RMR_OK;
+    return read_back(c, rgba, c->d_accum, need);
 }
 
 int rmr_write_accum(rmr_ctx* c, const float* rgba, size_t bytes) {
@@ -1493,7 +1563,7 @@ int rmr_write_accum(rmr_ctx* c, const float* rgba, size_t bytes) {
     RMR_FLUSH(c);
     const size_t need = (size_t)c->W * c->H * sizeof(float4);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
-    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
+    c->st.accum_changed();
     c->rendered = true;    // (the accumulator has contents the half image knows nothing of)
     c->est_valid = false;
     HIPCHK(c, hipMemcpyAsync(c->d_accum, rgba, need, hipMemcpyHostToDevice, c->stream));
@@ -1503,7 +1573,7 @@ int rmr_write_accum(rmr_ctx* c, const float* rgba, size_t bytes) {
 
 void* rmr_accum_device_ptr(rmr_ctx* c) {
     if (!c) return nullptr;
-    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;   // the pointer's contents include them
+    if (!flushed(c)) return nullptr;   // the pointer's contents include them
     return (void*)c->d_accum;
 }
 
@@ -1518,7 +1588,7 @@ int rmr_bind_accum(rmr_ctx* c, void* ptr, size_t bytes) {
     // (an external buffer is only swapped: launches already queued keep the pointer they captured)
     c->d_accum = (float4*)ptr;
     c->accum_external = true;
-    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
+    c->st.accum_changed();
     c->est_valid = false;
     return RMR_OK;
 }
@@ -1530,8 +1600,7 @@ int rmr_save_bmp(rmr_ctx* c, const char* path) {
     const float4* src = nullptr;
     int r = output_image(c, "rmr_save_bmp", &src);
     if (r) return r;
-    HIPCHK(c, hipMemcpyAsync(host.data(), src, host.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((r = read_back(c, host.data(), src, host.size() * sizeof(float)))) return r;
     r = rmr_encode_bmp(host.data(), c->W, c->H, path);
     if (r) return fail(c, r, std::string("cannot write ") + path);
     return RMR_OK;
@@ -2126,19 +2195,11 @@ namespace {
 int ensure_guides(rmr_ctx* c) {
     if (c->d_guide[0]) return RMR_OK;
     const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
-    float4* b[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i < 5; i++) {
-        if (hipMalloc((void**)&b[i], bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            for (int k = 0; k < i; k++) (void)hipFree(b[k]);
-            return fail(c, RMR_E_NOMEM, "cannot allocate the guide planes and filter images (5 x W x H x 16 bytes)");
-        }
-    }
-    for (int i = 0; i < 3; i++) c->d_guide[i] = b[i];
-    c->d_dn[0] = b[3];
-    c->d_dn[1] = b[4];
-    c->guides_valid = false;
-    c->dn_result = -1;
+    if (const int r = alloc_all(c, {{&c->d_guide[0], bytes}, {&c->d_guide[1], bytes}, {&c->d_guide[2], bytes},
+                                    {&c->d_dn[0], bytes}, {&c->d_dn[1], bytes}},
+                                "cannot allocate the guide planes and filter images (5 x W x H x 16 bytes)"))
+        return r;
+    c->st.guides_allocated();
     for (int i = 0; i < 3; i++) HIPCHK(c, hipMemsetAsync(c->d_guide[i], 0, bytes, c->stream));
     return RMR_OK;
 }
@@ -2157,7 +2218,7 @@ int render_guides(rmr_ctx* c, int x0, int y0, int x1, int y1) {
     P.x0 = x0; P.y0 = y0; P.x1 = x1; P.y1 = y1;
     HIPCHK(c, rmr::launch_guides(P, c->accel.map_np, c->d_guide[RMR_GUIDE_RAY], c->d_guide[RMR_GUIDE_HIT],
                                  c->d_guide[RMR_GUIDE_NORMAL], c->stream));
-    if (x0 == 0 && y0 == 0 && x1 == c->W && y1 == c->H) c->guides_valid = true;
+    if (x0 == 0 && y0 == 0 && x1 == c->W && y1 == c->H) c->st.guides_rendered();
     return RMR_OK;
 }
 
@@ -2190,14 +2251,12 @@ int rmr_read_guide(rmr_ctx* c, int plane, float* rgba, size_t bytes) {
     const size_t need = (size_t)c->W * c->H * sizeof(float4);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
     if (!c->d_guide[plane]) return fail(c, RMR_E_STATE, "no guides rendered (call rmr_render_guides)");
-    HIPCHK(c, hipMemcpyAsync(rgba, c->d_guide[plane], need, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RMR_OK;
+    return read_back(c, rgba, c->d_guide[plane], need);
 }
 
 void* rmr_guide_device_ptr(rmr_ctx* c, int plane) {
     if (!c || plane < RMR_GUIDE_RAY || plane > RMR_GUIDE_NORMAL) return nullptr;
-    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
+    if (!flushed(c)) return nullptr;
     if (hipSetDevice(c->device) != hipSuccess || ensure_guides(c) != RMR_OK) return nullptr;
     return (void*)c->d_guide[plane];
 }
@@ -2211,14 +2270,13 @@ int rmr_denoise(rmr_ctx* c, const rmr_denoise_params* p) {
     if (!denoise_params_ok(q))
         return fail(c, RMR_E_INVALID, "bad denoise params (iterations 0..8, normal_pow2 0..7, sigma_z finite > 0, sigma_c finite >= 0)");
     int r;
-    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
-    c->dn_guided = false;
-    if (!c->guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
+    c->st.denoise_begin();
+    if (!c->st.guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->W * c->H * sizeof(float4);
     if (q.iterations == 0) {
         HIPCHK(c, hipMemcpyAsync(c->d_dn[0], c->d_accum, bytes, hipMemcpyDeviceToDevice, c->stream));
-        c->dn_result = 0;
+        c->st.denoise_queued(0);
         return RMR_OK;
     }
     rmr::DenoisePass A{};
@@ -2237,7 +2295,7 @@ int rmr_denoise(rmr_ctx* c, const rmr_denoise_params* p) {
         A.inv_sigma_c2 = q.sigma_c > 0.0f ? (float)std::min(1.0 / (sc * sc), (double)FLT_MAX) : 0.0f;
         HIPCHK(c, rmr::launch_atrous(A, i < 2 && ((c->dn_tiled_steps >> i) & 1), c->stream));
     }
-    c->dn_result = (q.iterations - 1) & 1;
+    c->st.denoise_queued((q.iterations - 1) & 1);
     return RMR_OK;
 }
 
@@ -2246,31 +2304,26 @@ int rmr_read_denoised(rmr_ctx* c, float* rgba, size_t bytes) {
     RMR_FLUSH(c);
     const size_t need = (size_t)c->W * c->H * sizeof(float4);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
-    if (c->dn_result < 0) return fail(c, RMR_E_STATE, "no valid denoised image (call rmr_denoise)");
-    HIPCHK(c, hipMemcpyAsync(rgba, c->d_dn[c->dn_result], need, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RMR_OK;
+    const int i = c->st.readable(RMR_OUTPUT_DENOISED);
+    if (i < 0) return no_valid(c, RMR_OUTPUT_DENOISED);
+    return read_back(c, rgba, c->d_dn[i], need);
 }
 
 void* rmr_denoised_device_ptr(rmr_ctx* c) {
     if (!c) return nullptr;
-    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
-    return c->dn_result < 0 ? nullptr : (void*)c->d_dn[c->dn_result];
+    if (!flushed(c)) return nullptr;
+    const int i = c->st.readable(RMR_OUTPUT_DENOISED);
+    return i < 0 ? nullptr : (void*)c->d_dn[i];
 }
 
 int rmr_set_output_source(rmr_ctx* c, int source) {
     if (!c) return RMR_E_INVALID;
     RMR_FLUSH(c);
-    if (source != RMR_OUTPUT_ACCUM && source != RMR_OUTPUT_DENOISED && source != RMR_OUTPUT_TEMPORAL &&
-        source != RMR_OUTPUT_TONEMAPPED && source != RMR_OUTPUT_BLOOM)
-        return fail(c, RMR_E_INVALID, "bad output source");
-    // (refused, the source unchanged, while there is no temporal image to read)
-    if (source == RMR_OUTPUT_TEMPORAL && c->t_cur < 0)
-        return fail(c, RMR_E_STATE, "no valid temporal image (call rmr_temporal_accumulate)");
-    if (source == RMR_OUTPUT_TONEMAPPED && !c->tm_valid)
-        return fail(c, RMR_E_STATE, "no valid tonemapped image (call rmr_tonemap)");
-    if (source == RMR_OUTPUT_BLOOM && !c->bl_valid)
-        return fail(c, RMR_E_STATE, "no valid bloom image (call rmr_bloom)");
+    const int i = c->st.readable(source);
+    if (i == rmr::StageState::kNoSource) return fail(c, RMR_E_INVALID, "bad output source");
+    // (refused, the source unchanged, while there is no temporal, tonemapped or bloom image to read; the denoised
+    // image may be selected ahead of the rmr_denoise that makes it)
+    if (i < 0 && source != RMR_OUTPUT_DENOISED) return no_valid(c, source);
     c->output_source = source;
     return RMR_OK;
 }
@@ -2284,9 +2337,7 @@ int tile_error_host(rmr_ctx* c, float offset, float* out) {
     const size_t tiles = (size_t)((c->W + 7) / 8) * ((c->H + 7) / 8);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, rmr::launch_tile_error(c->d_accum, c->d_half, c->W, c->H, offset, c->d_tile_err, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_tile_err, tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RMR_OK;
+    return read_back(c, out, c->d_tile_err, tiles * sizeof(float));
 }
 }  // namespace
 
@@ -2307,14 +2358,12 @@ int rmr_read_half_accum(rmr_ctx* c, float* rgba, size_t bytes) {
     const size_t need = (size_t)c->W * c->H * sizeof(float4);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
     if (!c->est_on || !c->d_half) return fail(c, RMR_E_STATE, "the error estimate is off (call rmr_set_error_estimate)");
-    HIPCHK(c, hipMemcpyAsync(rgba, c->d_half, need, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RMR_OK;
+    return read_back(c, rgba, c->d_half, need);
 }
 
 void* rmr_half_device_ptr(rmr_ctx* c) {
     if (!c) return nullptr;
-    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
+    if (!flushed(c)) return nullptr;
     return c->est_on ? (void*)c->d_half : nullptr;
 }
 
@@ -2337,20 +2386,17 @@ int rmr_tile_error_images(rmr_ctx* c, const float* a_rgba, const float* b_rgba, 
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)w * h * sizeof(float4);
     const size_t tiles = (size_t)((w + 7) / 8) * ((h + 7) / 8);
-    float4 *dA = nullptr, *dB = nullptr;
-    float* dE = nullptr;
-    hipError_t e = hipMalloc((void**)&dA, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&dB, bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&dE, tiles * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(dA, a_rgba, bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dB, b_rgba, bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = rmr::launch_tile_error(dA, dB, w, h, offset, dE, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dE, tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    if (dA) (void)hipFree(dA);
-    if (dB) (void)hipFree(dB);
-    if (dE) (void)hipFree(dE);
+    hipError_t e;
+    {
+        Scratch S(c->stream);
+        float4 *dA = S.get<float4>(bytes), *dB = S.get<float4>(bytes);
+        float* dE = S.get<float>(tiles * sizeof(float));
+        S.up(dA, a_rgba, bytes);
+        S.up(dB, b_rgba, bytes);
+        S.run([&] { return rmr::launch_tile_error(dA, dB, w, h, offset, dE, c->stream); });
+        S.down(out, dE, tiles * sizeof(float));
+        e = S.done();
+    }
     HIPCHK(c, e);
     return RMR_OK;
 }
@@ -2490,26 +2536,17 @@ int rmr_denoise_variance(rmr_ctx* c, const rmr_denoise_params* p, const rmr_vari
     if (!c->est_on || !c->est_valid || !c->d_half)
         return fail(c, RMR_E_STATE, "the error estimate is not valid: call rmr_set_error_estimate before the first "
                                     "render since rmr_reload, or render with rmr_render_adaptive");
-    c->dn_result = -1; c->tm_valid = false; c->bl_valid = false;
-    c->dn_guided = false;
-    if (!c->guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
+    c->st.denoise_begin();
+    if (!c->st.guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_var[0]) {
-        float* b[3] = {nullptr, nullptr, nullptr};
-        for (int i = 0; i < 3; i++)
-            if (hipMalloc((void**)&b[i], (size_t)c->W * c->H * sizeof(float)) != hipSuccess) {
-                (void)hipGetLastError();
-                for (int k = 0; k < i; k++) (void)hipFree(b[k]);
-                return fail(c, RMR_E_NOMEM, "cannot allocate the variance planes (3 x W x H x 4 bytes)");
-            }
-        for (int i = 0; i < 3; i++) c->d_var[i] = b[i];
-    }
+    const size_t vbytes = (size_t)c->W * c->H * sizeof(float);
+    if (!c->d_var[0] && (r = alloc_all(c, {{&c->d_var[0], vbytes}, {&c->d_var[1], vbytes}, {&c->d_var[2], vbytes}},
+                                       "cannot allocate the variance planes (3 x W x H x 4 bytes)")))
+        return r;
     int img = 0, vres = 0;
     HIPCHK(c, run_guided(c->d_accum, c->d_half, c->d_guide[RMR_GUIDE_HIT], c->d_guide[RMR_GUIDE_NORMAL], c->W, c->H, q, u,
                          c->d_dn, c->d_var, c->dnv_tiled_steps, c->stream, &img, &vres));
-    c->dn_result = img;
-    c->var_result = vres;
-    c->dn_guided = true;
+    c->st.denoise_guided_queued(img, vres);
     return RMR_OK;
 }
 
@@ -2519,19 +2556,16 @@ int rmr_read_variance(rmr_ctx* c, int which, float* out, size_t bytes) {
     if (which != RMR_VARIANCE_SEED && which != RMR_VARIANCE_FILTERED) return fail(c, RMR_E_INVALID, "bad variance plane");
     const size_t need = (size_t)c->W * c->H * sizeof(float);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
-    if (c->dn_result < 0 || !c->dn_guided)
-        return fail(c, RMR_E_STATE, "no valid variance planes (call rmr_denoise_variance)");
-    const float* src = c->d_var[which == RMR_VARIANCE_SEED ? 0 : c->var_result];
-    HIPCHK(c, hipMemcpyAsync(out, src, need, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RMR_OK;
+    const int i = c->st.variance_plane(which);
+    if (i < 0) return fail(c, RMR_E_STATE, "no valid variance planes (call rmr_denoise_variance)");
+    return read_back(c, out, c->d_var[i], need);
 }
 
 void* rmr_variance_device_ptr(rmr_ctx* c, int which) {
     if (!c || (which != RMR_VARIANCE_SEED && which != RMR_VARIANCE_FILTERED)) return nullptr;
-    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
-    if (c->dn_result < 0 || !c->dn_guided) return nullptr;
-    return (void*)c->d_var[which == RMR_VARIANCE_SEED ? 0 : c->var_result];
+    if (!flushed(c)) return nullptr;
+    const int i = c->st.variance_plane(which);
+    return i < 0 ? nullptr : (void*)c->d_var[i];
 }
 
 int rmr_denoise_variance_images(rmr_ctx* c, const float* a_rgba, const float* b_rgba, const float* hit_rgba,
@@ -2547,22 +2581,21 @@ int rmr_denoise_variance_images(rmr_ctx* c, const float* a_rgba, const float* b_
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)w * h * sizeof(float4), vbytes = (size_t)w * h * sizeof(float);
     const float* src[4] = {a_rgba, b_rgba, hit_rgba, nrm_rgba};
-    float4* img[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // A, B, HIT, NORMAL, two filter images
-    float* var[3] = {nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipMalloc((void**)&img[i], bytes);
-    for (int i = 0; i < 3 && e == hipSuccess; i++) e = hipMalloc((void**)&var[i], vbytes);
-    for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipMemcpyAsync(img[i], src[i], bytes, hipMemcpyHostToDevice, c->stream);
-    int ri = 0, rv = 0;
-    if (e == hipSuccess)
-        e = run_guided(img[0], img[1], img[2], img[3], w, h, q, u, img + 4, var, c->dnv_tiled_steps, c->stream, &ri, &rv);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgba, img[4 + ri], bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && out_seed) e = hipMemcpyAsync(out_seed, var[0], vbytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && out_var) e = hipMemcpyAsync(out_var, var[rv], vbytes, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    for (float4* b : img) if (b) (void)hipFree(b);
-    for (float* b : var) if (b) (void)hipFree(b);
+    hipError_t e;
+    {
+        Scratch S(c->stream);
+        float4* img[6];   // A, B, HIT, NORMAL, two filter images
+        float* var[3];
+        for (float4*& b : img) b = S.get<float4>(bytes);
+        for (float*& b : var) b = S.get<float>(vbytes);
+        for (int i = 0; i < 4; i++) S.up(img[i], src[i], bytes);
+        int ri = 0, rv = 0;
+        S.run([&] { return run_guided(img[0], img[1], img[2], img[3], w, h, q, u, img + 4, var, c->dnv_tiled_steps, c->stream, &ri, &rv); });
+        S.down(out_rgba, img[4 + ri], bytes);
+        if (out_seed) S.down(out_seed, var[0], vbytes);
+        if (out_var) S.down(out_var, var[rv], vbytes);
+        e = S.done();
+    }
     HIPCHK(c, e);
     return RMR_OK;
 }
@@ -2610,26 +2643,23 @@ int rmr_temporal_accumulate(rmr_ctx* c, int source, float samples, const rmr_tem
     if (!c->scene_loaded) return fail(c, RMR_E_STATE, "no scene loaded (call rmr_load_scene_json / rmr_load_builtin_scene)");
     if (c->camera.model == RMR_CAMERA_EQUIRECT || c->camera.model == RMR_CAMERA_ORTHO)
         return fail(c, RMR_E_STATE, "no first-hit guides for the equirect and ortho camera models");
-    if (source == RMR_OUTPUT_DENOISED && c->dn_result < 0)
-        return fail(c, RMR_E_STATE, "no valid denoised image (call rmr_denoise)");
-    if (!c->guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
+    const int src_i = c->st.readable(source);
+    if (src_i < 0) return no_valid(c, source);
+    if (!c->st.guides_valid && (r = render_guides(c, 0, 0, c->W, c->H))) return r;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t px = (size_t)c->W * c->H, bytes = px * sizeof(float4);
     if (!c->d_tcol[0]) {
-        void* b[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        for (int i = 0; i < 6; i++)
-            if (hipMalloc(&b[i], i == 2 || i == 3 ? px * sizeof(float) : bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                for (int k = 0; k < i; k++) (void)hipFree(b[k]);
-                return fail(c, RMR_E_NOMEM, "cannot allocate the temporal planes (72 bytes per pixel)");
-            }
-        c->d_tcol[0] = (float4*)b[0]; c->d_tcol[1] = (float4*)b[1];
-        c->d_tn[0] = (float*)b[2]; c->d_tn[1] = (float*)b[3];
-        c->d_tguide[0] = (float4*)b[4]; c->d_tguide[1] = (float4*)b[5];
-        c->t_cur = -1;
+        if ((r = alloc_all(c, {{&c->d_tcol[0], bytes}, {&c->d_tcol[1], bytes}, {&c->d_tn[0], px * sizeof(float)},
+                               {&c->d_tn[1], px * sizeof(float)}, {&c->d_tguide[0], bytes}, {&c->d_tguide[1], bytes}},
+                           "cannot allocate the temporal planes (72 bytes per pixel)")))
+            return r;
+        c->st.temporal_reset();
     }
     rmr::TemporalPass T{};
-    bool have = c->t_cur >= 0 && temporal_pass(T, c->t_view, c->W, c->H, samples, q);
+    const bool have = c->st.t_cur >= 0 && temporal_pass(T, c->t_view, c->W, c->H, samples, q);
+    const int from = have ? c->st.t_cur : 0, to = 1 - from;
+    // no temporal image until everything below is queued, nor the images made from the old one
+    c->st.temporal_begin();
     if (!have) {
         // no history: the same kernel against counts of 0 (every other history plane zeroed, so that what
         // the skipped taps never read is defined), projected with the current view or, if that is
@@ -2637,20 +2667,12 @@ int rmr_temporal_accumulate(rmr_ctx* c, int source, float samples, const rmr_tem
         static const float kIdent[15] = {0, 0, 0, 0, 0, 1, 1, 0, 1, 0, 1, 1, 1, 1, 1};
         if (!c->view_set) default_view(c);
         if (!temporal_pass(T, c->view, c->W, c->H, samples, q)) (void)temporal_pass(T, kIdent, c->W, c->H, samples, q);
-        c->t_cur = 0;
         HIPCHK(c, hipMemsetAsync(c->d_tcol[0], 0, bytes, c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_tn[0], 0, px * sizeof(float), c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_tguide[0], 0, bytes, c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_tguide[1], 0, bytes, c->stream));
     }
-    const int from = c->t_cur, to = 1 - from;
-    c->t_cur = -1;   // (until everything below is queued)
-    if (c->tm_source == RMR_OUTPUT_TEMPORAL) c->tm_valid = false;   // (a tonemapped image of the old temporal image)
-    if (c->bl_source == RMR_OUTPUT_TEMPORAL) {                      // (and a bloom image of it, with what was tonemapped from that)
-        if (c->bl_valid && c->tm_source == RMR_OUTPUT_BLOOM) c->tm_valid = false;
-        c->bl_valid = false;
-    }
-    T.d.in = source == RMR_OUTPUT_DENOISED ? c->d_dn[c->dn_result] : c->d_accum;
+    T.d.in = source_image(c, source, src_i);
     T.d.hit = c->d_guide[RMR_GUIDE_HIT];
     T.d.nrm = c->d_guide[RMR_GUIDE_NORMAL];
     T.d.out = c->d_tcol[to];
@@ -2662,21 +2684,21 @@ int rmr_temporal_accumulate(rmr_ctx* c, int source, float samples, const rmr_tem
     T.xy_out = nullptr;
     HIPCHK(c, rmr::launch_temporal(T, c->stream));
     if (c->t_keep) {   // (timing the kernel alone against one history)
-        c->t_cur = from;
+        c->st.temporal_queued(from);
         return RMR_OK;
     }
     // the current guides and view become the history's
     HIPCHK(c, hipMemcpyAsync(c->d_tguide[0], c->d_guide[RMR_GUIDE_HIT], bytes, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_tguide[1], c->d_guide[RMR_GUIDE_NORMAL], bytes, hipMemcpyDeviceToDevice, c->stream));
     std::memcpy(c->t_view, c->view, sizeof c->t_view);
-    c->t_cur = to;
+    c->st.temporal_queued(to);
     return RMR_OK;
 }
 
 int rmr_temporal_reset(rmr_ctx* c) {
     if (!c) return RMR_E_INVALID;
     RMR_FLUSH(c);
-    c->t_cur = -1;
+    c->st.temporal_reset();
     return RMR_OK;
 }
 
@@ -2685,10 +2707,9 @@ int rmr_read_temporal(rmr_ctx* c, float* rgba, size_t bytes) {
     RMR_FLUSH(c);
     const size_t need = (size_t)c->W * c->H * sizeof(float4);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
-    if (c->t_cur < 0) return fail(c, RMR_E_STATE, "no valid temporal image (call rmr_temporal_accumulate)");
-    HIPCHK(c, hipMemcpyAsync(rgba, c->d_tcol[c->t_cur], need, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RMR_OK;
+    const int i = c->st.readable(RMR_OUTPUT_TEMPORAL);
+    if (i < 0) return no_valid(c, RMR_OUTPUT_TEMPORAL);
+    return read_back(c, rgba, c->d_tcol[i], need);
 }
 
 int rmr_read_temporal_count(rmr_ctx* c, float* out, size_t bytes) {
@@ -2696,16 +2717,16 @@ int rmr_read_temporal_count(rmr_ctx* c, float* out, size_t bytes) {
     RMR_FLUSH(c);
     const size_t need = (size_t)c->W * c->H * sizeof(float);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
-    if (c->t_cur < 0) return fail(c, RMR_E_STATE, "no valid temporal image (call rmr_temporal_accumulate)");
-    HIPCHK(c, hipMemcpyAsync(out, c->d_tn[c->t_cur], need, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RMR_OK;
+    const int i = c->st.readable(RMR_OUTPUT_TEMPORAL);
+    if (i < 0) return no_valid(c, RMR_OUTPUT_TEMPORAL);
+    return read_back(c, out, c->d_tn[i], need);
 }
 
 void* rmr_temporal_device_ptr(rmr_ctx* c) {
     if (!c) return nullptr;
-    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
-    return c->t_cur < 0 ? nullptr : (void*)c->d_tcol[c->t_cur];
+    if (!flushed(c)) return nullptr;
+    const int i = c->st.readable(RMR_OUTPUT_TEMPORAL);
+    return i < 0 ? nullptr : (void*)c->d_tcol[i];
 }
 
 int rmr_temporal_images(rmr_ctx* c, const float* s_rgba, const float* hit, const float* nrm, const float view[15],
@@ -2727,31 +2748,27 @@ int rmr_temporal_images(rmr_ctx* c, const float* s_rgba, const float* hit, const
     const size_t px = (size_t)w * h, bytes = px * sizeof(float4), nbytes = px * sizeof(float);
     // S, HIT, NORMAL, Hc, Hhit, Hnrm, out | Hn, n_out | xy
     const float* src[6] = {s_rgba, hit, nrm, h_rgba, h_hit, h_nrm};
-    float4* img[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    float* cnt[2] = {nullptr, nullptr};
-    float2* xy = nullptr;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 7 && e == hipSuccess; i++) e = hipMalloc((void**)&img[i], bytes);
-    for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void**)&cnt[i], nbytes);
-    if (out_xy && e == hipSuccess) e = hipMalloc((void**)&xy, px * sizeof(float2));
-    for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipMemcpyAsync(img[i], src[i], bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt[0], h_n, nbytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
+    hipError_t e;
+    {
+        Scratch S(c->stream);
+        float4* img[7];
+        float* cnt[2];
+        for (float4*& b : img) b = S.get<float4>(bytes);
+        for (float*& b : cnt) b = S.get<float>(nbytes);
+        float2* xy = out_xy ? S.get<float2>(px * sizeof(float2)) : nullptr;
+        for (int i = 0; i < 6; i++) S.up(img[i], src[i], bytes);
+        S.up(cnt[0], h_n, nbytes);
         T.d.in = img[0]; T.d.hit = img[1]; T.d.nrm = img[2];
         T.h_col = img[3]; T.h_hit = img[4]; T.h_nrm = img[5];
         T.d.out = img[6];
         T.h_n = cnt[0]; T.n_out = cnt[1];
         T.xy_out = xy;
-        e = rmr::launch_temporal(T, c->stream);
+        S.run([&] { return rmr::launch_temporal(T, c->stream); });
+        S.down(out_rgba, img[6], bytes);
+        S.down(out_n, cnt[1], nbytes);
+        if (out_xy) S.down(out_xy, xy, px * sizeof(float2));
+        e = S.done();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgba, img[6], bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_n, cnt[1], nbytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && out_xy) e = hipMemcpyAsync(out_xy, xy, px * sizeof(float2), hipMemcpyDeviceToHost, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    for (float4* b : img) if (b) (void)hipFree(b);
-    for (float* b : cnt) if (b) (void)hipFree(b);
-    if (xy) (void)hipFree(xy);
     HIPCHK(c, e);
     return RMR_OK;
 }
@@ -2759,53 +2776,37 @@ int rmr_temporal_images(rmr_ctx* c, const float* s_rgba, const float* hit, const
 // ---- tone mapping and histogram auto-exposure (rmr_tonemap.hip, tonemap.cpp) -----------------------
 static_assert(sizeof(rmr_tonemap_params) == 32, "rmr_tonemap_params is 32 bytes (include/rmr.h)");
 namespace {
-// The image a stage source names, with the existing readers' messages.
+// The image a stage source names, with the existing readers' messages. The stages take the accumulator, the
+// denoised and the temporal image; bloom_too: the bloom image as well.
 int tone_source(rmr_ctx* c, int source, const float4** src, bool bloom_too = false) {
-    if (bloom_too && source == RMR_OUTPUT_BLOOM) {
-        if (!c->bl_valid) return fail(c, RMR_E_STATE, "no valid bloom image (call rmr_bloom)");
-        *src = c->d_bl;
-    } else if (source == RMR_OUTPUT_ACCUM) {
-        *src = c->d_accum;
-    } else if (source == RMR_OUTPUT_DENOISED) {
-        if (c->dn_result < 0) return fail(c, RMR_E_STATE, "no valid denoised image (call rmr_denoise)");
-        *src = c->d_dn[c->dn_result];
-    } else if (source == RMR_OUTPUT_TEMPORAL) {
-        if (c->t_cur < 0) return fail(c, RMR_E_STATE, "no valid temporal image (call rmr_temporal_accumulate)");
-        *src = c->d_tcol[c->t_cur];
-    } else {
+    const int i = c->st.readable(source);
+    if (i == rmr::StageState::kNoSource || source == RMR_OUTPUT_TONEMAPPED || (source == RMR_OUTPUT_BLOOM && !bloom_too))
         return fail(c, RMR_E_INVALID, bloom_too ? "bad source (RMR_OUTPUT_ACCUM, RMR_OUTPUT_DENOISED, RMR_OUTPUT_TEMPORAL or RMR_OUTPUT_BLOOM)"
                                                 : "bad source (RMR_OUTPUT_ACCUM, RMR_OUTPUT_DENOISED or RMR_OUTPUT_TEMPORAL)");
-    }
+    if (i < 0) return no_valid(c, source);
+    *src = source_image(c, source, i);
     return RMR_OK;
 }
 
 // The stage's buffers, at first use: all four or none.
 int ensure_tonemap(rmr_ctx* c) {
     if (c->d_tm) return RMR_OK;
-    const size_t sizes[4] = {(size_t)c->W * c->H * sizeof(float4), (size_t)rmr::kToneSlabRows * rmr::kToneWords * sizeof(uint32_t),
-                             sizeof(rmr::ToneState), 255 * sizeof(double)};
-    void* b[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i < 4; i++)
-        if (hipMalloc(&b[i], sizes[i]) != hipSuccess) {
-            (void)hipGetLastError();
-            for (int k = 0; k < i; k++) (void)hipFree(b[k]);
-            return fail(c, RMR_E_NOMEM, "cannot allocate the tonemapped plane (16 bytes per pixel) and the histogram slab");
-        }
+    if (const int r = alloc_all(c, {{&c->d_tm, (size_t)c->W * c->H * sizeof(float4)},
+                                    {&c->d_tm_slab, (size_t)rmr::kToneSlabRows * rmr::kToneWords * sizeof(uint32_t)},
+                                    {&c->d_tm_state, sizeof(rmr::ToneState)}, {&c->d_tm_lc, 255 * sizeof(double)}},
+                                "cannot allocate the tonemapped plane (16 bytes per pixel) and the histogram slab"))
+        return r;
     // the table and the zeroed state go through the context's stream, ahead of the kernels that read them
     // (the host copy of the table lives in the context, so the queued copy's source outlives this call)
     rmr::tonemap_lc_table(c->tm_lc);
-    hipError_t e = hipMemcpyAsync(b[3], c->tm_lc, sizeof c->tm_lc, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(b[2], 0, sizeof(rmr::ToneState), c->stream);
+    hipError_t e = hipMemcpyAsync(c->d_tm_lc, c->tm_lc, sizeof c->tm_lc, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_tm_state, 0, sizeof(rmr::ToneState), c->stream);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(c->stream);
-        for (void* p : b) (void)hipFree(p);
+        free_all({&c->d_tm, &c->d_tm_slab, &c->d_tm_state, &c->d_tm_lc});
         HIPCHK(c, e);
     }
-    c->d_tm = (float4*)b[0];
-    c->d_tm_slab = (uint32_t*)b[1];
-    c->d_tm_state = (rmr::ToneState*)b[2];
-    c->d_tm_lc = (double*)b[3];
-    c->tm_valid = false;
+    c->st.tonemap_begin();
     c->tm_used = 0;
     return RMR_OK;
 }
@@ -2834,7 +2835,7 @@ int rmr_tonemap(rmr_ctx* c, int source, const rmr_tonemap_params* p) {
     if ((r = tone_source(c, source, &src, true))) return r;
     HIPCHK(c, hipSetDevice(c->device));
     if ((r = ensure_tonemap(c))) return r;
-    c->tm_valid = false;   // (until everything below is queued)
+    c->st.tonemap_begin();   // (until everything below is queued)
     const size_t px = (size_t)c->W * c->H;
     const float iw2 = rmr::tonemap_iw2(q);
     if (q.auto_exposure) {
@@ -2847,8 +2848,7 @@ int rmr_tonemap(rmr_ctx* c, int source, const rmr_tonemap_params* p) {
         HIPCHK(c, rmr::launch_tonemap(src, c->d_tm, px, nullptr, c->tm_scale, q.curve, iw2, c->stream));
         c->tm_used = 1;
     }
-    c->tm_source = source;
-    c->tm_valid = true;
+    c->st.tonemap_queued(source);
     return RMR_OK;
 }
 
@@ -2857,16 +2857,14 @@ int rmr_read_tonemapped(rmr_ctx* c, float* rgba, size_t bytes) {
     RMR_FLUSH(c);
     const size_t need = (size_t)c->W * c->H * sizeof(float4);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
-    if (!c->tm_valid) return fail(c, RMR_E_STATE, "no valid tonemapped image (call rmr_tonemap)");
-    HIPCHK(c, hipMemcpyAsync(rgba, c->d_tm, need, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RMR_OK;
+    if (c->st.readable(RMR_OUTPUT_TONEMAPPED) < 0) return no_valid(c, RMR_OUTPUT_TONEMAPPED);
+    return read_back(c, rgba, c->d_tm, need);
 }
 
 void* rmr_tonemapped_device_ptr(rmr_ctx* c) {
     if (!c) return nullptr;
-    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
-    return c->tm_valid ? (void*)c->d_tm : nullptr;
+    if (!flushed(c)) return nullptr;
+    return c->st.readable(RMR_OUTPUT_TONEMAPPED) < 0 ? nullptr : (void*)c->d_tm;
 }
 
 int rmr_read_exposure(rmr_ctx* c, double* log2_scale, float* scale) {
@@ -2879,8 +2877,7 @@ int rmr_read_exposure(rmr_ctx* c, double* log2_scale, float* scale) {
         // (rmr_tonemap_reset clears the state's valid word only: l and scale stay what the last call used)
         struct { double l; float scale; uint32_t valid; } head;
         static_assert(offsetof(rmr::ToneState, scale) == 8 && offsetof(rmr::ToneState, valid) == 12, "ToneState's head");
-        HIPCHK(c, hipMemcpyAsync(&head, c->d_tm_state, sizeof head, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (const int r = read_back(c, &head, c->d_tm_state, sizeof head)) return r;
         l = head.l;
         s = head.scale;
     }
@@ -2925,16 +2922,10 @@ namespace {
 int ensure_bloom(rmr_ctx* c) {
     if (c->d_bl) return RMR_OK;
     const rmr::BloomLevels L = rmr::bloom_levels(c->W, c->H, rmr::kBloomMaxLevels);
-    void *plane = nullptr, *pyr = nullptr;
-    if (hipMalloc(&plane, (size_t)c->W * c->H * sizeof(float4)) != hipSuccess ||
-        hipMalloc(&pyr, L.total * sizeof(float4)) != hipSuccess) {
-        (void)hipGetLastError();
-        if (plane) (void)hipFree(plane);
-        return fail(c, RMR_E_NOMEM, "cannot allocate the bloom plane (16 bytes per pixel) and its pyramid (a third of that)");
-    }
-    c->d_bl = (float4*)plane;
-    c->d_bl_pyr = (float4*)pyr;
-    c->bl_valid = false;
+    if (const int r = alloc_all(c, {{&c->d_bl, (size_t)c->W * c->H * sizeof(float4)}, {&c->d_bl_pyr, L.total * sizeof(float4)}},
+                                "cannot allocate the bloom plane (16 bytes per pixel) and its pyramid (a third of that)"))
+        return r;
+    c->st.bloom_reset();
     return RMR_OK;
 }
 
@@ -2977,11 +2968,9 @@ int rmr_bloom(rmr_ctx* c, int source, const rmr_bloom_params* p) {
     if ((r = tone_source(c, source, &src))) return r;
     HIPCHK(c, hipSetDevice(c->device));
     if ((r = ensure_bloom(c))) return r;
-    c->bl_valid = false;   // (until everything below is queued)
-    if (c->tm_source == RMR_OUTPUT_BLOOM) c->tm_valid = false;   // (a tonemapped image of the old bloom image)
+    c->st.bloom_begin();   // (until everything below is queued; a tonemapped image of the old bloom image goes too)
     HIPCHK(c, bloom_queue(c, src, q, 0));
-    c->bl_source = source;
-    c->bl_valid = true;
+    c->st.bloom_queued(source);
     return RMR_OK;
 }
 
@@ -2990,16 +2979,14 @@ int rmr_read_bloom(rmr_ctx* c, float* rgba, size_t bytes) {
     RMR_FLUSH(c);
     const size_t need = (size_t)c->W * c->H * sizeof(float4);
     if (bytes < need) return fail(c, RMR_E_INVALID, "buffer too small");
-    if (!c->bl_valid) return fail(c, RMR_E_STATE, "no valid bloom image (call rmr_bloom)");
-    HIPCHK(c, hipMemcpyAsync(rgba, c->d_bl, need, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RMR_OK;
+    if (c->st.readable(RMR_OUTPUT_BLOOM) < 0) return no_valid(c, RMR_OUTPUT_BLOOM);
+    return read_back(c, rgba, c->d_bl, need);
 }
 
 void* rmr_bloom_device_ptr(rmr_ctx* c) {
     if (!c) return nullptr;
-    if (!c->deferred.empty() && flush_calls(c) != RMR_OK) return nullptr;
-    return c->bl_valid ? (void*)c->d_bl : nullptr;
+    if (!flushed(c)) return nullptr;
+    return c->st.readable(RMR_OUTPUT_BLOOM) < 0 ? nullptr : (void*)c->d_bl;
 }
 
 #if RMR_DIAG
@@ -3024,37 +3011,15 @@ int rmr_diag_bloom_time(rmr_ctx* c, int which, int levels, int n, float* ms) {
     int r;
     if ((r = ensure_tonemap(c))) return r;
     if ((r = ensure_bloom(c))) return r;
-    c->bl_valid = false;
-    if (c->tm_source == RMR_OUTPUT_BLOOM) c->tm_valid = false;
+    c->st.bloom_begin();
     const size_t px = (size_t)c->W * c->H;
-    const int blocks = rmr::lum_hist_blocks(px);
-    rmr_tonemap_params tq;
-    rmr_default_tonemap_params(&tq);
-    const rmr::ToneMeter M = rmr::tonemap_meter(tq);
     rmr_bloom_params q;
     rmr_default_bloom_params(&q);
     q.levels = levels;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    HIPCHK(c, hipEventCreate(&ev[0]));
-    hipError_t e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = rmr::launch_lum_hist(c->d_accum, px, c->d_tm_slab, blocks, false, c->stream);
-    for (int i = 0; i < 32 && e == hipSuccess; i++)
-        e = rmr::launch_meter(c->d_tm_slab, blocks, c->d_tm_state, c->d_tm_lc, M, false, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
-    for (int i = 0; i < n && e == hipSuccess; i++) {
-        if (which == 3) e = hipMemcpyAsync(c->d_bl, c->d_accum, px * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
-        else e = bloom_queue(c, c->d_accum, q, which);
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    float t = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&t, ev[0], ev[1]);
-    (void)hipEventDestroy(ev[0]);
-    if (ev[1]) (void)hipEventDestroy(ev[1]);
-    HIPCHK(c, e);
-    *ms = t / (float)n;
-    return RMR_OK;
+    return timed_rounds(c, false, false, n, ms, [&] {
+        if (which == 3) return hipMemcpyAsync(c->d_bl, c->d_accum, px * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
+        return bloom_queue(c, c->d_accum, q, which);
+    });
 }
 
 // Diagnostic library only (not in include/rmr.h; tools/tonemap_time.py): whether k_lum_hist folds equal
@@ -3078,38 +3043,23 @@ int rmr_diag_tonemap_time(rmr_ctx* c, int which, int n, float* ms) {
     HIPCHK(c, hipSetDevice(c->device));
     int r;
     if ((r = ensure_tonemap(c))) return r;
-    c->tm_valid = false;
+    c->st.tonemap_begin();
     const size_t px = (size_t)c->W * c->H;
     const int blocks = rmr::lum_hist_blocks(px);
     rmr_tonemap_params q;
     rmr_default_tonemap_params(&q);
     const rmr::ToneMeter M = rmr::tonemap_meter(q);
     const float iw2 = rmr::tonemap_iw2(q);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    HIPCHK(c, hipEventCreate(&ev[0]));
-    hipError_t e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = rmr::launch_lum_hist(c->d_accum, px, c->d_tm_slab, blocks, c->tm_fold, c->stream);
-    for (int i = 0; i < 32 && e == hipSuccess; i++)
-        e = rmr::launch_meter(c->d_tm_slab, blocks, c->d_tm_state, c->d_tm_lc, M, true, c->stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
-    for (int i = 0; i < n && e == hipSuccess; i++) {
+    return timed_rounds(c, c->tm_fold, true, n, ms, [&] {
+        hipError_t e = hipSuccess;
         if (which == 0 || which == 4) e = rmr::launch_lum_hist(c->d_accum, px, c->d_tm_slab, blocks, c->tm_fold, c->stream);
         if ((which == 1 || which == 4) && e == hipSuccess)
             e = rmr::launch_meter(c->d_tm_slab, blocks, c->d_tm_state, c->d_tm_lc, M, true, c->stream);
         if ((which == 2 || which == 4) && e == hipSuccess)
             e = rmr::launch_tonemap(c->d_accum, c->d_tm, px, c->d_tm_state, 0.0f, q.curve, iw2, c->stream);
         if (which == 3) e = hipMemcpyAsync(c->d_tm, c->d_accum, px * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = es;
-    float t = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&t, ev[0], ev[1]);
-    (void)hipEventDestroy(ev[0]);
-    if (ev[1]) (void)hipEventDestroy(ev[1]);
-    HIPCHK(c, e);
-    *ms = t / (float)n;
-    return RMR_OK;
+        return e;
+    });
 }
 
 // Diagnostic library only (not in include/rmr.h; tools/denoise_time.py): which a-trous passes run the
