@@ -189,11 +189,13 @@ int rmr_get_section_cycles(rmr_ctx* ctx, uint64_t out[4]);
  * [14] map evals in shading batches (certified getNormal probes, rmr_trace.h cert_normals; part of [0]),
  * [4..7] the section cycles above (or the RMR_JIT_AMBCOUNT fallback counts, tools/amb_rate.py). */
 int rmr_get_counters(rmr_ctx* ctx, uint64_t out[16]);
-/* The first n of the whole counter block (n <= 32). [0..15] as above; [16] events the lane-slot kernels
+/* The first n of the whole counter block (n <= 34). [0..15] as above; [16] events the lane-slot kernels
  * deposited into another lane's empty slot (the overflow deposit, rmr_trace.h RMR_SLOT_OVERFLOW);
  * [17..30] the profiling build's counters, each in a slot of its own (rmr_internal.h kCntProf*: refill
  * claim / ray cycles, uncertified hits, lanes per full map() batch, and the lane-slot schedule's passes,
- * park steps, lost lane-iterations by cause and events per batch); zeros in every other build. */
+ * park steps, lost lane-iterations by cause and events per batch); zeros in every other build;
+ * [31..33] the trailing steps of the lane-slot kernels (rmr_set_trail_steps), in every build: steps taken
+ * (lane-level; part of [0]), passes run (wave-level), lanes evaluated in the passes (taken + refused). */
 int rmr_get_counters_n(rmr_ctx* ctx, uint64_t* out, int n);
 /* Select kernel implementation (0 = persistent wavefront kernel, 1 = one launch-thread per path). */
 int rmr_set_kernel(rmr_ctx* ctx, int kernel);
@@ -873,6 +875,13 @@ int rmr_set_tuning(rmr_ctx* ctx, int shade_threshold, int grid_per_cu, long long
  * wait for that trace's drain, and the next trace behind them; a few free slots let them run beside
  * it. Scheduling only: results do not depend on it. RMR_E_INVALID for blocks < 0. */
 int rmr_set_grid_reserve(rmr_ctx* ctx, int blocks);
+/* Trailing steps of the lane-slot kernels (rmr_trace.h RMR_TRAIL_STEPS): behind each map-loop iteration's
+ * whole map, up to `steps` (0..3) further march steps that evaluate the map's nearest primitive alone,
+ * wherever a distance bound proves it the whole map's result. -1 (the default): the kernel class's own
+ * number. Takes effect only in kernels specialised with the steps compiled in, and only with a positive
+ * stepMultiply. Scheduling only: every sample and rmr_stats::map_evals are the same for every value.
+ * RMR_E_INVALID outside -1..3. */
+int rmr_set_trail_steps(rmr_ctx* ctx, int steps);
 /* Test hook: per-sample radiance (before the running mean) of the integer rect, written as
  * out[k][y-y0][x-x0][4]; sample k is seeded with times[k]. The accumulator is left unchanged. */
 int rmr_trace_samples(rmr_ctx* ctx, const float* times, int x0, int y0, int x1, int y1, uint32_t nspp, float* out);

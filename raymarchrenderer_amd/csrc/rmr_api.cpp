@@ -29,6 +29,7 @@
 #include "rmr_camera.hpp"
 #include "rmr_ray_check.h"
 #include "rmr_jit.hpp"
+#include "rmr_trail_rule.h"
 #include "scene.hpp"
 #include "temporal.hpp"
 #include "tonemap.hpp"
@@ -232,6 +233,7 @@ struct rmr_ctx {
     // refill threshold follows the park threshold as the others' follows the shading threshold
     int lane_slots = -1;
     int park_threshold = 0, slot_threshold = 0;
+    int trail_steps = -1;       // trailing steps per map-loop iteration (rmr_set_trail_steps): -1 the kernel class's
     int jit_slots = -1;         // the request `jit` was specialised with (slots_request)
     // nearest-primitive cache: 40 lanes per full map() batch, or once waiting lanes >= cache-served ones
     // (R = 8; csg256 with the candidate grid: 15.7 -> 14.8 ms per 4 spp against R = 2)
@@ -627,6 +629,8 @@ int ensure_jit(rmr_ctx* c, bool rays = false) {
     k.park_t = facts.park_t();
     k.slot_t = facts.slot_t();
     k.slot_t_small = facts.slot_t_small();
+    k.trail = facts.trail;
+    k.trail_k = facts.trail_k();
     c->jit_loaded.push_back(k);
     jk = k;
     ready = true;
@@ -1123,7 +1127,11 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
             const bool small = P.n_units < (uint64_t)gp.grid * (uint64_t)(jk.block / 64) * (uint64_t)jk.chunk *
                                                (uint64_t)rmr::JitFacts::kSlotSmallClaims;
             const int batch = c->slot_threshold > 0 ? c->slot_threshold : (small ? jk.slot_t_small : jk.slot_t);
-            P.shade_threshold = park | (batch << 8);
+            // trailing steps (rmr_trace.h RMR_TRAIL_STEPS), bits 16-17: only where the source has them, and
+            // only for a march that advances (rmr_trail_rule.h: the rule's t >= t0)
+            int trail = !jk.trail ? 0 : (c->trail_steps >= 0 ? c->trail_steps : jk.trail_k);
+            if (!(P.step_mult > 0.0f) || !std::isfinite(P.step_mult)) trail = 0;
+            P.shade_threshold = park | (batch << 8) | (std::min(trail, (int)rmr::kTrailMaxSteps) << 16);
             P.refill_threshold = refill_for(c->refill_threshold, park);
         }
         if ((r = submit_launch(c, P, S, use_jit, gp.grid, rays ? c->d_rays : nullptr, !rl))) return r;
@@ -1922,6 +1930,13 @@ int rmr_set_tuning(rmr_ctx* c, int shade_threshold, int grid_per_cu, long long s
     }
     if (grid_per_cu >= 0) c->grid_per_cu = grid_per_cu;
     if (samp_budget_bytes > 0) c->samp_budget = (size_t)samp_budget_bytes;
+    return RMR_OK;
+}
+
+int rmr_set_trail_steps(rmr_ctx* c, int steps) {
+    if (!c || steps < -1 || steps > rmr::kTrailMaxSteps) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    c->trail_steps = steps;
     return RMR_OK;
 }
 

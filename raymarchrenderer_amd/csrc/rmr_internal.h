@@ -57,8 +57,12 @@ constexpr int kQueueWordStride = 32;   // 32-bit words between two partition cou
 // The kernels' raw device counters (KParams::counters; rmr_get_counters_n): kCounterSlots 64-bit words.
 // [0..15] as rmr.h documents them (the flop-count and other diagnostic builds use 9..15 as well). From
 // 16 up every counter has a slot of its own:
-constexpr int kCounterSlots = 32;
+constexpr int kCounterSlots = 34;
 constexpr int kCntOverflow = 16;         // lane-slot kernels: events deposited into another lane's empty slot
+// lane-slot kernels with trailing steps (rmr_trace.h RMR_TRAIL_STEPS), every build:
+constexpr int kCntTrailSteps = 31;       //   trailing steps taken (lane-level; part of counter 0)
+constexpr int kCntTrailPasses = 32;      //   trailing passes run (wave-level)
+constexpr int kCntTrailLanes = 33;       //   lanes evaluated in those passes (taken + refused)
 // RMR_PROFILE builds (rmr_trace.h trace_main), zero otherwise:
 constexpr int kCntProfClaim = 17;        // refill: cycles in work-queue claims
 constexpr int kCntProfRays = 18;         // refill: cycles in the chunk's primary rays

@@ -44,6 +44,8 @@ struct JitKernel {
     bool slots = false;         // the lane-slot schedule (rmr_trace.h RMR_LANE_SLOTS)
     int park_t = 0, slot_t = 0; // its default thresholds (JitFacts)
     int slot_t_small = 0;       // ... the batch threshold of launches under kSlotSmallClaims claims per wave
+    bool trail = false;         // the source has the trailing steps (rmr_trace.h RMR_TRAIL_STEPS)
+    int trail_k = 0;            // ... and takes this many per map-loop iteration unless told otherwise
 };
 
 // What jit_source decided about the kernel class (the launch settings follow from these, not from
@@ -56,6 +58,9 @@ struct JitFacts {
     // sphere/box kernels) / this source has it on
     bool slots_ok = false, slots = false;
     bool overflow = false;   // ... with the park step's overflow deposit (rmr_trace.h RMR_SLOT_OVERFLOW)
+    bool trail = false;      // ... with the trailing steps compiled in (rmr_trace.h RMR_TRAIL_STEPS)
+    // trailing steps per map-loop iteration where the source has them
+    int trail_k() const { return trail ? 2 : 0; }
     int chunk() const { return (cache || slots) ? 64 : 128; }   // rmr_trace.h RMR_CHUNK_CACHE / RMR_CHUNK_SLOTS / RMR_CHUNK
     // lane slots: finished marches per park step, slot events per shading batch (Cornell-5 1080p 64 spp:
     // flat over 8-10 / 28-40, +10% and more outside 6-12 / 24-48)

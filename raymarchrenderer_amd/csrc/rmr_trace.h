@@ -28,6 +28,7 @@
 #include "rmr_math.h"
 #include "rmr_internal.h"
 #include "rmr_slot_rule.h"
+#include "rmr_trail_rule.h"
 
 namespace rmr {
 
@@ -2576,6 +2577,38 @@ static_assert(RMR_QUEUE_PARTS >= 1 && RMR_QUEUE_PARTS <= 64 && RMR_QUEUE_PARTS *
 #ifndef RMR_SLOT_OVERFLOW
 #define RMR_SLOT_OVERFLOW 0
 #endif
+// Trailing steps (lane-slot kernels with batch probes; the hipRTC source asks for them, rmr_jit.cpp): every
+// map-loop iteration still runs the whole approximate map for every marching lane, and that map leaves its
+// minimiser w and its runner-up s2 in registers. After the iteration's march_update the wave runs up to K
+// more passes (K: bits 16-17 of KParams::shade_threshold, 0 = none) in which a lane whose one-primitive
+// bound holds at its new march point (rmr_trail_rule.h: the derivation and the float statements) takes
+// the next march step from primitive w alone — map(p) is (F_w(p), id_w) there, the value the whole map
+// returns — and a lane whose bound fails sits the pass out, unchanged, until the next iteration's map.
+// No lane waits for another and no state crosses iterations. A pass no lane qualifies for is not run.
+// The primitive's numbers come from the table the certified probes read (P.dprims, scene order), or from
+// a copy of it in LDS (RMR_TRAIL_LDS: scenes of at most kTrailLdsPrims primitives).
+#ifndef RMR_TRAIL_STEPS
+#define RMR_TRAIL_STEPS 0
+#endif
+#ifndef RMR_TRAIL_LDS
+#define RMR_TRAIL_LDS 0
+#endif
+// 8 primitives, 256 B: a 512-B table for 16 measured +14 % per map-loop iteration, which
+// fits five blocks per CU under an LDS granule of 1280 B: the lane-slot block's 26,624 B occupy 21 granules
+// (26,880 B), six blocks of 22 exceed the CU's 163,840 B, and 256 B are left in the 21st.
+constexpr int kTrailLdsPrims = 8;
+// primitive w of the table at p: rmr_trail_rule.h's box form with sqrt_cr_big (the rule refuses the len2
+// it is not exact for), the same bits as prim_dist_at, hence sd_box / sd_sphere, at points without NaN
+RMR_D float trail_dist(const float4* q, V3 p, float& mid, float& len2, bool& box) {
+    const float4 a = q[0], b = q[1];   // c.xyz r.x | r.yz type|index<<8 mat_id
+    box = (__float_as_int(b.z) & 0xff) == RMR_PRIM_BOX;
+    const V3 h = box ? v3(a.w, b.x, b.y) : v3s(0.0f);
+    const float rad = box ? 0.0f : a.w;
+    mid = b.w;
+    const V3 qq = vabs(p - v3(a.x, a.y, a.z)) - h;
+    len2 = trail_len2(qq.x, qq.y, qq.z);
+    return (trail_k(qq.x, qq.y, qq.z) + sqrt_cr_big(len2)) - rad;
+}
 // the primary ray's first march step with the chunk's rays (chunk_ray EYEC; lane-slot kernels only)
 #ifndef RMR_EYE_CHUNK
 #define RMR_EYE_CHUNK 1   // (0: as a march_update of the fresh lanes at every refill, A/B)
@@ -2606,6 +2639,8 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
     // per-wave event counters, 32-bit (wave-uniform: SGPRs; 64-bit ones cost the cache kernels
     // scratch round trips), flushed to the 64-bit global counters before any can pass 2^31
     WCount maps = 0, iters = 0, shades = 0, fulls = 0, shaded = 0, bmaps = 0, ovfs = 0;
+    // trailing steps: steps taken (part of `maps`), passes run, lanes evaluated in them (taken + refused)
+    WCount tsteps = 0, tpasses = 0, tlanes = 0;
     // lane slots: RM1 HO kernels with the certifying inline map, persistent (launched without
     // separateChannels and without an env map only: the host picks the code object, rmr_api.cpp)
     constexpr bool SLOTS = RMR_LANE_SLOTS && PERSIST && VAR == RMR_VARIANT_RM1 && CERT && MAP::kCert && !MAP::kCache &&
@@ -2613,6 +2648,8 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
     constexpr bool BP = SLOTS && RMR_BATCH_PROBES;   // uncertified hits' probes in the shading batch
     constexpr bool EYEC = SLOTS && RMR_EYE_CHUNK;    // the eye step with the chunk's rays
     constexpr bool OVF = SLOTS && RMR_SLOT_OVERFLOW;   // events of lanes with a full slot into empty slots
+    constexpr bool TRAIL = BP && RMR_TRAIL_STEPS;       // one-primitive march steps behind each full map
+    constexpr bool TRAIL_LDS = TRAIL && RMR_TRAIL_LDS;
     constexpr uint32_t CHUNK = MAP::kCache ? RMR_CHUNK_CACHE : (SLOTS ? RMR_CHUNK_SLOTS : RMR_CHUNK);
     const uint32_t n_units = (uint32_t)P.n_units;   // < 2^32 per launch (host chunking)
     // units per claim: the LDS ray buffer's CHUNK, or fewer for a small launch (the host's chunk_units)
@@ -2644,6 +2681,7 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
     // lane slots: finished marches before the park step runs, slot events before a shading batch
     // (in the shading threshold's place: bits 0-7 and 8-15)
     const int PK = T & 0xff, T2 = (T >> 8) & 0xff;
+    const int KT = TRAIL ? (T >> 16) & 3 : 0;   // trailing steps per map-loop iteration (rmr_api.cpp)
     int sst = 0;             // the lane's slot: 0 empty, 1 an event awaiting shading, 2 a ray ready to march
     uint32_t nev = 0;        // slots holding an event (wave-uniform)
     // eye_map: every primary ray (a fresh unit, or a separateChannels restart) starts its march at
@@ -2724,6 +2762,14 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
 #define RMR_PRIM_DIST(k, p, mid, j) (dp_lds ? prim_dist_tab(s_dp + kTabStep * (k), p, mid, j) : prim_dist(P, k, p, mid, j))
     static_assert(!RMR_NPC_TAB_SOA || MAP::kCache, "an SoA table kernel reads dtab as the LDS copy only");
 #define RMR_DTAB (dp_lds ? (const float4*)s_dp : (const float4*)P.dprims)
+    // trailing steps: the table in LDS, in the global table's layout (the generator asks for it only for
+    // scenes it holds, rmr_jit.cpp; a larger table would be cut short here, never overrun)
+    __shared__ float4 s_tp[TRAIL_LDS ? 2 * kTrailLdsPrims : 1];
+    if constexpr (TRAIL_LDS) {
+        for (int i = (int)threadIdx.x; i < 2 * P.n_prims && i < 2 * kTrailLdsPrims; i += (int)blockDim.x)
+            s_tp[i] = ((const float4*)P.dprims)[i];
+        __syncthreads();
+    }
     const int wv = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) & 3);   // the wave's index in its block (an SGPR)
     uint32_t chunk_base = 0;
 #ifdef RMR_WAVE_TIMES   // counters [9] ~min start, [11] ~min / [10] max queue exhaustion, [12] ~min /
@@ -3042,6 +3088,7 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
             uint64_t am = amask;
             // the loop's own counts (scalar registers; the wave counters were carried in VGPRs here)
             uint32_t lmaps = 0, liters = 0;
+            uint32_t ltsteps = 0, ltpasses = 0, ltlanes = 0;   // (trailing steps)
             // lane slots: PK more finished marches than the lanes that wait in registers for their slot
             const int TL = SLOTS ? __popcll(__ballot(is_shade(L.phase))) + PK : T;
 #ifdef RMR_PROFILE
@@ -3056,12 +3103,25 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                 else lost_idle += (uint64_t)__popcll(__ballot(L.phase == PH_IDLE));
                 if constexpr (SLOTS) ready_wait += (uint64_t)__popcll(__ballot(sst == 2));
 #endif
+                // trailing steps: the iteration's anchor (rmr_trail_rule.h trail_anchor, the map's point's
+                // ray parameter, the map's minimiser); read only by lanes that were active here
+                float tr_anchor = 0.0f, tr_t0 = 0.0f;
+                int tr_w = 0;
                 if (is_active(L.phase)) {
                     // (BP: every active lane marches; its point has no probe offset)
                     const V3 p = BP ? vfma(L.d, L.t, L.o) : RMR_MARCH_POINT(L);
                     if constexpr (!MAP::kCounts)   // every primitive of the fold (Mandelbulb iterations: inside)
                         RMR_COUNT(P.counters, active_lanes(), (uint64_t)P.flops_static, (uint64_t)P.transc_static);
-                    if constexpr (BP) {
+                    if constexpr (TRAIL) {
+                        int w;
+                        bool cert;
+                        float s2;
+                        const V2 m = MAP::eval_t(P, p, w, cert, s2);
+                        tr_anchor = trail_anchor(s2, P.am_r2, npc_eps(P, p));
+                        tr_t0 = L.t;
+                        tr_w = w;
+                        march_update<HO, false, true, true>(P, L, m, w, cert);
+                    } else if constexpr (BP) {
                         int w;
                         bool cert;
                         const V2 m = MAP::eval_c(P, p, w, cert);
@@ -3080,6 +3140,43 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                 }
                 lmaps += (uint32_t)__popcll(am);
                 liters++;
+                if constexpr (TRAIL) {
+                    // Up to KT wave-uniform passes. A lane takes part while it still marches, from outside,
+                    // the ray the iteration's map was evaluated on (phases change in march_update alone, so
+                    // a lane active here was active at the map; batch-probe kernels have no active phase
+                    // but PH_MARCH) and every pass so far accepted its step: a refused lane has not
+                    // moved, so the rule would refuse it again.
+                    bool q = is_active(L.phase) && !L.inside;
+                    for (int k = 0; k < KT; k++, q = q && is_active(L.phase)) {
+                        const uint64_t qm = __ballot(q);
+                        if (!qm) break;
+                        const V3 p = vfma(L.d, L.t, L.o);
+                        float mid, len2;
+                        bool box;
+                        const float F = trail_dist((TRAIL_LDS ? (const float4*)s_tp : (const float4*)P.dprims) + 2 * (q ? tr_w : 0),
+                                                   p, mid, len2, box);
+                        const TrailStep ts = trail_rule(tr_anchor, tr_t0, L.t, trail_linf(p.x, p.y, p.z), trail_finite(p.x, p.y, p.z),
+                                                        F, len2, P.npc_eps0, P.am_dmax);
+                        const bool ok = q && ts.accept;
+                        const uint64_t um = __ballot(ok);
+                        ltpasses++;
+                        ltlanes += (uint32_t)__popcll(qm);
+                        if (!um) break;
+#ifdef RMR_COUNT_FLOPS   // one primitive and its opU, as the cache path counts them, per type
+                        {
+                            const uint64_t nb = (uint64_t)__popcll(__ballot(ok && box));
+                            RMR_COUNT(P.counters, (uint64_t)__popcll(um) - nb, 10 + 2, 1);
+                            RMR_COUNT(P.counters, nb, 22 + 2, 1);
+                        }
+#endif
+                        // the step march() takes with map(p) = (F, id_w); a hit parks certified by the
+                        // rule's own certificate or uncertified for the batch probes (the same bits)
+                        if (ok) march_update<HO, false, true, true>(P, L, v2(F, mid), tr_w, ts.cert);
+                        q = ok;
+                        lmaps += (uint32_t)__popcll(um);
+                        ltsteps += (uint32_t)__popcll(um);
+                    }
+                }
                 const uint64_t sm = __ballot(is_shade(L.phase));
                 am = __ballot(is_active(L.phase));
 #ifdef RMR_PROFILE
@@ -3089,6 +3186,11 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
             }
             maps += (WCount)__builtin_amdgcn_readfirstlane(lmaps);
             iters += (WCount)__builtin_amdgcn_readfirstlane(liters);
+            if constexpr (TRAIL) {
+                tsteps += (WCount)__builtin_amdgcn_readfirstlane(ltsteps);
+                tpasses += (WCount)__builtin_amdgcn_readfirstlane(ltpasses);
+                tlanes += (WCount)__builtin_amdgcn_readfirstlane(ltlanes);
+            }
         }
         RMR_STAMP(c2);
         if constexpr (SLOTS) {
@@ -3325,8 +3427,14 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                 if (CERT) atomicAdd(P.counters + 14, (unsigned long long)bmaps);
                 // events deposited into another lane's empty slot (RMR_SLOT_OVERFLOW)
                 if (OVF) atomicAdd(P.counters + kCntOverflow, (unsigned long long)ovfs);
+                if (TRAIL) {   // trailing steps taken (in [0] too), passes run, lanes evaluated in them
+                    atomicAdd(P.counters + kCntTrailSteps, (unsigned long long)tsteps);
+                    atomicAdd(P.counters + kCntTrailPasses, (unsigned long long)tpasses);
+                    atomicAdd(P.counters + kCntTrailLanes, (unsigned long long)tlanes);
+                }
             }
             maps = iters = shades = fulls = shaded = bmaps = ovfs = 0;
+            tsteps = tpasses = tlanes = 0;
         }
         if (last) break;
     }

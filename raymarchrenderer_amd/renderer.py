@@ -172,6 +172,11 @@ class Renderer:
             st |= 1 << 23 | p << 16 | min(64, int(slot_batch or 0)) << 24
         self._chk(self._L.rmr_set_tuning(self._ctx, st, int(grid_per_cu), int(samp_budget)))
 
+    def set_trail_steps(self, steps):
+        """Trailing steps per map-loop iteration of the lane-slot kernels (rmr_set_trail_steps): 0..3, -1 the
+        kernel class's own; scheduling only."""
+        self._chk(self._L.rmr_set_trail_steps(self._ctx, int(steps)))
+
     def set_grid_reserve(self, blocks):
         """Workgroups the persistent trace launch leaves free (rmr_set_grid_reserve; scheduling only)."""
         self._chk(self._L.rmr_set_grid_reserve(self._ctx, int(blocks)))
@@ -798,11 +803,12 @@ class Renderer:
     def reset_stats(self):
         self._chk(self._L.rmr_reset_stats(self._ctx))
 
-    def counters(self):
-        """The kernels' 32 raw device counters (rmr_get_counters_n; rmr.h and rmr_internal.h document the
-        slots: 0-15 as ever, 16 the overflow deposits, 17-30 the profiling build's own)."""
-        raw = (C.c_uint64 * 32)()
-        self._chk(self._L.rmr_get_counters_n(self._ctx, raw, 32))
+    def counters(self, n=32):
+        """The kernels' first n raw device counters (rmr_get_counters_n; rmr.h and rmr_internal.h document
+        the slots: 0-15 as ever, 16 the overflow deposits, 17-30 the profiling build's own, 31-33 the
+        trailing steps')."""
+        raw = (C.c_uint64 * n)()
+        self._chk(self._L.rmr_get_counters_n(self._ctx, raw, n))
         return [int(v) for v in raw]
 
 

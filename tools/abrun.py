@@ -12,6 +12,9 @@ VARIANT = [LABEL=]SPEC[;SPEC...], SPEC one of
     shade:T         rmr_set_tuning shading threshold (T + 256 R: refill threshold R)
     slots:off | slots:P,T2   lane-slot kernels: the schedule off, or its park / batch thresholds
     overflow:on | overflow:off   lane-slot kernels: the park step's overflow deposit (RMR_JIT_OVERFLOW)
+    trail:K | trail:K,global     lane-slot kernels: K trailing steps per map-loop iteration (RMR_JIT_TRAIL=1 and
+                    rmr_set_trail_steps; K = 0: compiled in, none taken); global: the primitive table
+                    read from global memory (RMR_JIT_TRAIL=2) instead of the LDS copy
 e.g.  python tools/abrun.py --cases c2,c4 base="lib:tools/librmr_base.so" new="lib:raymarchrenderer_amd/librmr_diag.so"
       python tools/abrun.py --cases glass,default w6="opts:-DRMR_PROG_WAVES=6" w7="opts:-DRMR_PROG_WAVES=7" def=""
 
@@ -54,7 +57,7 @@ CASES = {
 
 def parse_variant(text):
     label, _, spec = text.partition("=") if ("=" in text.split(":")[0]) else ("", "", text)
-    v = {"label": label or text or "default", "lib": None, "env": {}, "cull": None, "shade": None}
+    v = {"label": label or text or "default", "lib": None, "env": {}, "cull": None, "shade": None, "trail": None}
     for item in filter(None, spec.split(";")):
         kind, _, val = item.partition(":")
         if kind == "lib":
@@ -75,6 +78,12 @@ def parse_variant(text):
             if val not in ("on", "off"):
                 raise SystemExit("overflow:on or overflow:off, not %r" % item)
             v["env"]["RMR_JIT_OVERFLOW"] = "1" if val == "on" else "0"
+        elif kind == "trail":   # rmr_jit.cpp: part of the generated source; K: a launch parameter
+            k, _, tab = val.partition(",")
+            if tab not in ("", "global") or not k.isdigit() or int(k) > 3:
+                raise SystemExit("trail:K or trail:K,global with K in 0..3, not %r" % item)
+            v["env"]["RMR_JIT_TRAIL"] = "2" if tab else "1"
+            v["trail"] = int(k)
         else:
             raise SystemExit("unknown variant spec %r" % item)
     return v
@@ -124,6 +133,8 @@ def main():
                     r.set_culling(v["cull"])
                 if v["shade"] is not None:
                     r.set_tuning(v["shade"], -1, 0)
+                if v["trail"] is not None:
+                    r.set_trail_steps(v["trail"])
                 r.reload()
                 r.reset_stats()
                 r.render_spp(times)
@@ -131,7 +142,7 @@ def main():
                 if rnd:
                     ms[i].append(s.trace_ms)
                 if rnd == a.rounds:
-                    img[i], st[i], cnt[i] = r.read_accum(), s, r.counters()
+                    img[i], st[i], cnt[i] = r.read_accum(), s, r.counters(32 if v["trail"] is None else 34)
         apply_env({"env": {}}, keys, saved)
         t0 = float(np.median(ms[0]))
         out = {"case": name, "W": W, "H": H, "spp": spp, "bounces": bounces}
@@ -147,6 +158,13 @@ def main():
                 "overflow_deposits": cnt[i][16],
                 "bitwise_equal_to_first": bool(np.array_equal(img[i].view(np.uint32), img[0].view(np.uint32))),
             }
+            if v["trail"] is not None:   # rmr_internal.h kCntTrail*: steps taken, passes, lanes evaluated in them
+                c = cnt[i]
+                out[v["label"]]["trail"] = {
+                    "steps": c[31], "passes": c[32], "lanes": c[33],
+                    "steps_share_of_march_evals": round(c[31] / max(1, c[0] - c[14]), 4),
+                    "accepted_share": round(c[31] / max(1, c[33]), 4),
+                    "lanes_per_pass": round(c[33] / max(1, c[32]), 2), "passes_per_iter": round(c[32] / max(1, c[1]), 3)}
             if a.raw:
                 out[v["label"]]["raw"] = cnt[i]
             if "-DRMR_PROFILE" in v["env"].get("RMR_JIT_OPTS", ""):
