@@ -13,10 +13,17 @@
 // and the box form of F_w used there is sd_box / sd_sphere bit for bit. Wherever it certifies: at each of
 // getNormal's six probes of the point every other primitive is strictly farther than w.
 // Last line "ok"; a line "FAIL ..." per violation otherwise.
+//
+// trail_rule_test --scene FILE runs the same checks on one scene read from a text file instead (generated
+// scenes at other scales and offsets, tests/scene_family.py write_rule_scene): the first line max_dist, then
+// one line per primitive, `b|s id cx cy cz rx ry rz`, every number a C hex float; 200,000 triples. The
+// origins and the march's outer limit, which the compiled-in scenes have about the origin at Cornell-5's
+// size, move and scale with the file's scene (Frame).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "rmr_trail_rule.h"
@@ -28,10 +35,17 @@ struct Prim {
     float c[3], r[3];
     float id;
 };
+// where the rays start and how far a march is followed: the compiled-in scenes' constants (an eye at
+// (0, 3, -6), origins within 4.5 of the origin, marches up to 30 from it) are this frame at c = 0, k = 1
+struct Frame {
+    float c[3] = {0.0f, 0.0f, 0.0f};
+    float k = 1.0f;
+};
 struct Scene {
     const char* name;
     std::vector<Prim> prims;
     float max_dist;
+    Frame fr;
 };
 
 Prim box(float id, float cx, float cy, float cz, float rx, float ry, float rz) { return Prim{true, {cx, cy, cz}, {rx, ry, rz}, id}; }
@@ -282,12 +296,13 @@ void origin(const Scene& s, Rng& g, float* o, float* d) {
     unit(g, d);
     const int kind = g.below(8);
     if (kind == 0) {
-        o[0] = 0.0f; o[1] = 3.0f; o[2] = -6.0f;   // an eye above and in front of the scene, looking in
+        const float eye[3] = {0.0f, 3.0f, -6.0f};   // an eye above and in front of the scene, looking in
+        for (int k = 0; k < 3; k++) o[k] = s.fr.c[k] + s.fr.k * eye[k];
         if (d[2] < 0.0f) d[2] = -d[2];
         return;
     }
     if (kind <= 2) {
-        for (int k = 0; k < 3; k++) o[k] = 4.5f * g.sym();
+        for (int k = 0; k < 3; k++) o[k] = s.fr.c[k] + s.fr.k * (4.5f * g.sym());
         return;
     }
     const Prim& q = s.prims[(size_t)g.below((int)s.prims.size())];
@@ -316,7 +331,7 @@ Tally run_scene(const Scene& s, uint64_t want, uint64_t seed) {
     const float mults[3] = {0.25f, 0.5f, 1.7f};
     Tally T;
     Rng g{seed};
-    for (uint64_t ray = 0; T.triples < want; ray++) {
+    for (uint64_t ray = 0; T.triples < want && ray < 64 * want; ray++) {
         const float mult = mults[ray % 3];
         float o[3], d[3];
         origin(s, g, o, d);
@@ -324,7 +339,9 @@ Tally run_scene(const Scene& s, uint64_t want, uint64_t seed) {
         for (int step = 0; step < 512; step++) {   // march(), rmr_trace.h march_update
             float p0[3];
             point_at(o, d, t, p0);
-            if (!rmr::trail_finite(p0[0], p0[1], p0[2]) || rmr::trail_linf(p0[0], p0[1], p0[2]) > 30.0f) break;
+            if (!rmr::trail_finite(p0[0], p0[1], p0[2]) ||
+                rmr::trail_linf(p0[0] - s.fr.c[0], p0[1] - s.fr.c[1], p0[2] - s.fr.c[2]) > s.fr.k * 30.0f)
+                break;
             float dx, dy;
             fold(s, p0, dx, dy);
             int w;
@@ -344,7 +361,7 @@ Tally run_scene(const Scene& s, uint64_t want, uint64_t seed) {
             // steps of any length ahead of the anchor
             for (int k = 0; k < 2; k++) {
                 float F;
-                attempt(s, c, o, d, anchor, t, t + g.uni() * 1.5f * fabsf(s2 == s2 && s2 < 100.0f ? s2 : 1.0f), w, T, F);
+                attempt(s, c, o, d, anchor, t, t + g.uni() * 1.5f * fabsf(s2 == s2 && s2 < s.fr.k * 100.0f ? s2 : s.fr.k), w, T, F);
             }
             t = tn;
         }
@@ -352,18 +369,97 @@ Tally run_scene(const Scene& s, uint64_t want, uint64_t seed) {
     return T;
 }
 
+// the frame of a scene read from a file: the box of its primitives, without those more than 100 times
+// the smallest one (a ground sphere of radius 10^4 says nothing about where the scene's surfaces meet);
+// k takes the compiled-in scenes' half-size of 4 to the box's
+Frame frame_of(const std::vector<Prim>& prims) {
+    auto size = [](const Prim& q) { return fmaxf(fabsf(q.r[0]), q.box ? fmaxf(fabsf(q.r[1]), fabsf(q.r[2])) : 0.0f); };
+    float least = INFINITY;
+    for (const Prim& q : prims) least = fminf(least, size(q));
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (const Prim& q : prims) {
+        if (size(q) > 100.0f * least) continue;
+        for (int k = 0; k < 3; k++) {
+            const float h = fabsf(q.box ? q.r[k] : q.r[0]);
+            lo[k] = fminf(lo[k], q.c[k] - h);
+            hi[k] = fmaxf(hi[k], q.c[k] + h);
+        }
+    }
+    Frame fr;
+    float half = 0.0f;
+    for (int k = 0; k < 3; k++) {
+        fr.c[k] = 0.5f * (lo[k] + hi[k]);
+        half = fmaxf(half, 0.5f * (hi[k] - lo[k]));
+    }
+    fr.k = half / 4.0f;
+    return fr;
+}
+
+bool read_scene(const char* path, Scene& s) {
+    std::FILE* f = std::fopen(path, "r");
+    if (!f) return false;
+    bool ok = std::fscanf(f, "%f", &s.max_dist) == 1;
+    while (ok) {
+        char kind;
+        Prim q{};
+        const int n = std::fscanf(f, " %c %f %f %f %f %f %f %f", &kind, &q.id, &q.c[0], &q.c[1], &q.c[2], &q.r[0], &q.r[1], &q.r[2]);
+        if (n == EOF) break;
+        ok = n == 8 && (kind == 'b' || kind == 's') && s.prims.size() < 64;
+        q.box = kind == 'b';
+        if (ok) s.prims.push_back(q);
+    }
+    std::fclose(f);
+    ok = ok && !s.prims.empty() && s.max_dist > 0.0f;
+    if (ok) s.fr = frame_of(s.prims);
+    return ok && s.fr.k > 0.0f && std::isfinite(s.fr.k);
+}
+
+void report(const Scene& s, const Tally& T) {
+    std::printf("%s maxDist %g: triples %llu accepted %llu (%.1f %%) hits %llu certified %llu certified hits %llu\n", s.name,
+                (double)s.max_dist, (unsigned long long)T.triples, (unsigned long long)T.accepted,
+                100.0 * (double)T.accepted / (double)T.triples, (unsigned long long)T.hits, (unsigned long long)T.certified,
+                (unsigned long long)T.cert_hits);
+}
+
+int run_file(const char* path) {
+    std::string name(path);
+    name = name.substr(name.find_last_of('/') + 1);
+    name = name.substr(0, name.find('.'));
+    Scene s{name.c_str(), {}, 0.0f, Frame{}};
+    if (!read_scene(path, s)) {
+        std::printf("FAIL %s: not a scene file (max_dist, then `b|s id cx cy cz rx ry rz` per primitive)\n", path);
+        return 2;
+    }
+    const uint64_t want = 200000ull;
+    const Tally T = run_scene(s, want, 0x5eed);
+    report(s, T);
+    uint64_t fails = T.fails;
+    if (T.triples < want) {
+        fails++;
+        std::printf("FAIL %s: fewer than %llu triples\n", s.name, (unsigned long long)want);
+    }
+    if (fails) {
+        std::printf("FAIL %llu violations\n", (unsigned long long)fails);
+        return 1;
+    }
+    std::printf("ok\n");
+    return 0;
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc == 3 && std::strcmp(argv[1], "--scene") == 0) return run_file(argv[2]);
+    if (argc != 1) {
+        std::printf("usage: trail_rule_test [--scene FILE]\n");
+        return 2;
+    }
     const Scene scenes[] = {cornell5(1000.0f), cornell5(6.0f), overlay("overlay2", 2.0f), overlay("overlay4", 4.0f), big_sphere()};
     uint64_t fails = 0;
     uint64_t seed = 0x5eed;
     for (const Scene& s : scenes) {
         const Tally T = run_scene(s, 1000000ull, seed++);
-        std::printf("%s maxDist %g: triples %llu accepted %llu (%.1f %%) hits %llu certified %llu certified hits %llu\n", s.name,
-                    (double)s.max_dist, (unsigned long long)T.triples, (unsigned long long)T.accepted,
-                    100.0 * (double)T.accepted / (double)T.triples, (unsigned long long)T.hits, (unsigned long long)T.certified,
-                    (unsigned long long)T.cert_hits);
+        report(s, T);
         fails += T.fails;
         if (T.triples < 1000000ull) {
             fails++;

@@ -20,26 +20,12 @@ from oracle import camera, oracle, scene_compile
 from raymarchrenderer_amd import Renderer, abi, time_schedule
 
 from .conftest import SCENES
+from .scene_family import H0, RECT0, W0, _box, _diffuse, _primary_dirs, _sphere   # noqa: F401 (other tests import them from here)
 
 pytestmark = pytest.mark.gpu
 
 CORNELL = os.path.join(SCENES, "cornell5.scene")
-W0, H0, RECT0 = 72, 40, (3, 5, 67, 38)   # the clip rect cuts 8x8 tiles on every side
 TUNINGS = [(1, 1), (8, 32), (20, 64)]
-
-
-def _diffuse(i, c):
-    return {"id": i, "total_vars": 2, "nodes": [{"name": "shader_diffuse", "inputs": [c], "outputs": [0, 1]}],
-            "color": 0, "dir": 1}
-
-
-def _box(mat, c, r):
-    return {"matID": mat, "total_vars": 1, "distance": 0, "nodes": [{"name": "map_box", "inputs": [-1, c, r], "outputs": [0]}]}
-
-
-def _sphere(mat, c, rad):
-    return {"matID": mat, "total_vars": 1, "distance": 0,
-            "nodes": [{"name": "map_sphere", "inputs": [-1, c, [rad, rad, rad]], "outputs": [0]}]}
 
 
 def overlay_scene(overlay_r):
@@ -63,21 +49,6 @@ def _same(a, b):
     a = np.asarray(a, np.float32)
     b = np.asarray(b, np.float32)
     return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-
-
-def _primary_dirs(view, W, H, rect):
-    """The rect's pixel rays without the jitter (RayMarch.glsl main: mix of the four corner rays)."""
-    v = np.asarray(view, np.float64)
-    r00, r01, r10, r11 = v[3:6], v[6:9], v[9:12], v[12:15]
-    x0, y0, x1, y1 = rect
-    out = []
-    for py in range(y0, y1):
-        for px in range(x0, x1):
-            u, w = px / W, py / H
-            top, bot = r00 + (r01 - r00) * u, r10 + (r11 - r10) * u
-            d = top + (bot - top) * w
-            out.append(d / np.linalg.norm(d))
-    return np.asarray(out, np.float32)
 
 
 def near_tie_share(scene):
