@@ -794,6 +794,85 @@ int rmr_query_rejects(rmr_ctx* ctx, uint64_t* out);
  * depend on it. RMR_E_INVALID for blocks < 0. */
 int rmr_set_query_grid(rmr_ctx* ctx, int blocks);
 
+/* ---- sampled AOVs: coverage, depth, normal, position and id mattes per pixel ------------------ */
+/* No counterpart in the reference. Additive: no other entry point changes.
+ *
+ * Per pixel, the first hits of the beauty samples' own primary rays, folded in sample order. Sample k
+ * of a call is seeded times[k], as in rmr_render_spp, and its ray is the context's camera model's: bit
+ * for bit what rmr_camera_rays returns and what the render of the same schedule traces first. Its hit is
+ * rmr_cast_rays' with RMR_CAST_NORMALS (pos, t, n, id), bit for bit; id < 0 is a miss (a far hit, an id
+ * found at t >= maxDist, is one).
+ *
+ * State: five W x H float4 planes (row 0 = top), 80 bytes per pixel.
+ *   RMR_AOV_STATS     (n, h, sum_t, min_t)  samples folded, hits among them, sum and min of t over the hits
+ *   RMR_AOV_NORMAL    (sum n.x, sum n.y, sum n.z, other)  other: hits whose id found no slot
+ *   RMR_AOV_POSITION  (sum pos.x, sum pos.y, sum pos.z, 0)
+ *   RMR_AOV_IDS01     (id0, c0, id1, c1)    four (material id, hit count) slots in the order the ids
+ *   RMR_AOV_IDS23     (id2, c2, id3, c3)    were first seen
+ * Initial state: every sum and count 0, min_t = +inf, every slot (-1, 0). Counts are float32, exact up
+ * to 2^24.
+ * Fold of one sample: n = n + 1; for a miss nothing else; for a hit h = h + 1, sum_t = sum_t + t,
+ * min_t = (t < min_t ? t : min_t), each component of sum n and sum pos gets its addend (one float32
+ * addition each, no fma); then the first slot j with id_j == id gets c_j = c_j + 1, else the first slot
+ * with id_j == -1 becomes (id, 1), else other = other + 1. The state is a function of the pixel's hit
+ * sequence alone: cutting a frame into calls, rects or launches does not change a bit of it.
+ *
+ * Resolve: five W x H float4 planes, float32, one IEEE operation per step:
+ *   RMR_AOV_R_DEPTH     (mean_t, min_t, alpha, n): alpha = n > 0 ? h / n : 0; mean_t = h > 0 ? sum_t / h
+ *                       : maxDist; min_t = h > 0 ? min_t : maxDist
+ *   RMR_AOV_R_NORMAL    (N / len, alpha) with N = sum n, len = sqrt((N.x N.x + N.y N.y) + N.z N.z), each
+ *                       component divided by len; (0, 0, 0, alpha) when h == 0 or len is 0 or not finite
+ *   RMR_AOV_R_POSITION  (sum pos / h, h), each component divided by h; (0, 0, 0, 0) when h == 0
+ *   RMR_AOV_R_IDS01, RMR_AOV_R_IDS23  the four slots sorted by count descending, then id ascending, each
+ *                       as (id, c / n); empty slots stay (-1, 0) and sort last
+ * maxDist: the context's params at the time of the resolve. */
+#define RMR_AOV_STATS 0
+#define RMR_AOV_NORMAL 1
+#define RMR_AOV_POSITION 2
+#define RMR_AOV_IDS01 3
+#define RMR_AOV_IDS23 4
+#define RMR_AOV_R_DEPTH 0
+#define RMR_AOV_R_NORMAL 1
+#define RMR_AOV_R_POSITION 2
+#define RMR_AOV_R_IDS01 3
+#define RMR_AOV_R_IDS23 4
+/* Folds the nspp samples seeded times[0 .. nspp) into the pixels of the integer rect [x0,x1) x [y0,y1)
+ * (clamped to the image; only pixels inside it are touched). restart != 0: the rect's pixels start from
+ * the initial state. nspp == 0 with times null: only the restart, if any. Works under all four camera
+ * models. Queued on the context's stream after the held rmr_render calls; does not synchronise. The
+ * accumulator, the half image, the estimate, the guides and every output stage are left as they are.
+ * The planes are allocated, in the initial state, at first use (RMR_E_NOMEM); rmr_reload, a scene load,
+ * rmr_set_image_size and rmr_destroy free them; rmr_set_view, rmr_set_params and rmr_set_camera_model
+ * keep them (the caller restarts, as with the accumulator).
+ * RMR_E_STATE without a scene; RMR_E_INVALID for nspp == 0 with times non-null, nspp > 0 with times null,
+ * and for a call that could take a pixel's n past 2^24 (counted as the samples of every call since the
+ * last rmr_aov_reset or whole-image restart). */
+int rmr_render_aov(rmr_ctx* ctx, const float* times, uint32_t nspp, int x0, int y0, int x1, int y1, int restart);
+/* The initial state everywhere; the planes are kept (nothing to do while there are none). */
+int rmr_aov_reset(rmr_ctx* ctx);
+/* One raw state plane (RMR_AOV_*) / one resolved plane (RMR_AOV_R_*), W x H x 4 floats; synchronise.
+ * RMR_E_STATE before the first rmr_render_aov since the planes were freed; RMR_E_INVALID for a bad
+ * plane or bytes != W x H x 16. */
+int rmr_read_aov(rmr_ctx* ctx, int plane, float* rgba, size_t bytes);
+int rmr_read_aov_resolved(rmr_ctx* ctx, int which, float* rgba, size_t bytes);
+/* The planes in device memory (null for a bad plane or a failed allocation). rmr_aov_device_ptr allocates
+ * the state at first use. rmr_aov_resolved_device_ptr queues the resolve of the current state on the
+ * context's stream (the resolved planes, 80 bytes per pixel more, are allocated at the first resolve) and
+ * is null before the first rmr_render_aov; the pointer's contents are valid until the next rmr_render_aov
+ * or rmr_aov_reset. No synchronisation. */
+void* rmr_aov_device_ptr(rmr_ctx* ctx, int plane);
+void* rmr_aov_resolved_device_ptr(rmr_ctx* ctx, int which);
+/* A call is cut into launches of at most n samples each (default 6), so that a launch stays short on a
+ * shared device. Scheduling only: the state does not depend on it. RMR_E_INVALID for n < 1. */
+int rmr_set_aov_launch_samples(rmr_ctx* ctx, int n);
+/* The rule on the host, no context and no GPU. state: [5][n_px][4] floats (the raw planes one after the
+ * other); hits[k][pixel], rmr_hit as rmr_cast_rays gives them with RMR_CAST_NORMALS; out: [5][n_px][4].
+ * rmr_aov_fold folds each pixel's nspp hits in the order k = 0, 1, ...; RMR_E_INVALID (nothing written)
+ * if a pixel's n would pass 2^24. */
+int rmr_aov_init(float* state, size_t n_px);
+int rmr_aov_fold(float* state, const rmr_hit* hits, size_t n_px, uint32_t nspp);
+int rmr_aov_resolve(const float* state, size_t n_px, float max_dist, float* out);
+
 /* ---- display ---------------------------------------------------------------------------- */
 /* Graphics::Display(centre, zoom, min, max) (Graphics.cpp:356-390 with createFQ 227-258 and
  * FullQuad.vs / FullQuad.fs), headless: draws the accumulator into a screen_w x screen_h RGBA8 image

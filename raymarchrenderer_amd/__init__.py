@@ -6,7 +6,7 @@ reference's Graphics / Camera / Screen host interfaces.
 """
 from . import abi
 from ._lib import RMRError, lib
-from .renderer import (Camera, Graphics, Renderer, Screen, adaptive_select, bloom_pixels, camera_frame, camera_view,
+from .renderer import (Camera, Graphics, Renderer, Screen, adaptive_select, aov_fold, aov_init, aov_resolve, bloom_pixels, camera_frame, camera_view,
                        check_bloom_params,
                        check_camera_model, check_rays, check_temporal_params, check_tonemap_params, default_camera_view,
                        encode_bmp, encode_pfm, exposure_from_histogram, luminance_bins, parity_schedule, save_name,
@@ -16,4 +16,5 @@ __all__ = ["abi", "lib", "RMRError", "Renderer", "Graphics", "Camera", "Screen",
            "default_camera_view", "encode_bmp", "encode_pfm", "tile_spiral", "time_schedule", "parity_schedule",
            "save_name", "adaptive_select", "camera_frame", "check_camera_model", "check_rays",
            "check_temporal_params", "temporal_view_inverse", "check_tonemap_params", "luminance_bins",
-           "exposure_from_histogram", "tonemap_pixels", "check_bloom_params", "bloom_pixels"]
+           "exposure_from_histogram", "tonemap_pixels", "check_bloom_params", "bloom_pixels", "aov_fold", "aov_resolve",
+           "aov_init"]

@@ -44,6 +44,8 @@ EXPORTS = [
     "rmr_luminance_bins", "rmr_exposure_from_histogram", "rmr_tonemap_pixels",
     "rmr_default_bloom_params", "rmr_check_bloom_params", "rmr_bloom", "rmr_read_bloom", "rmr_bloom_device_ptr",
     "rmr_bloom_pixels",
+    "rmr_render_aov", "rmr_aov_reset", "rmr_read_aov", "rmr_read_aov_resolved", "rmr_aov_device_ptr",
+    "rmr_aov_resolved_device_ptr", "rmr_set_aov_launch_samples", "rmr_aov_init", "rmr_aov_fold", "rmr_aov_resolve",
 ]
 
 
@@ -211,6 +213,16 @@ def lib(diag=None):
         "rmr_read_bloom": (C.c_int, [vp, fp, C.c_size_t]),
         "rmr_bloom_device_ptr": (vp, [vp]),
         "rmr_bloom_pixels": (C.c_int, [C.POINTER(abi.BloomParams), fp, C.c_int, C.c_int, fp]),
+        "rmr_render_aov": (C.c_int, [vp, fp, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "rmr_aov_reset": (C.c_int, [vp]),
+        "rmr_read_aov": (C.c_int, [vp, C.c_int, fp, C.c_size_t]),
+        "rmr_read_aov_resolved": (C.c_int, [vp, C.c_int, fp, C.c_size_t]),
+        "rmr_aov_device_ptr": (vp, [vp, C.c_int]),
+        "rmr_aov_resolved_device_ptr": (vp, [vp, C.c_int]),
+        "rmr_set_aov_launch_samples": (C.c_int, [vp, C.c_int]),
+        "rmr_aov_init": (C.c_int, [fp, C.c_size_t]),
+        "rmr_aov_fold": (C.c_int, [fp, C.c_void_p, C.c_size_t, C.c_uint32]),
+        "rmr_aov_resolve": (C.c_int, [fp, C.c_size_t, C.c_float, fp]),
         "rmr_diag_bloom_tail": (C.c_int, [vp, C.c_int]),
         "rmr_diag_bloom_time": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp]),
         "rmr_diag_tonemap_fold": (C.c_int, [vp, C.c_int]),

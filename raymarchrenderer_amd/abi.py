@@ -280,6 +280,20 @@ OUTPUT_TONEMAPPED = 3
 OUTPUT_BLOOM = 4
 OUTPUT_SOURCES = {"accum": OUTPUT_ACCUM, "denoised": OUTPUT_DENOISED, "temporal": OUTPUT_TEMPORAL,
                   "tonemapped": OUTPUT_TONEMAPPED, "bloom": OUTPUT_BLOOM}
+# sampled AOVs (rmr.h rmr_render_aov): the raw state planes and the resolved planes
+AOV_STATS = 0
+AOV_NORMAL = 1
+AOV_POSITION = 2
+AOV_IDS01 = 3
+AOV_IDS23 = 4
+AOV_PLANES = {"stats": AOV_STATS, "normal": AOV_NORMAL, "position": AOV_POSITION, "ids01": AOV_IDS01, "ids23": AOV_IDS23}
+AOV_R_DEPTH = 0
+AOV_R_NORMAL = 1
+AOV_R_POSITION = 2
+AOV_R_IDS01 = 3
+AOV_R_IDS23 = 4
+AOV_RESOLVED = {"depth": AOV_R_DEPTH, "normal": AOV_R_NORMAL, "position": AOV_R_POSITION, "ids01": AOV_R_IDS01,
+                "ids23": AOV_R_IDS23}
 # variance planes of the variance-guided denoiser (rmr.h)
 VARIANCE_SEED = 0
 VARIANCE_FILTERED = 1

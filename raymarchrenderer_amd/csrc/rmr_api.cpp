@@ -58,6 +58,9 @@ hipError_t launch_eval_map(const KParams& P, int np, const float* xyz, uint64_t 
 hipError_t launch_pack_rays(const rmr_ray* rays, uint64_t n, uint64_t u0, uint32_t units, float extent, float4* rec,
                             unsigned long long* rejects, unsigned long long* first_bad, hipStream_t s);
 hipError_t launch_unpack_rgba(const float4* samp, const float4* rec, float* out, uint32_t cnt, hipStream_t s);
+hipError_t launch_aov(const KParams& P, const CamParams& C, int np, float4* state, bool restart, hipStream_t s);
+hipError_t launch_aov_init(float4* state, size_t n_px, hipStream_t s);
+hipError_t launch_aov_resolve(const float4* state, size_t n_px, float max_dist, float4* out, hipStream_t s);
 }  // namespace rmr
 
 using rmr::CompiledScene;
@@ -71,6 +74,8 @@ constexpr int kSlotGridReserve = 32;   // workgroups a slotted launch leaves fre
 constexpr int kDenoiseTiledSteps = 3;
 // the same for the variance-guided passes (rmr_denoise_var.hip); DESIGN.md §4.11
 constexpr int kDenoiseVarTiledSteps = 3;
+// samples per launch of the sampled AOVs' kernel (rmr_set_aov_launch_samples); DESIGN.md §4.15
+constexpr int kAovLaunchSamples = 6;
 
 struct rmr_ctx {
     int device = 0;
@@ -128,6 +133,15 @@ struct rmr_ctx {
     void* d_qout = nullptr;
     size_t qin_cap = 0, qout_cap = 0;     // bytes
     int query_grid = 0;                   // rmr_set_query_grid: 0 = one thread per ray / point
+    // sampled AOVs (rmr_render_aov, rmr_aov.hip): the five state planes (one allocation,
+    // W x H float4 each, at first use) and the five resolved planes (at the first resolve); freed at
+    // rmr_reload, a scene load, rmr_set_image_size and rmr_destroy
+    float4* d_aov = nullptr;
+    float4* d_aov_res = nullptr;
+    bool aov_rendered = false;            // an rmr_render_aov since the planes were allocated
+    bool aov_res_valid = false;           // d_aov_res is (or is queued to be) the resolve of the current state
+    uint64_t aov_samples = 0;             // a bound on every pixel's n: samples since the last whole-image restart
+    int aov_launch_samples = kAovLaunchSamples;
     // which of the output stages' images below are valid: the one place that says so (stage_state.hpp)
     rmr::StageState st;
     // first-hit guides and the preview denoiser (rmr_render_guides / rmr_denoise): three guide planes and
@@ -422,6 +436,13 @@ void free_bloom(rmr_ctx* c) {
     c->st.bloom_reset();
 }
 
+// Release the sampled AOVs' planes (the caller has synced the context's stream).
+void free_aov(rmr_ctx* c) {
+    free_all({&c->d_aov, &c->d_aov_res});
+    c->aov_rendered = c->aov_res_valid = false;
+    c->aov_samples = 0;
+}
+
 // Release the half image and the tile-error map (the caller has synced the context's stream).
 void free_estimate(rmr_ctx* c) {
     free_all({&c->d_half, &c->d_tile_err});
@@ -539,6 +560,10 @@ int upload_scene(rmr_ctx* c) {
     a.grid.cells = {};
     a.grid.list = {};
     c->esc_infl_dev = -1.0;
+    if (c->d_aov) {   // the sampled AOVs are the old scene's
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        free_aov(c);
+    }
     c->scene_kp = scene_params(c);
     c->st.scene_loaded();   // (every scene load comes through here)
     c->scene_loaded = true;
@@ -1333,6 +1358,7 @@ void rmr_destroy(rmr_ctx* c) {
     free_temporal(c);
     free_tonemap(c);
     free_bloom(c);
+    free_aov(c);
     free_estimate(c);
     if (c->d_accum && !c->accum_external) (void)hipFree(c->d_accum);
     for (auto& k : c->jit_loaded)
@@ -1368,6 +1394,11 @@ int rmr_set_image_size(rmr_ctx* c, int w, int h) {
     if (w <= 0 || h <= 0 || w > 32768 || h > 32768) return fail(c, RMR_E_INVALID, "bad image size");
     c->pend_W = w;
     c->pend_H = h;
+    if (c->d_aov) {   // (the sampled AOVs are of the old size's image)
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        free_aov(c);
+    }
     // (the auto-exposure's adaptation state is of the old size's images)
     if (c->d_tm_state) HIPCHK(c, hipSetDevice(c->device));
     if (c->d_tm_state) HIPCHK(c, hipMemsetAsync(&c->d_tm_state->valid, 0, sizeof(uint32_t), c->stream));
@@ -1464,6 +1495,7 @@ int rmr_reload(rmr_ctx* c) {
     free_temporal(c);
     free_tonemap(c);
     free_bloom(c);
+    free_aov(c);
     c->W = c->pend_W;
     c->H = c->pend_H;
     if (resize) {
@@ -1998,6 +2030,22 @@ int rmr_get_camera_model(const rmr_ctx* c, rmr_camera_model* m) {
     return RMR_OK;
 }
 
+namespace {
+// The generator kernels' second argument from the context's camera model and view.
+int camera_params(rmr_ctx* c, rmr::CamParams& cam) {
+    const rmr_camera_model& m = c->camera;
+    cam = rmr::CamParams{};
+    cam.model = m.model;
+    cam.p[0] = m.aperture; cam.p[1] = m.focus; cam.p[2] = m.width; cam.p[3] = m.height;
+    float f[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const bool eye_rays = m.model == RMR_CAMERA_VIEW || (m.model == RMR_CAMERA_THIN_LENS && m.aperture == 0.0f);
+    if (!eye_rays && !rmr::camera_frame(c->view, f))
+        return fail(c, RMR_E_INVALID, "the view has no camera frame (rmr_camera_frame): the camera model needs one");
+    for (int k = 0; k < 3; k++) { cam.U[k] = f[k]; cam.V[k] = f[3 + k]; cam.F[k] = f[6 + k]; }
+    return RMR_OK;
+}
+}  // namespace
+
 int rmr_trace_rays(rmr_ctx* c, const rmr_ray* rays, size_t n, float* out_rgba) {
     if (!c || (n && (!rays || !out_rgba))) return RMR_E_INVALID;
     RMR_FLUSH(c);
@@ -2021,18 +2069,11 @@ int rmr_camera_rays(rmr_ctx* c, const float* times, uint32_t nspp, int x0, int y
     if (!rmr::clamp_rect(c->W, c->H, x0, y0, x1, y1) || nspp == 0) return RMR_OK;
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->view_set) default_view(c);
-    const rmr_camera_model& m = c->camera;
     rmr::CamParams cam{};
-    cam.model = m.model;
-    cam.p[0] = m.aperture; cam.p[1] = m.focus; cam.p[2] = m.width; cam.p[3] = m.height;
-    float f[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const bool eye_rays = m.model == RMR_CAMERA_VIEW || (m.model == RMR_CAMERA_THIN_LENS && m.aperture == 0.0f);
-    if (!eye_rays && !rmr::camera_frame(c->view, f))
-        return fail(c, RMR_E_INVALID, "the view has no camera frame (rmr_camera_frame): the camera model needs one");
-    for (int k = 0; k < 3; k++) { cam.U[k] = f[k]; cam.V[k] = f[3 + k]; cam.F[k] = f[6 + k]; }
+    int r;
+    if ((r = camera_params(c, cam))) return r;
     const std::vector<TileXY> tiles = rect_tiles(x0, y0, x1, y1);
     const TileXY* d_tiles = nullptr;
-    int r;
     if ((r = tile_list(c, tiles, &d_tiles))) return r;
     KParams P;
     if ((r = view_params(c, P))) return r;
@@ -2200,6 +2241,133 @@ int rmr_query_rejects(rmr_ctx* c, uint64_t* out) {
 int rmr_set_query_grid(rmr_ctx* c, int blocks) {
     if (!c || blocks < 0) return RMR_E_INVALID;
     c->query_grid = blocks;
+    return RMR_OK;
+}
+
+// ---- sampled AOVs (rmr_aov.hip, rmr_aov_rule.h) ---------------------------------
+namespace {
+constexpr uint64_t kAovMaxSamples = (uint64_t)1 << 24;   // float32 counts are exact up to here
+
+// The five state planes, in the initial state, at first use.
+int ensure_aov(rmr_ctx* c) {
+    if (c->d_aov) return RMR_OK;
+    const size_t n_px = (size_t)c->W * c->H;
+    if (const int r = alloc_all(c, {{&c->d_aov, 5 * n_px * sizeof(float4)}},
+                                "cannot allocate the sampled AOVs' state (W x H x 80 bytes)"))
+        return r;
+    c->aov_rendered = c->aov_res_valid = false;
+    c->aov_samples = 0;
+    HIPCHK(c, rmr::launch_aov_init(c->d_aov, n_px, c->stream));
+    return RMR_OK;
+}
+
+// The resolved planes of the current state, queued on the context's stream unless they are that already.
+int resolve_aov(rmr_ctx* c) {
+    if (!c->d_aov || !c->aov_rendered) return fail(c, RMR_E_STATE, "no sampled AOVs (call rmr_render_aov)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n_px = (size_t)c->W * c->H;
+    if (!c->d_aov_res) {
+        if (const int r = alloc_all(c, {{&c->d_aov_res, 5 * n_px * sizeof(float4)}},
+                                    "cannot allocate the sampled AOVs' resolved planes (W x H x 80 bytes)"))
+            return r;
+        c->aov_res_valid = false;
+    }
+    if (c->aov_res_valid) return RMR_OK;
+    HIPCHK(c, rmr::launch_aov_resolve(c->d_aov, n_px, c->params.max_dist, c->d_aov_res, c->stream));
+    c->aov_res_valid = true;
+    return RMR_OK;
+}
+
+bool aov_plane_ok(int plane) { return plane >= RMR_AOV_STATS && plane <= RMR_AOV_IDS23; }
+}  // namespace
+
+int rmr_render_aov(rmr_ctx* c, const float* times, uint32_t nspp, int x0, int y0, int x1, int y1, int restart) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if ((nspp == 0) != (times == nullptr))
+        return fail(c, RMR_E_INVALID, "rmr_render_aov: times and nspp must both be given or both be empty");
+    if (!c->scene_loaded) return fail(c, RMR_E_STATE, "no scene loaded (call rmr_load_scene_json / rmr_load_builtin_scene)");
+    const bool whole = rmr::clamp_rect(c->W, c->H, x0, y0, x1, y1) && x0 == 0 && y0 == 0 && x1 == c->W && y1 == c->H;
+    const uint64_t before = (restart && whole) ? 0 : c->aov_samples;
+    if (before + nspp > kAovMaxSamples)
+        return fail(c, RMR_E_INVALID, "rmr_render_aov: more than 2^24 samples per pixel (restart, or call rmr_aov_reset)");
+    HIPCHK(c, hipSetDevice(c->device));
+    int r;
+    if ((r = ensure_aov(c))) return r;
+    c->aov_rendered = true;
+    if (x0 >= x1 || y0 >= y1 || (nspp == 0 && !restart)) return RMR_OK;
+    if (!c->view_set) default_view(c);
+    rmr::CamParams cam{};
+    if ((r = camera_params(c, cam))) return r;
+    KParams P;
+    if ((r = view_params(c, P))) return r;
+    P.x0 = x0; P.y0 = y0; P.x1 = x1; P.y1 = y1;
+    c->aov_res_valid = false;
+    c->aov_samples = before + nspp;
+    const uint32_t per = (uint32_t)std::max(1, c->aov_launch_samples);
+    uint32_t k0 = 0;
+    do {   // (once with no samples for a bare restart)
+        const uint32_t n = std::min(per, nspp - k0);
+        const float* d_times = nullptr;
+        if (n > 1 && (r = stage_times(c, times + k0, n, &d_times))) return r;
+        P.nspp = n;
+        P.times = d_times;
+        P.time1 = n ? times[k0] : 0.0f;
+        HIPCHK(c, rmr::launch_aov(P, cam, c->accel.map_np, c->d_aov, restart != 0 && k0 == 0, c->stream));
+        k0 += n;
+    } while (k0 < nspp);
+    return RMR_OK;
+}
+
+int rmr_aov_reset(rmr_ctx* c) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    c->aov_samples = 0;
+    if (!c->d_aov) return RMR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->aov_res_valid = false;
+    HIPCHK(c, rmr::launch_aov_init(c->d_aov, (size_t)c->W * c->H, c->stream));
+    return RMR_OK;
+}
+
+int rmr_read_aov(rmr_ctx* c, int plane, float* rgba, size_t bytes) {
+    if (!c || !rgba) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!aov_plane_ok(plane)) return fail(c, RMR_E_INVALID, "bad sampled-AOV plane");
+    const size_t n_px = (size_t)c->W * c->H;
+    if (bytes != n_px * sizeof(float4)) return fail(c, RMR_E_INVALID, "rmr_read_aov: bytes must be W x H x 16");
+    if (!c->d_aov || !c->aov_rendered) return fail(c, RMR_E_STATE, "no sampled AOVs (call rmr_render_aov)");
+    HIPCHK(c, hipSetDevice(c->device));
+    return read_back(c, rgba, c->d_aov + (size_t)plane * n_px, bytes);
+}
+
+int rmr_read_aov_resolved(rmr_ctx* c, int which, float* rgba, size_t bytes) {
+    if (!c || !rgba) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!aov_plane_ok(which)) return fail(c, RMR_E_INVALID, "bad sampled-AOV plane");
+    const size_t n_px = (size_t)c->W * c->H;
+    if (bytes != n_px * sizeof(float4)) return fail(c, RMR_E_INVALID, "rmr_read_aov_resolved: bytes must be W x H x 16");
+    if (const int r = resolve_aov(c)) return r;
+    return read_back(c, rgba, c->d_aov_res + (size_t)which * n_px, bytes);
+}
+
+void* rmr_aov_device_ptr(rmr_ctx* c, int plane) {
+    if (!c || !aov_plane_ok(plane)) return nullptr;
+    if (!flushed(c)) return nullptr;
+    if (hipSetDevice(c->device) != hipSuccess || ensure_aov(c) != RMR_OK) return nullptr;
+    return (void*)(c->d_aov + (size_t)plane * c->W * c->H);
+}
+
+void* rmr_aov_resolved_device_ptr(rmr_ctx* c, int which) {
+    if (!c || !aov_plane_ok(which)) return nullptr;
+    if (!flushed(c)) return nullptr;
+    if (resolve_aov(c) != RMR_OK) return nullptr;
+    return (void*)(c->d_aov_res + (size_t)which * c->W * c->H);
+}
+
+int rmr_set_aov_launch_samples(rmr_ctx* c, int n) {
+    if (!c || n < 1) return RMR_E_INVALID;
+    c->aov_launch_samples = n;
     return RMR_OK;
 }
 

@@ -9,8 +9,8 @@
 // Like the guide pass: the scene's table-driven map class, no RNG, no escape bound, no approximate map,
 // so every class gives the oracle's march / getNormal / map bits.
 #include <hip/hip_runtime.h>
+#include "rmr_cast.h"
 #include "rmr_ray_check.h"
-#include "rmr_trace.h"
 
 static_assert(sizeof(rmr_hit) == 32, "rmr_hit is the guide planes' HIT and NORMAL of one ray: 32 bytes");
 static_assert(sizeof(rmr_ray) == 40, "rmr_ray is 40 bytes");
@@ -36,33 +36,6 @@ RMR_D void store_rejected(rmr_hit* out) {
     *out = h;
 }
 
-// getNormal at the hits of a wave (k_guides' loop): probes +x, -x, +y, -y, +z, -z with probe_point's
-// offsets and signed zeros, then normalize. Wave-uniform outside the per-lane guard.
-template <class MAP>
-RMR_D V3 hit_normal(const KParams& P, bool is_hit, V3 pos) {
-    V3 n = v3(0.0f, 0.0f, 0.0f);
-    if (__ballot(is_hit)) {
-        float plus = 0.0f;
-#pragma unroll 1
-        for (int c = 0; c < 6; c++) {
-            const int ax = c >> 1;
-            const bool neg = (c & 1) != 0;
-            const float hs = neg ? -0.001f : 0.001f, z0 = neg ? -0.0f : 0.0f;
-            if (is_hit) {
-                const V3 q = v3(pos.x + (ax == 0 ? hs : z0), pos.y + (ax == 1 ? hs : z0), pos.z + (ax == 2 ? hs : z0));
-                const float m = MAP::eval(P, q).x;
-                const float dv = plus - m;
-                plus = neg ? plus : m;
-                n.x = (neg && ax == 0) ? dv : n.x;
-                n.y = (neg && ax == 1) ? dv : n.y;
-                n.z = (neg && ax == 2) ? dv : n.z;
-            }
-        }
-        if (is_hit) n = normalize(n);
-    }
-    return n;
-}
-
 // One ray per thread, strided over the grid by whole waves (a wave's trip count is uniform). A ray the
 // rule rejects gets (0, 0, 0, -1, 0, 0, 0, -2) and is counted.
 template <int NP, bool NORMALS>
@@ -80,27 +53,8 @@ __global__ __launch_bounds__(256) void k_cast_rays(KParams P, const rmr_ray* ray
         note_rejects(have && !ok, i, rejects, first_bad);
         const V3 o = v3(r.o[0], r.o[1], r.o[2]), dir = v3(r.d[0], r.d[1], r.d[2]);
 
-        // march(o, dir, +1): the hit test comes before the t >= maxDist test (a far hit keeps its t)
-        float t = 0.0f, id = -1.0f;
-        bool done = !ok;
-        for (int s = 0; s < P.max_steps; s++) {
-            if (!__ballot(!done)) break;
-            if (!done) {
-                const V2 m = MAP::eval(P, vfma(dir, t, o));
-                if (m.x < 0.001f) {
-                    id = m.y;
-                    done = true;
-                } else if (t >= P.max_dist) {
-                    t = P.max_dist;
-                    done = true;
-                } else {
-                    t = fmaf(m.x, P.step_mult, t);
-                }
-            }
-        }
-        if (!done) { t = P.max_dist; id = -1.0f; }   // fell out of the loop: (maxDist, -1)
-        const bool is_hit = ok && t < P.max_dist;
-        if (!is_hit) id = -1.0f;
+        float t, id;
+        const bool is_hit = march_first_hit<MAP>(P, ok, o, dir, t, id);
         const V3 pos = vfma(dir, t, o);
         V3 nn = v3(0.0f, 0.0f, 0.0f);
         if constexpr (NORMALS) nn = hit_normal<MAP>(P, is_hit, pos);

@@ -64,6 +64,7 @@ struct Options {
     rmr_bloom_params bloom_p{};
     double variance_guided = -1.0;  // --variance-guided [SIGMA_L]: the guided filter's sigma_l, < 0 = the plain filter
     std::string aov;                // --aov PREFIX: guide planes as PREFIX_*.pfm
+    std::string sampled_aov;        // --sampled-aov PREFIX: the sampled AOVs as PREFIX_*.pfm
     double adaptive = -1.0;         // --adaptive T: the tile-error threshold, < 0 = uniform sampling
     int min_samples = 16, pass_samples = 16;   // --min-samples / --pass-samples (rmr_adaptive_params)
     bool have_camera = false;
@@ -341,6 +342,47 @@ bool write_aovs(const Options& o) {
     return true;
 }
 
+// --sampled-aov PREFIX: the render's own sample schedule folded into the sampled AOVs (rmr_render_aov), the
+// resolved planes as float images: PREFIX_alpha.pfm (R = alpha, G = samples, B = hits), PREFIX_depth.pfm
+// (R = mean t, G = min t), PREFIX_normal.pfm, PREFIX_position.pfm (the planes' xyz) and PREFIX_ids.pfm
+// (R, G = id0, coverage0; B = id1)
+bool write_sampled_aovs(const Options& o) {
+    rmr_ctx* c = Graphics::context();
+    const int W = (int)Graphics::getImageSize().x, H = (int)Graphics::getImageSize().y;
+    auto fail = [&](const std::string& what) {
+        std::cerr << "--sampled-aov: " << what << ": " << rmr_last_error(c) << std::endl;
+        return false;
+    };
+    const unsigned ns = o.samples > 0 ? (unsigned)o.samples : (unsigned)o.passes;
+    std::vector<float> times(ns);
+    for (unsigned s = 0; s < ns; s++) times[s] = seed_time(o.frame, s);
+    if (rmr_render_aov(c, ns ? times.data() : nullptr, ns, 0, 0, W, H, 1) != RMR_OK) return fail("rmr_render_aov");
+    const size_t n = (size_t)W * H * 4;
+    std::vector<float> depth(n), nrm(n), pos(n), ids(n), alpha(n, 0.0f);
+    if (rmr_read_aov_resolved(c, RMR_AOV_R_DEPTH, depth.data(), n * sizeof(float)) != RMR_OK ||
+        rmr_read_aov_resolved(c, RMR_AOV_R_NORMAL, nrm.data(), n * sizeof(float)) != RMR_OK ||
+        rmr_read_aov_resolved(c, RMR_AOV_R_POSITION, pos.data(), n * sizeof(float)) != RMR_OK ||
+        rmr_read_aov_resolved(c, RMR_AOV_R_IDS01, ids.data(), n * sizeof(float)) != RMR_OK)
+        return fail("rmr_read_aov_resolved");
+    for (size_t i = 0; i < (size_t)W * H; i++) {
+        alpha[4 * i] = depth[4 * i + 2];
+        alpha[4 * i + 1] = depth[4 * i + 3];
+        alpha[4 * i + 2] = pos[4 * i + 3];
+        depth[4 * i + 2] = 0.0f;
+    }
+    const struct { const char* name; const std::vector<float>* img; } files[] = {
+        {"_alpha.pfm", &alpha}, {"_depth.pfm", &depth}, {"_normal.pfm", &nrm}, {"_position.pfm", &pos}, {"_ids.pfm", &ids}};
+    for (const auto& f : files) {
+        const std::string path = o.sampled_aov + f.name;
+        if (rmr_encode_pfm(f.img->data(), W, H, path.c_str()) != RMR_OK) {
+            std::cerr << "--sampled-aov: cannot write " << path << std::endl;
+            return false;
+        }
+        if (!o.quiet) std::cout << "Saved plane as: " << path << std::endl;
+    }
+    return true;
+}
+
 void report(const Options& o, const RenderResult& r) {
     std::cout << "Render Time: " << r.seconds << std::endl;  // Program.cpp:297
     if (!o.quiet && r.seconds > 0)
@@ -451,6 +493,10 @@ void usage() {
         "                      0.18); alone it implies --tonemap aces; not with --gpus / --devices\n"
         "  --aov PREFIX        first-hit planes as float PFM: PREFIX_normal.pfm, PREFIX_position.pfm,\n"
         "                      PREFIX_ray.pfm, PREFIX_depth_id.pfm (R = t, G = material id or -1, B = 0)\n"
+        "  --sampled-aov PREFIX  the render's own samples' first hits folded per pixel (anti-aliased, every\n"
+        "                      --camera model): PREFIX_alpha.pfm (R = alpha, G = samples, B = hits),\n"
+        "                      PREFIX_depth.pfm (R = mean t, G = min t), PREFIX_normal.pfm, PREFIX_position.pfm,\n"
+        "                      PREFIX_ids.pfm (R, G = id0, coverage0; B = id1); not with --gpus / --devices\n"
         "  --adaptive T        adaptive sampling: render until every block's tile error is <= T, at most\n"
         "                      --samples per pixel, over the whole image; prints passes, mean spp, open tiles\n"
         "                      and max error; with --aov also PREFIX_spp.pfm (R = samples) and PREFIX_error.pfm\n"
@@ -598,6 +644,10 @@ bool parse(int argc, char** argv, Options& o) {
             o.aov = next("--aov");
             if (o.aov.empty()) return false;
         }
+        else if (a == "--sampled-aov") {
+            o.sampled_aov = next("--sampled-aov");
+            if (o.sampled_aov.empty()) return false;
+        }
         else if (a == "--adaptive") {
             char* end = nullptr;
             const char* v = next("--adaptive");
@@ -704,6 +754,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--camera equirect / ortho: no --denoise and no --aov (no first-hit guides for these models)\n");
         return 2;
     }
+    if (!o.sampled_aov.empty() && (!o.devices.empty() || o.interactive)) {
+        std::fprintf(stderr, "--sampled-aov: not with --gpus / --devices or --interactive\n");
+        return 2;
+    }
     Screen::setScreenSize(Vector2(1280, 720));  // Program.cpp:89
     Graphics::setDevice(o.device);
     if (!o.devices.empty()) {
@@ -765,6 +819,7 @@ int main(int argc, char** argv) {
     save(o);
     int rc = Graphics::lastStatus() == RMR_OK ? 0 : 1;
     if (rc == 0 && !o.aov.empty() && !write_aovs(o)) rc = 1;
+    if (rc == 0 && !o.sampled_aov.empty() && !write_sampled_aovs(o)) rc = 1;
     Graphics::Shutdown();
     return rc;
 }

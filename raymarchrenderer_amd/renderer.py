@@ -76,6 +76,7 @@ class Renderer:
         rc = self._L.rmr_create(C.byref(self._ctx), device)
         if rc != abi.RMR_OK:
             raise RMRError(rc, "rmr_create failed (no HIP device %d?)" % device)
+        self._device = int(device)
         self.set_image_size(width, height)
         self.reload()
         self.variant = None
@@ -364,6 +365,82 @@ class Renderer:
     def set_query_grid(self, blocks):
         """rmr_set_query_grid: cap the cast / eval kernels' grid (0: automatic). Scheduling only."""
         self._chk(self._L.rmr_set_query_grid(self._ctx, int(blocks)))
+
+    # -- sampled AOVs: coverage, depth, normal, position and id mattes (rmr.h; DESIGN.md §4.15) --
+    def render_aov(self, times, rect=None, restart=False):
+        """rmr_render_aov: fold the first hits of the samples seeded `times` (the beauty render's own
+        primary rays under the current camera model) into the rect's pixels; restart=True starts the rect
+        from the initial state. Queued on the context's stream, no sync."""
+        times = np.ascontiguousarray(times if times is not None else [], np.float32).reshape(-1)
+        if rect is None:
+            w, h = self.image_size()
+            rect = (0, 0, w, h)
+        x0, y0, x1, y1 = (int(v) for v in rect)
+        self._chk(self._L.rmr_render_aov(self._ctx, _fp(times) if len(times) else None, len(times), x0, y0, x1, y1,
+                                         1 if restart else 0))
+
+    def aov_reset(self):
+        """rmr_aov_reset: the initial state everywhere."""
+        self._chk(self._L.rmr_aov_reset(self._ctx))
+
+    def set_aov_launch_samples(self, n):
+        """rmr_set_aov_launch_samples: most samples per kernel launch of render_aov. Scheduling only."""
+        self._chk(self._L.rmr_set_aov_launch_samples(self._ctx, int(n)))
+
+    @staticmethod
+    def _aov_plane(who, plane, names):
+        if isinstance(plane, str):
+            if plane not in names:
+                raise ValueError("%s: unknown plane %r (%s)" % (who, plane, ", ".join(names)))
+            plane = names[plane]
+        return int(plane)
+
+    def read_aov_raw(self, plane):
+        """One raw state plane as (H, W, 4) float32; plane: abi.AOV_* or 'stats' / 'normal' / 'position' /
+        'ids01' / 'ids23'."""
+        plane = self._aov_plane("read_aov_raw", plane, abi.AOV_PLANES)
+        w, h = self.image_size()
+        out = np.zeros((h, w, 4), np.float32)
+        self._chk(self._L.rmr_read_aov(self._ctx, plane, _fp(out), out.nbytes))
+        return out
+
+    def read_aov_resolved(self, which):
+        """One resolved plane as (H, W, 4) float32; which: abi.AOV_R_* or 'depth' / 'normal' / 'position' /
+        'ids01' / 'ids23'."""
+        which = self._aov_plane("read_aov_resolved", which, abi.AOV_RESOLVED)
+        w, h = self.image_size()
+        out = np.zeros((h, w, 4), np.float32)
+        self._chk(self._L.rmr_read_aov_resolved(self._ctx, which, _fp(out), out.nbytes))
+        return out
+
+    def read_aov(self):
+        """The resolved AOVs as a dict of float32 arrays: alpha, depth (mean t), min_depth, samples, hits,
+        other (H, W); normal, position (H, W, 3); ids and coverage (H, W, 4), the four id slots sorted by
+        coverage (-1: empty)."""
+        depth = self.read_aov_resolved(abi.AOV_R_DEPTH)
+        nrm = self.read_aov_resolved(abi.AOV_R_NORMAL)
+        pos = self.read_aov_resolved(abi.AOV_R_POSITION)
+        s01, s23 = self.read_aov_resolved(abi.AOV_R_IDS01), self.read_aov_resolved(abi.AOV_R_IDS23)
+        slots = np.concatenate([s01, s23], axis=2)
+        return {"alpha": depth[..., 2].copy(), "depth": depth[..., 0].copy(), "min_depth": depth[..., 1].copy(),
+                "normal": nrm[..., :3].copy(), "position": pos[..., :3].copy(), "samples": depth[..., 3].copy(),
+                "hits": pos[..., 3].copy(), "ids": slots[..., 0::2].copy(), "coverage": slots[..., 1::2].copy(),
+                "other": self.read_aov_raw(abi.AOV_NORMAL)[..., 3].copy()}
+
+    def aov_device(self):
+        """rmr_aov_resolved_device_ptr: the resolved planes as torch tensors on the context's device, a dict
+        'depth' / 'normal' / 'position' / 'ids01' / 'ids23' of (H, W, 4) float32 views of the library's
+        memory: no copy, no sync (the resolve is queued on the context's stream). Valid until the next
+        render_aov, aov_reset, reload or scene load."""
+        import torch
+        w, h = self.image_size()
+        out = {}
+        for name, which in abi.AOV_RESOLVED.items():
+            ptr = self._L.rmr_aov_resolved_device_ptr(self._ctx, which)
+            if not ptr:
+                raise RMRError(-5, (self._L.rmr_last_error(self._ctx) or b"").decode(errors="replace"))
+            out[name] = torch.as_tensor(_DeviceArray(ptr, (h, w, 4), self), device="cuda:%d" % self._device)
+        return out
 
     def sync(self):
         self._chk(self._L.rmr_sync(self._ctx))
@@ -877,6 +954,51 @@ def bloom_pixels(rgba, params=None, **fields):
     rc = lib().rmr_bloom_pixels(C.byref(p), _fp(a), a.shape[1], a.shape[0], _fp(out))
     if rc != abi.RMR_OK:
         raise RMRError(rc, "rmr_bloom_pixels: bad params or image")
+    return out
+
+
+class _DeviceArray:
+    """A float32 array in the library's device memory, for torch.as_tensor (no copy); keeps its owner alive."""
+
+    def __init__(self, ptr, shape, owner):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4", "data": (int(ptr), False),
+                                         "strides": None, "version": 2}
+
+
+def aov_init(n_px):
+    """rmr_aov_init (no GPU): the sampled AOVs' initial state of n_px pixels, (5, n_px, 4) float32."""
+    state = np.zeros((5, int(n_px), 4), np.float32)
+    rc = lib().rmr_aov_init(_fp(state), int(n_px))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_aov_init")
+    return state
+
+
+def aov_fold(state, hits):
+    """rmr_aov_fold (no GPU): fold hits[k][pixel], a (nspp, n_px) structured array of abi.HIT_DTYPE (any
+    shape (nspp, ...) with n_px values per sample), into a copy of the (5, n_px, 4) state, sample 0 first."""
+    st = np.array(state, np.float32, order="C")
+    if st.ndim != 3 or st.shape[0] != 5 or st.shape[2] != 4:
+        raise ValueError("aov_fold: a (5, n_px, 4) state, got shape %r" % (st.shape,))
+    n_px = st.shape[1]
+    h = np.ascontiguousarray(hits, np.dtype(abi.HIT_DTYPE))
+    h = h.reshape(-1, n_px) if n_px else h.reshape(0, 0)
+    rc = lib().rmr_aov_fold(_fp(st), h.ctypes.data, n_px, len(h))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_aov_fold: a pixel's sample count would pass 2^24")
+    return st
+
+
+def aov_resolve(state, max_dist):
+    """rmr_aov_resolve (no GPU): the five resolved planes (5, n_px, 4) of a (5, n_px, 4) state."""
+    st = np.ascontiguousarray(state, np.float32)
+    if st.ndim != 3 or st.shape[0] != 5 or st.shape[2] != 4:
+        raise ValueError("aov_resolve: a (5, n_px, 4) state, got shape %r" % (st.shape,))
+    out = np.zeros_like(st)
+    rc = lib().rmr_aov_resolve(_fp(st), st.shape[1], C.c_float(max_dist), _fp(out))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_aov_resolve")
     return out
 
 
