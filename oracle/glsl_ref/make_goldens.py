@@ -5,7 +5,8 @@ the reference GLSL (RayMarch*.glsl from /root/reference) on Mesa llvmpipe in thi
 
 Fixtures are data (inputs + reference outputs); the reference source itself is not stored.
   kat_<scene>.npz   function-level known answers: map / march / getNormal / rand chain /
-                    randHemisphere on fixed input sets (+ wavelengthToColor for RM3)
+                    randHemisphere on fixed input sets (+ wavelengthToColor for RM3; + edge_in / edge_out for
+                    trig_nodes: map with NaN and +-inf objects)
   img_<name>.npz    low-spp renders (4 spp) and converged renders (--conv-spp) of 64x48 images
   display_ref.npz   Graphics::Display (FullQuad.vs / .fs, GL_FRAMEBUFFER_SRGB, blend) drawn screens
 MANIFEST.json records every configuration, the camera, the seed schedule and the GL driver.
@@ -49,6 +50,8 @@ IMAGES = {
     "rm1_mandelbulb_b2": (os.path.join(ROOT, "scenes", "mandelbulb.scene"), 1, {"max_bounces": 2}, 65536),
     # C4's generator cut to 64 primitives (the reference codegen compiles it; 256 does not finish)
     "rm1_csg64_b4": (os.path.join(ROOT, "scenes", "csg64.scene"), 1, {"max_bounces": 4}, 32768),
+    # math_sine / math_cosine / misc_getX / misc_getZ, real divisors, products of variables (tests/node_family.py trig)
+    "rm1_trig_nodes_b3": (os.path.join(ROOT, "scenes", "trig_nodes.scene"), 1, {"max_bounces": 3}, 65536),
 }
 KATS = {
     "rm3": (None, 3),
@@ -57,6 +60,7 @@ KATS = {
     "csg_nodes": (os.path.join(ROOT, "scenes", "csg_nodes.scene"), 1),
     "mandelbulb": (os.path.join(ROOT, "scenes", "mandelbulb.scene"), 1),
     "csg64": (os.path.join(ROOT, "scenes", "csg64.scene"), 1),
+    "trig_nodes": (os.path.join(ROOT, "scenes", "trig_nodes.scene"), 1),
 }
 
 
@@ -94,6 +98,13 @@ def make_kat(name, path, variant, rng):
         wls = np.arange(360, 860, dtype=np.float32)
         out["wl_in"] = wls
         out["wl_out"] = ref_run.wl2rgb_probe(wls)
+    if name == "trig_nodes":
+        # opU with one object NaN or +-inf beside finite ones: map of the nan_objects case of
+        # tests/node_family.py at its hand-computed points, through the same map probe
+        from tests import node_family
+        edge = node_family.nan_rule_points()
+        out["edge_in"] = edge
+        out["edge_out"] = ref_run.probe(1, node_family.scene("nan_objects"), 0, edge, len(edge), 2, prm)
     np.savez_compressed(os.path.join(GOLDEN, "kat_%s.npz" % name), **out)
 
 
@@ -218,11 +229,16 @@ def main():
     man.setdefault("kat", {})
     man.setdefault("images", {})
     rng = np.random.default_rng(20251015)
-    for name, (path, variant) in KATS.items():
+    for k, (name, (path, variant)) in enumerate(KATS.items()):
         if args.only and "kat_" + name not in args.only.split(","):
             continue
-        make_kat(name, path, variant, rng)
+        # the first six fixtures were drawn from one shared stream in this order; a later one has a stream of
+        # its own, so that --only does not hand it the inputs of another fixture (the pooled hemisphere
+        # test would see those samples twice)
+        make_kat(name, path, variant, rng if k < 6 else np.random.default_rng([20251015, k]))
         man["kat"][name] = {"scene": os.path.relpath(path, ROOT) if path else "builtin", "variant": variant}
+        if name == "trig_nodes":
+            man["kat"][name]["edge"] = "map of tests/node_family.py nan_objects at nan_rule_points() (NaN and +-inf objects)"
         print("kat", name, flush=True)
     if not args.only or "display" in args.only.split(","):
         make_display()

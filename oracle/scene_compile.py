@@ -139,8 +139,16 @@ def _op(code, ins=(), outs=()):
 
 
 def _vec_literal(v):
+    """A literal whose float32 value is not finite prints as "inf" / "nan", which is no GLSL literal:
+    the reference's shader compile fails (probed on llvmpipe with oracle/glsl_ref/shader_build.py)."""
     v = list(v) + [0, 0, 0]
-    return tuple(quant_v1(v[i]) if v[i] is not None else 0.0 for i in range(3))
+    try:
+        out = tuple(quant_v1(v[i]) if v[i] is not None else 0.0 for i in range(3))
+    except OverflowError:   # struct.pack("f") of a finite double beyond float32
+        out = (float("inf"),)
+    if not all(np.isfinite(x) for x in out):
+        raise SceneError("literal %r is not a finite float: vec3(inf, ...) does not compile" % (v[:3],))
+    return out
 
 
 def _total_vars(obj, what):

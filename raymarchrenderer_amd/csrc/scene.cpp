@@ -77,8 +77,13 @@ struct Builder {
     }
 };
 
-void literal3(const json::Value& a, float out[3]) {  // "vec3(%f, %f, %f)" of a JSON array
-    for (int i = 0; i < 3; i++) out[i] = quant_v1(a[i].as_double());
+// "vec3(%f, %f, %f)" of a JSON array. A number whose float value is not finite prints as "inf" / "nan",
+// which is no GLSL literal: the reference's shader compile fails on it
+void literal3(const json::Value& a, float out[3]) {
+    for (int i = 0; i < 3; i++) {
+        out[i] = quant_v1(a[i].as_double());
+        if (!std::isfinite(out[i])) throw SceneError("a literal is not a finite float: vec3(inf, ...) does not compile");
+    }
 }
 
 int total_vars(const json::Value& o, const std::string& what) {

@@ -49,6 +49,8 @@ CASES = [
     # through the BVH + nearest-primitive cache
     ("rm1_csg_nodes_b4", os.path.join(SCENES, "csg_nodes.scene"), "rm1", {"max_bounces": 4}),
     ("rm1_csg64_b4", os.path.join(SCENES, "csg64.scene"), "rm1", {"max_bounces": 4}),
+    # math_sine / math_cosine / misc_getX / misc_getZ, real divisors, products of variables (tests/node_family.py trig)
+    ("rm1_trig_nodes_b3", os.path.join(SCENES, "trig_nodes.scene"), "rm1", {"max_bounces": 3}),
 ]
 
 

@@ -22,7 +22,10 @@ KATS = {"rm3": (None, "rm3"), "cornell5": (os.path.join(SCENES, "cornell5.scene"
         # C3's Mandelbulb node added to the reference path (oracle/glsl_ref/shader_build.py X1)
         "mandelbulb": (os.path.join(SCENES, "mandelbulb.scene"), "rm1"),
         # C4's generator cut to 64 primitives (the BVH / nearest-primitive-cache scene size class)
-        "csg64": (os.path.join(SCENES, "csg64.scene"), "rm1")}
+        "csg64": (os.path.join(SCENES, "csg64.scene"), "rm1"),
+        # math_sine / math_cosine / misc_getX / misc_getZ, real divisors, products of two and three variables
+        # (the trig case of tests/node_family.py)
+        "trig_nodes": (os.path.join(SCENES, "trig_nodes.scene"), "rm1")}
 
 
 def _tables(path, variant):
@@ -85,6 +88,21 @@ def test_kat_nan_direction_semantics(name):
         a = oracle.march(t, o, nan3, 1.0)
         b = oracle.march(t, o, nan3, -1.0)
         np.testing.assert_array_equal(np.concatenate([m, a, b]), r)
+
+
+def test_kat_nan_and_infinite_objects_exact():
+    """opU with one object NaN or +-inf beside finite ones, on the reference as llvmpipe runs it: map of the
+    nan_objects case of tests/node_family.py at its hand-computed points (edge_in / edge_out of the trig_nodes
+    fixture, through the ordinary map probe). The oracle returns the same distance and id, float for
+    float: a NaN object never becomes the distance but takes the id, -inf is the distance, +inf never wins."""
+    from . import node_family
+    k = np.load(os.path.join(GOLDEN, "kat_trig_nodes.npz"))
+    assert np.array_equal(k["edge_in"].view(np.uint32), node_family.nan_rule_points().view(np.uint32))
+    t = node_family.tables("nan_objects")
+    out = np.array([oracle.map_p(t, p) for p in k["edge_in"]])
+    ref = k["edge_out"]
+    assert not np.isnan(ref).any() and np.isneginf(ref[:, 0]).sum() == 2
+    np.testing.assert_array_equal(out, ref)
 
 
 def test_kat_wavelength_to_color_exact():
@@ -233,6 +251,7 @@ IMAGES = {
     "rm1_csg64_b4": (os.path.join(SCENES, "csg64.scene"), "rm1", {"max_bounces": 4}),
     "rm1_csg_nodes_b4": (os.path.join(SCENES, "csg_nodes.scene"), "rm1", {"max_bounces": 4}),
     "rm1_mandelbulb_b2": (os.path.join(SCENES, "mandelbulb.scene"), "rm1", {"max_bounces": 2}),
+    "rm1_trig_nodes_b3": (os.path.join(SCENES, "trig_nodes.scene"), "rm1", {"max_bounces": 3}),
 }
 
 

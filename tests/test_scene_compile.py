@@ -73,6 +73,15 @@ def test_opu_order_and_program_objects():
     {"materials": [{"id": 0, "total_vars": 1, "color": 3, "nodes": []}]},           # vars[3] of vars[1]
     {"objects": [{"matID": 0, "total_vars": 1, "distance": 0,
                   "nodes": [{"name": "map_box", "inputs": [-1, [0, 0, 0]], "outputs": [0]}]}]},
+    # a literal beyond float32 prints as vec3(..., inf, ...), which llvmpipe's GLSL compiler refuses
+    # (probed with oracle/glsl_ref/shader_build.py): a primitive's centre, a program's operand, a material's
+    {"objects": [{"matID": 0, "total_vars": 1, "distance": 0,
+                  "nodes": [{"name": "map_box", "inputs": [-1, [0, 1e39, 3], [1, 1, 1]], "outputs": [0]}]}]},
+    {"objects": [{"matID": 0, "total_vars": 2, "distance": 1,
+                  "nodes": [{"name": "math_multiply", "inputs": [-1, [1, -1e39, 1]], "outputs": [0]},
+                            {"name": "map_sphere", "inputs": [0, [0, 0, 0], [1, 1, 1]], "outputs": [1]}]}]},
+    {"materials": [{"id": 0, "total_vars": 2, "color": 0, "dir": 1,
+                    "nodes": [{"name": "shader_diffuse", "inputs": [[0.5, 3.5e38, 0.5]], "outputs": [0, 1]}]}]},
 ])
 def test_rejects_what_glsl_rejects(bad):
     with pytest.raises(RMRError):
