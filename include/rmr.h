@@ -873,6 +873,104 @@ int rmr_aov_init(float* state, size_t n_px);
 int rmr_aov_fold(float* state, const rmr_hit* hits, size_t n_px, uint32_t nspp);
 int rmr_aov_resolve(const float* state, size_t n_px, float max_dist, float* out);
 
+/* ---- SDF volume sampling and surface-nets mesh extraction ---------------------------------- */
+/* No counterpart in the reference. Additive: no other entry point changes.
+ *
+ * A lattice of n[0] x n[1] x n[2] points. Point (ix, iy, iz) has the float32 coordinates
+ *   origin[a] + (float)i_a * spacing       (the product rounded, then the sum rounded: no fused multiply-add)
+ * and the linear index ix + n[0] * (iy + n[1] * iz), x fastest. */
+typedef struct rmr_volume_desc {
+    float origin[3];
+    float spacing;
+    int32_t n[3];
+} rmr_volume_desc;
+/* No context and no GPU. RMR_OK iff every number is finite, spacing > 0, 2 <= n[a] <= 4096 and the point
+ * count is <= 2^30; otherwise RMR_E_INVALID, and *bad_field (when bad_field is not NULL) names the first
+ * failing field: "origin", "spacing", "n" or "points" (a static string; NULL for RMR_OK, "desc" for a
+ * NULL descriptor). */
+int rmr_check_volume(const rmr_volume_desc* desc, const char** bad_field);
+/* dist[k], id[k] = map(point k) as rmr_eval_map states it (the fold from (maxDist, -1); a NaN gives what
+ * map() gives), by one kernel through the scene's table-driven map class that computes its points itself:
+ * no point list, 4 bytes written per point, 8 with id. id may be NULL. Host memory, n[0] n[1] n[2] floats
+ * each. State rules as rmr_cast_rays: flushes held rmr_render calls, runs on the context's stream and
+ * synchronises; the accumulator, the half image, the estimate, the guides, every stage image, the sampled
+ * AOVs and the reject counter are left as they are; rmr_set_query_grid caps its grid too. RMR_E_INVALID,
+ * naming the field, for a descriptor rmr_check_volume rejects; RMR_E_STATE without a scene. */
+int rmr_sample_volume(rmr_ctx* ctx, const rmr_volume_desc* desc, float* dist, float* id);
+/* The same into device memory of the context's device, queued on the context's stream without
+ * synchronising (as rmr_eval_map_device). */
+int rmr_sample_volume_device(rmr_ctx* ctx, const rmr_volume_desc* desc, float* d_dist, float* d_id);
+
+/* Surface nets over the sampled volume. With dist the lattice's distances and iso the level:
+ *   A point is inside iff dist < iso (a NaN is outside, dist == iso is outside).
+ *   A cell is the cube of 8 neighbouring points, at cell coordinates 0 .. n[a] - 2; it is active iff its
+ *   corners are not all inside and not all outside. Each active cell has exactly one vertex; vertices are
+ *   numbered in the order of the cells' linear index cx + (n[0] - 1) * (cy + (n[1] - 1) * cz).
+ *   On a cell edge whose ends differ in inside-ness the crossing is t = (iso - d0) / (d1 - d0), from the
+ *   lower end (d0) to the upper end (d1); a t that is not finite or outside [0, 1] is 0.5.
+ *   The cell's 12 edges in order: axis a = x, y, z; with u = a + 1, v = a + 2 (cyclic) the edge at offsets
+ *   (ou, ov) = (0, 0), (1, 0), (0, 1), (1, 1) on u and v. A crossing contributes t on axis a, ou on u and
+ *   ov on v. s = the float32 sum of the contributions in that order, per axis; count = their number.
+ *   vertex_a = (origin[a] + (float)c_a * spacing) + spacing * (s_a / (float)count).
+ *   A lattice edge runs from point p along axis ax; with (ax, u, v) a cyclic permutation of (x, y, z) it is
+ *   interior iff 1 <= p[u] <= n[u] - 2 and 1 <= p[v] <= n[v] - 2. An interior edge whose ends differ emits
+ *   one quad (a boundary edge none: a surface that leaves the lattice is cut open there) of the vertices
+ *   of the cells at (c[u], c[v]) = (p[u]-1, p[v]-1), (p[u], p[v]-1), (p[u], p[v]), (p[u]-1, p[v]), c[ax] =
+ *   p[ax], in that order when the lower end is inside and in the reverse order otherwise: by the right-hand
+ *   rule the quad's normal points from inside to outside. Quads are ordered by the linear index of the
+ *   edge's lower point, then by axis x, y, z.
+ *   RMR_MESH_NORMALS: normals[v] = getNormal(vertex v) as rmr_cast_rays states it (six probes, normalize);
+ *   RMR_MESH_IDS: ids[v] = map(vertex v).y; both at the float32 vertex position, bit for bit what
+ *   rmr_cast_rays / rmr_eval_map give there. */
+#define RMR_MESH_NORMALS 1
+#define RMR_MESH_IDS 2
+typedef struct rmr_mesh_params {
+    float iso;
+    int32_t flags;   /* RMR_MESH_* */
+} rmr_mesh_params;
+typedef struct rmr_mesh_info {
+    uint64_t n_vertices, n_quads;
+} rmr_mesh_info;
+/* Samples the lattice (as rmr_sample_volume_device, into memory of the library's) and extracts the mesh:
+ * classify and count, an exclusive scan of the block totals (which alone decides every element's place: two
+ * calls give the same bytes), then vertices, quads and attributes. Everything is queued on the context's
+ * stream; the call synchronises once, after the scan, for the counts, sizes the mesh's buffers exactly and
+ * queues the rest. The buffers belong to the library; the working memory (9 bytes per point and the
+ * distances) is kept for the next extraction. State rules as rmr_sample_volume. RMR_E_INVALID for a bad
+ * descriptor (naming the field), a non-finite iso, unknown flags and for 2^32 or more vertices or quads;
+ * RMR_E_STATE without a scene; RMR_E_NOMEM when an allocation fails. After any error there is no mesh. */
+int rmr_extract_mesh(rmr_ctx* ctx, const rmr_volume_desc* desc, const rmr_mesh_params* params, rmr_mesh_info* info);
+/* The last extraction's mesh to host memory: vertices [n_vertices][3] floats, normals [n_vertices][3]
+ * floats or NULL, ids [n_vertices] floats or NULL, quads [n_quads][4] uint32. Synchronises. RMR_E_STATE
+ * before a valid extraction and for an attribute that was not extracted. */
+int rmr_read_mesh(rmr_ctx* ctx, float* vertices, float* normals, float* ids, uint32_t* quads);
+/* The mesh's device buffers (NULL: no mesh, not extracted, or empty); written by work queued on the
+ * context's stream. No synchronisation. */
+#define RMR_MESH_BUF_VERTICES 0
+#define RMR_MESH_BUF_NORMALS 1
+#define RMR_MESH_BUF_IDS 2
+#define RMR_MESH_BUF_QUADS 3
+void* rmr_mesh_device_ptr(rmr_ctx* ctx, int which);
+/* Releases the mesh and the extraction's working memory (synchronises). The mesh lives until the next
+ * rmr_extract_mesh, rmr_mesh_free, rmr_reload or rmr_destroy; a render, a view change or a parameter change
+ * does not drop it. */
+int rmr_mesh_free(rmr_ctx* ctx);
+/* The same rule on a host volume, no context and no GPU, in count-then-fill form: *info always receives
+ * the counts; with vertices and quads NULL nothing else happens; otherwise both are filled, or, where
+ * vertex_cap (vertices) or quad_cap (quads) is too small, nothing is written and the result is
+ * RMR_E_INVALID. RMR_E_INVALID also for a bad descriptor or a non-finite iso. */
+int rmr_surface_nets(const float* dist, const rmr_volume_desc* desc, float iso, float* vertices, size_t vertex_cap,
+                     uint32_t* quads, size_t quad_cap, rmr_mesh_info* info);
+/* Wavefront OBJ: "v x y z" (9 significant digits: the float32 values read back exactly), with normals
+ * "vn x y z" and faces "f a//a b//b c//c d//d", without them "f a b c d"; indices from 1. RMR_E_IO when
+ * the file cannot be written, RMR_E_INVALID for an index >= n_vertices. */
+int rmr_encode_obj(const char* path, const float* vertices, const float* normals, size_t n_vertices,
+                   const uint32_t* quads, size_t n_quads);
+/* PLY, binary little-endian: vertex properties float x y z, with normals float nx ny nz, with ids float
+ * material; faces "list uchar uint vertex_indices" of 4. */
+int rmr_encode_ply(const char* path, const float* vertices, const float* normals, const float* ids, size_t n_vertices,
+                   const uint32_t* quads, size_t n_quads);
+
 /* ---- display ---------------------------------------------------------------------------- */
 /* Graphics::Display(centre, zoom, min, max) (Graphics.cpp:356-390 with createFQ 227-258 and
  * FullQuad.vs / FullQuad.fs), headless: draws the accumulator into a screen_w x screen_h RGBA8 image

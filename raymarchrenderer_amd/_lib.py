@@ -46,6 +46,8 @@ EXPORTS = [
     "rmr_bloom_pixels",
     "rmr_render_aov", "rmr_aov_reset", "rmr_read_aov", "rmr_read_aov_resolved", "rmr_aov_device_ptr",
     "rmr_aov_resolved_device_ptr", "rmr_set_aov_launch_samples", "rmr_aov_init", "rmr_aov_fold", "rmr_aov_resolve",
+    "rmr_check_volume", "rmr_sample_volume", "rmr_sample_volume_device", "rmr_extract_mesh", "rmr_read_mesh",
+    "rmr_mesh_device_ptr", "rmr_mesh_free", "rmr_surface_nets", "rmr_encode_obj", "rmr_encode_ply",
 ]
 
 
@@ -223,6 +225,17 @@ def lib(diag=None):
         "rmr_aov_init": (C.c_int, [fp, C.c_size_t]),
         "rmr_aov_fold": (C.c_int, [fp, C.c_void_p, C.c_size_t, C.c_uint32]),
         "rmr_aov_resolve": (C.c_int, [fp, C.c_size_t, C.c_float, fp]),
+        "rmr_check_volume": (C.c_int, [C.POINTER(abi.VolumeDesc), C.POINTER(C.c_char_p)]),
+        "rmr_sample_volume": (C.c_int, [vp, C.POINTER(abi.VolumeDesc), fp, fp]),
+        "rmr_sample_volume_device": (C.c_int, [vp, C.POINTER(abi.VolumeDesc), C.c_void_p, C.c_void_p]),
+        "rmr_extract_mesh": (C.c_int, [vp, C.POINTER(abi.VolumeDesc), C.POINTER(abi.MeshParams), C.POINTER(abi.MeshInfo)]),
+        "rmr_read_mesh": (C.c_int, [vp, fp, fp, fp, C.POINTER(C.c_uint32)]),
+        "rmr_mesh_device_ptr": (vp, [vp, C.c_int]),
+        "rmr_mesh_free": (C.c_int, [vp]),
+        "rmr_surface_nets": (C.c_int, [fp, C.POINTER(abi.VolumeDesc), C.c_float, fp, C.c_size_t, C.POINTER(C.c_uint32),
+                                       C.c_size_t, C.POINTER(abi.MeshInfo)]),
+        "rmr_encode_obj": (C.c_int, [C.c_char_p, fp, fp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]),
+        "rmr_encode_ply": (C.c_int, [C.c_char_p, fp, fp, fp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]),
         "rmr_diag_bloom_tail": (C.c_int, [vp, C.c_int]),
         "rmr_diag_bloom_time": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp]),
         "rmr_diag_tonemap_fold": (C.c_int, [vp, C.c_int]),

@@ -294,6 +294,35 @@ AOV_R_IDS01 = 3
 AOV_R_IDS23 = 4
 AOV_RESOLVED = {"depth": AOV_R_DEPTH, "normal": AOV_R_NORMAL, "position": AOV_R_POSITION, "ids01": AOV_R_IDS01,
                 "ids23": AOV_R_IDS23}
+
+
+# SDF volume sampling and surface-nets extraction (rmr.h rmr_sample_volume / rmr_extract_mesh)
+class VolumeDesc(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float), ("n", C.c_int32 * 3)]
+
+
+class MeshParams(C.Structure):
+    _fields_ = [("iso", C.c_float), ("flags", C.c_int32)]
+
+
+class MeshInfo(C.Structure):
+    _fields_ = [("n_vertices", C.c_uint64), ("n_quads", C.c_uint64)]
+
+
+def volume_desc(origin, spacing, shape):
+    """rmr_volume_desc of a lattice: origin (x, y, z), spacing, shape (nx, ny, nz) points."""
+    o, n = [float(v) for v in origin], [int(v) for v in shape]
+    if len(o) != 3 or len(n) != 3:
+        raise ValueError("a lattice has an origin of 3 coordinates and a shape of 3 point counts")
+    return VolumeDesc((C.c_float * 3)(*o), float(spacing), (C.c_int32 * 3)(*n))
+
+
+MESH_NORMALS = 1
+MESH_IDS = 2
+MESH_BUF_VERTICES = 0
+MESH_BUF_NORMALS = 1
+MESH_BUF_IDS = 2
+MESH_BUF_QUADS = 3
 # variance planes of the variance-guided denoiser (rmr.h)
 VARIANCE_SEED = 0
 VARIANCE_FILTERED = 1

@@ -61,6 +61,17 @@ hipError_t launch_unpack_rgba(const float4* samp, const float4* rec, float* out,
 hipError_t launch_aov(const KParams& P, const CamParams& C, int np, float4* state, bool restart, hipStream_t s);
 hipError_t launch_aov_init(float4* state, size_t n_px, hipStream_t s);
 hipError_t launch_aov_resolve(const float4* state, size_t n_px, float max_dist, float4* out, hipStream_t s);
+uint32_t mesh_blocks(const rmr_volume_desc& d);
+uint32_t mesh_scan_groups(uint32_t blocks);
+hipError_t launch_sample_volume(const KParams& P, int np, const rmr_volume_desc& d, float* dist, float* id, int grid_cap,
+                                hipStream_t s);
+hipError_t launch_mesh_count(const rmr_volume_desc& d, const float* dist, float iso, uint8_t* flags, uint2* totals,
+                             uint2* group_totals, unsigned long long* bases, unsigned long long* counts, hipStream_t s);
+hipError_t launch_mesh_emit(const rmr_volume_desc& d, const float* dist, float iso, const uint8_t* flags, const uint2* totals,
+                            const unsigned long long* bases, uint32_t* cell_vertex, float* vertices, uint32_t* quads,
+                            hipStream_t s);
+hipError_t launch_mesh_attr(const KParams& P, int np, const float* vertices, uint32_t n_vertices, float* normals, float* ids,
+                            hipStream_t s);
 }  // namespace rmr
 
 using rmr::CompiledScene;
@@ -142,6 +153,21 @@ struct rmr_ctx {
     bool aov_res_valid = false;           // d_aov_res is (or is queued to be) the resolve of the current state
     uint64_t aov_samples = 0;             // a bound on every pixel's n: samples since the last whole-image restart
     int aov_launch_samples = kAovLaunchSamples;
+    // the extracted mesh (rmr_extract_mesh, rmr_volume.hip): its buffers, sized exactly, and
+    // the extraction's working memory (distances, flag bytes, cell numbers: grows only; block totals, group
+    // totals, bases and the two counts in one allocation); freed at rmr_mesh_free, rmr_reload and rmr_destroy
+    float* d_mesh_v = nullptr;
+    float* d_mesh_n = nullptr;
+    float* d_mesh_id = nullptr;
+    uint32_t* d_mesh_q = nullptr;
+    bool mesh_valid = false;
+    int mesh_flags = 0;
+    uint64_t mesh_nv = 0, mesh_nq = 0;
+    void* d_mesh_dist = nullptr;
+    void* d_mesh_flag = nullptr;
+    void* d_mesh_cell = nullptr;
+    void* d_mesh_scan = nullptr;
+    size_t mesh_dist_cap = 0, mesh_flag_cap = 0, mesh_cell_cap = 0, mesh_scan_cap = 0;   // bytes
     // which of the output stages' images below are valid: the one place that says so (stage_state.hpp)
     rmr::StageState st;
     // first-hit guides and the preview denoiser (rmr_render_guides / rmr_denoise): three guide planes and
@@ -441,6 +467,20 @@ void free_aov(rmr_ctx* c) {
     free_all({&c->d_aov, &c->d_aov_res});
     c->aov_rendered = c->aov_res_valid = false;
     c->aov_samples = 0;
+}
+
+// Release the mesh's buffers (the caller has synced the context's stream); there is no mesh afterwards.
+void drop_mesh(rmr_ctx* c) {
+    free_all({&c->d_mesh_v, &c->d_mesh_n, &c->d_mesh_id, &c->d_mesh_q});
+    c->mesh_valid = false;
+    c->mesh_flags = 0;
+    c->mesh_nv = c->mesh_nq = 0;
+}
+// The same and the extraction's working memory.
+void free_mesh(rmr_ctx* c) {
+    drop_mesh(c);
+    free_all({&c->d_mesh_dist, &c->d_mesh_flag, &c->d_mesh_cell, &c->d_mesh_scan});
+    c->mesh_dist_cap = c->mesh_flag_cap = c->mesh_cell_cap = c->mesh_scan_cap = 0;
 }
 
 // Release the half image and the tile-error map (the caller has synced the context's stream).
@@ -1359,6 +1399,7 @@ void rmr_destroy(rmr_ctx* c) {
     free_tonemap(c);
     free_bloom(c);
     free_aov(c);
+    free_mesh(c);
     free_estimate(c);
     if (c->d_accum && !c->accum_external) (void)hipFree(c->d_accum);
     for (auto& k : c->jit_loaded)
@@ -1496,6 +1537,7 @@ int rmr_reload(rmr_ctx* c) {
     free_tonemap(c);
     free_bloom(c);
     free_aov(c);
+    free_mesh(c);
     c->W = c->pend_W;
     c->H = c->pend_H;
     if (resize) {
@@ -2368,6 +2410,140 @@ void* rmr_aov_resolved_device_ptr(rmr_ctx* c, int which) {
 int rmr_set_aov_launch_samples(rmr_ctx* c, int n) {
     if (!c || n < 1) return RMR_E_INVALID;
     c->aov_launch_samples = n;
+    return RMR_OK;
+}
+
+// ---- SDF volume sampling and surface-nets extraction (rmr_volume.hip, rmr_mesh_rule.h) ----
+namespace {
+int volume_begin(rmr_ctx* c, const char* who, const rmr_volume_desc* desc, KParams& P) {
+    const char* bad = nullptr;
+    if (rmr_check_volume(desc, &bad) != RMR_OK)
+        return fail(c, RMR_E_INVALID, std::string(who) + ": bad volume descriptor field '" + bad + "'");
+    return query_begin(c, P);
+}
+size_t volume_points(const rmr_volume_desc* d) { return (size_t)d->n[0] * (size_t)d->n[1] * (size_t)d->n[2]; }
+}  // namespace
+
+int rmr_sample_volume_device(rmr_ctx* c, const rmr_volume_desc* desc, float* d_dist, float* d_id) {
+    if (!c || !desc || !d_dist) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    KParams P;
+    int r;
+    if ((r = volume_begin(c, "rmr_sample_volume_device", desc, P))) return r;
+    HIPCHK(c, rmr::launch_sample_volume(P, c->accel.map_np, *desc, d_dist, d_id, c->query_grid, c->stream));
+    return RMR_OK;
+}
+
+int rmr_sample_volume(rmr_ctx* c, const rmr_volume_desc* desc, float* dist, float* id) {
+    if (!c || !desc || !dist) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    KParams P;
+    int r;
+    if ((r = volume_begin(c, "rmr_sample_volume", desc, P))) return r;
+    const size_t n = volume_points(desc);
+    if ((r = ensure_qbuf(c, &c->d_qout, &c->qout_cap, n * (id ? 2 : 1) * sizeof(float)))) return r;
+    float* d_dist = (float*)c->d_qout;
+    float* d_id = id ? d_dist + n : nullptr;
+    HIPCHK(c, rmr::launch_sample_volume(P, c->accel.map_np, *desc, d_dist, d_id, c->query_grid, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dist, d_dist, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (id) HIPCHK(c, hipMemcpyAsync(id, d_id, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+int rmr_extract_mesh(rmr_ctx* c, const rmr_volume_desc* desc, const rmr_mesh_params* mp, rmr_mesh_info* info) {
+    if (!c || !desc || !mp || !info) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    info->n_vertices = info->n_quads = 0;
+    c->mesh_valid = false;   // (whatever happens from here on, the last mesh is gone; its buffers go below or with the next free)
+    if (!(mp->iso - mp->iso == 0.0f)) return fail(c, RMR_E_INVALID, "rmr_extract_mesh: iso must be finite");
+    if (mp->flags & ~(RMR_MESH_NORMALS | RMR_MESH_IDS)) return fail(c, RMR_E_INVALID, "rmr_extract_mesh: unknown flags");
+    KParams P;
+    int r;
+    if ((r = volume_begin(c, "rmr_extract_mesh", desc, P))) return r;
+    if (c->d_mesh_v || c->d_mesh_q) HIPCHK(c, hipStreamSynchronize(c->stream));   // (the last mesh's queued work)
+    drop_mesh(c);
+    // the working memory: distances, a flag byte and a cell number per point; block totals, group totals,
+    // the groups' bases and the two counts
+    const size_t n = volume_points(desc);
+    const uint32_t blocks = rmr::mesh_blocks(*desc), groups = rmr::mesh_scan_groups(blocks);
+    const size_t scan_bytes = ((size_t)blocks + groups) * sizeof(uint2) + ((size_t)groups * 2 + 2) * sizeof(unsigned long long);
+    if ((r = ensure_qbuf(c, &c->d_mesh_dist, &c->mesh_dist_cap, n * sizeof(float)))) return r;
+    if ((r = ensure_qbuf(c, &c->d_mesh_flag, &c->mesh_flag_cap, n))) return r;
+    if ((r = ensure_qbuf(c, &c->d_mesh_cell, &c->mesh_cell_cap, n * sizeof(uint32_t)))) return r;
+    if ((r = ensure_qbuf(c, &c->d_mesh_scan, &c->mesh_scan_cap, scan_bytes))) return r;
+    float* dist = (float*)c->d_mesh_dist;
+    uint8_t* flags = (uint8_t*)c->d_mesh_flag;
+    uint2* totals = (uint2*)c->d_mesh_scan;
+    uint2* group_totals = totals + blocks;
+    unsigned long long* bases = (unsigned long long*)(group_totals + groups);
+    unsigned long long* d_counts = bases + 2 * (size_t)groups;
+    HIPCHK(c, rmr::launch_sample_volume(P, c->accel.map_np, *desc, dist, nullptr, c->query_grid, c->stream));
+    HIPCHK(c, rmr::launch_mesh_count(*desc, dist, mp->iso, flags, totals, group_totals, bases, d_counts, c->stream));
+    unsigned long long counts[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // the call's one synchronisation: the counts size the buffers
+    const unsigned long long nv = counts[0], nq = counts[1];
+    if (nv >= (1ull << 32) || nq >= (1ull << 32)) return fail(c, RMR_E_INVALID, "rmr_extract_mesh: 2^32 or more vertices or quads");
+    auto get = [&](auto** p, size_t bytes) {
+        if (bytes == 0 || hipMalloc((void**)p, bytes) == hipSuccess) return true;
+        (void)hipGetLastError();
+        *p = nullptr;
+        return false;
+    };
+    if (!get(&c->d_mesh_v, nv * 3 * sizeof(float)) || !get(&c->d_mesh_q, nq * 4 * sizeof(uint32_t)) ||
+        !get(&c->d_mesh_n, (mp->flags & RMR_MESH_NORMALS) ? nv * 3 * sizeof(float) : 0) ||
+        !get(&c->d_mesh_id, (mp->flags & RMR_MESH_IDS) ? nv * sizeof(float) : 0)) {
+        drop_mesh(c);
+        return fail(c, RMR_E_NOMEM, "rmr_extract_mesh: cannot allocate the mesh (" + std::to_string(nv) + " vertices, " +
+                                        std::to_string(nq) + " quads)");
+    }
+    if (nv) {
+        HIPCHK(c, rmr::launch_mesh_emit(*desc, dist, mp->iso, flags, totals, bases, (uint32_t*)c->d_mesh_cell, c->d_mesh_v,
+                                        c->d_mesh_q, c->stream));
+        HIPCHK(c, rmr::launch_mesh_attr(P, c->accel.map_np, c->d_mesh_v, (uint32_t)nv, c->d_mesh_n, c->d_mesh_id, c->stream));
+    }
+    c->mesh_valid = true;
+    c->mesh_flags = mp->flags;
+    c->mesh_nv = info->n_vertices = nv;
+    c->mesh_nq = info->n_quads = nq;
+    return RMR_OK;
+}
+
+int rmr_read_mesh(rmr_ctx* c, float* vertices, float* normals, float* ids, uint32_t* quads) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!c->mesh_valid) return fail(c, RMR_E_STATE, "no mesh (call rmr_extract_mesh)");
+    if ((normals && !(c->mesh_flags & RMR_MESH_NORMALS)) || (ids && !(c->mesh_flags & RMR_MESH_IDS)))
+        return fail(c, RMR_E_STATE, "rmr_read_mesh: the attribute was not extracted (rmr_mesh_params.flags)");
+    if ((c->mesh_nv && !vertices) || (c->mesh_nq && !quads)) return fail(c, RMR_E_INVALID, "rmr_read_mesh: null buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nv = (size_t)c->mesh_nv, nq = (size_t)c->mesh_nq;
+    if (nv) HIPCHK(c, hipMemcpyAsync(vertices, c->d_mesh_v, nv * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (nv && normals) HIPCHK(c, hipMemcpyAsync(normals, c->d_mesh_n, nv * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (nv && ids) HIPCHK(c, hipMemcpyAsync(ids, c->d_mesh_id, nv * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (nq) HIPCHK(c, hipMemcpyAsync(quads, c->d_mesh_q, nq * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+void* rmr_mesh_device_ptr(rmr_ctx* c, int which) {
+    if (!c || !c->mesh_valid) return nullptr;
+    switch (which) {
+    case RMR_MESH_BUF_VERTICES: return c->d_mesh_v;
+    case RMR_MESH_BUF_NORMALS: return c->d_mesh_n;
+    case RMR_MESH_BUF_IDS: return c->d_mesh_id;
+    case RMR_MESH_BUF_QUADS: return c->d_mesh_q;
+    default: return nullptr;
+    }
+}
+
+int rmr_mesh_free(rmr_ctx* c) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_mesh(c);
     return RMR_OK;
 }
 

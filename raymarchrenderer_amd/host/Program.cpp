@@ -65,6 +65,12 @@ struct Options {
     double variance_guided = -1.0;  // --variance-guided [SIGMA_L]: the guided filter's sigma_l, < 0 = the plain filter
     std::string aov;                // --aov PREFIX: guide planes as PREFIX_*.pfm
     std::string sampled_aov;        // --sampled-aov PREFIX: the sampled AOVs as PREFIX_*.pfm
+    std::string mesh;               // --mesh FILE.obj|FILE.ply: the scene's surface-nets mesh
+    bool mesh_ply = false;
+    bool have_mesh_bounds = false, have_mesh_opts = false;
+    double mesh_bounds[6] = {0, 0, 0, 0, 0, 0};   // --mesh-bounds x0,y0,z0,x1,y1,z1
+    int mesh_grid = 128;            // --mesh-grid N: cells along the longest side
+    float mesh_iso = 0.0f;          // --mesh-iso V
     double adaptive = -1.0;         // --adaptive T: the tile-error threshold, < 0 = uniform sampling
     int min_samples = 16, pass_samples = 16;   // --min-samples / --pass-samples (rmr_adaptive_params)
     bool have_camera = false;
@@ -383,6 +389,52 @@ bool write_sampled_aovs(const Options& o) {
     return true;
 }
 
+// The lattice of --mesh-bounds and --mesh-grid: the spacing is the longest side over N, the longest side has
+// N cells and the other sides are rounded up to whole cells; the origin is the bounds' lower corner.
+rmr_volume_desc mesh_lattice(const Options& o) {
+    rmr_volume_desc d;
+    double longest = 0.0;
+    int which = 0;
+    for (int a = 0; a < 3; a++) {
+        const double side = o.mesh_bounds[3 + a] - o.mesh_bounds[a];
+        if (side > longest) { longest = side; which = a; }
+        d.origin[a] = (float)o.mesh_bounds[a];
+    }
+    d.spacing = (float)(longest / (double)o.mesh_grid);
+    for (int a = 0; a < 3; a++) {
+        const double cells = std::ceil((o.mesh_bounds[3 + a] - o.mesh_bounds[a]) / (double)d.spacing);
+        d.n[a] = a == which ? o.mesh_grid + 1 : (int)std::fmin(std::fmax(cells, 1.0), 1e6) + 1;
+    }
+    return d;
+}
+
+// --mesh FILE: rmr_extract_mesh over that lattice with normals and material ids, written as OBJ (v, vn, f) or
+// binary PLY (x y z nx ny nz material)
+bool write_mesh(const Options& o) {
+    rmr_ctx* c = Graphics::context();
+    auto fail = [&](const std::string& what) {
+        std::cerr << "--mesh: " << what << ": " << rmr_last_error(c) << std::endl;
+        return false;
+    };
+    const rmr_volume_desc d = mesh_lattice(o);
+    const rmr_mesh_params mp = {o.mesh_iso, RMR_MESH_NORMALS | RMR_MESH_IDS};
+    rmr_mesh_info info = {0, 0};
+    if (rmr_extract_mesh(c, &d, &mp, &info) != RMR_OK) return fail("rmr_extract_mesh");
+    std::vector<float> v(3 * (size_t)info.n_vertices), n(3 * (size_t)info.n_vertices), ids((size_t)info.n_vertices);
+    std::vector<uint32_t> q(4 * (size_t)info.n_quads);
+    if (rmr_read_mesh(c, v.data(), n.data(), ids.data(), q.data()) != RMR_OK) return fail("rmr_read_mesh");
+    const int rc = o.mesh_ply ? rmr_encode_ply(o.mesh.c_str(), v.data(), n.data(), ids.data(), (size_t)info.n_vertices, q.data(), (size_t)info.n_quads)
+                              : rmr_encode_obj(o.mesh.c_str(), v.data(), n.data(), (size_t)info.n_vertices, q.data(), (size_t)info.n_quads);
+    if (rc != RMR_OK) {
+        std::cerr << "--mesh: cannot write " << o.mesh << std::endl;
+        return false;
+    }
+    if (!o.quiet)
+        std::cout << "Saved mesh as: " << o.mesh << " (" << info.n_vertices << " vertices, " << info.n_quads << " quads, lattice "
+                  << d.n[0] << "x" << d.n[1] << "x" << d.n[2] << ", spacing " << d.spacing << ")" << std::endl;
+    return true;
+}
+
 void report(const Options& o, const RenderResult& r) {
     std::cout << "Render Time: " << r.seconds << std::endl;  // Program.cpp:297
     if (!o.quiet && r.seconds > 0)
@@ -497,6 +549,14 @@ void usage() {
         "                      --camera model): PREFIX_alpha.pfm (R = alpha, G = samples, B = hits),\n"
         "                      PREFIX_depth.pfm (R = mean t, G = min t), PREFIX_normal.pfm, PREFIX_position.pfm,\n"
         "                      PREFIX_ids.pfm (R, G = id0, coverage0; B = id1); not with --gpus / --devices\n"
+        "  --mesh FILE.obj|FILE.ply  after the render: the scene's surface as a quad mesh (surface nets over a\n"
+        "                      lattice of distance samples, rmr.h rmr_extract_mesh) with normals and, in PLY,\n"
+        "                      material ids; needs --mesh-bounds; not with --gpus / --devices or --interactive\n"
+        "  --mesh-bounds x0,y0,z0,x1,y1,z1   the box that is meshed (required: a scene has no finite box of its\n"
+        "                      own); a surface that leaves it is cut open there\n"
+        "  --mesh-grid N       cells along the box's longest side (1..4095, default 128); the spacing is that\n"
+        "                      side over N, the other sides are rounded up to whole cells\n"
+        "  --mesh-iso V        the level that is meshed (default 0; V > 0 grows the shape)\n"
         "  --adaptive T        adaptive sampling: render until every block's tile error is <= T, at most\n"
         "                      --samples per pixel, over the whole image; prints passes, mean spp, open tiles\n"
         "                      and max error; with --aov also PREFIX_spp.pfm (R = samples) and PREFIX_error.pfm\n"
@@ -648,6 +708,34 @@ bool parse(int argc, char** argv, Options& o) {
             o.sampled_aov = next("--sampled-aov");
             if (o.sampled_aov.empty()) return false;
         }
+        else if (a == "--mesh") {
+            o.mesh = next("--mesh");
+            const size_t dot = o.mesh.rfind('.');
+            const std::string ext = dot == std::string::npos ? "" : o.mesh.substr(dot);
+            if (ext != ".obj" && ext != ".ply") return false;
+            o.mesh_ply = ext == ".ply";
+        } else if (a == "--mesh-bounds") {
+            char tail = 0;
+            double* b = o.mesh_bounds;
+            if (std::sscanf(next("--mesh-bounds"), "%lf,%lf,%lf,%lf,%lf,%lf%c", b, b + 1, b + 2, b + 3, b + 4, b + 5, &tail) != 6)
+                return false;
+            for (int k = 0; k < 3; k++)
+                if (!std::isfinite((float)b[k]) || !std::isfinite((float)b[3 + k]) || !(b[3 + k] > b[k])) return false;
+            o.have_mesh_bounds = true;
+        } else if (a == "--mesh-grid") {
+            char* end = nullptr;
+            const char* v = next("--mesh-grid");
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 1 || n > 4095) return false;
+            o.mesh_grid = (int)n;
+            o.have_mesh_opts = true;
+        } else if (a == "--mesh-iso") {
+            char* end = nullptr;
+            const char* v = next("--mesh-iso");
+            o.mesh_iso = std::strtof(v, &end);
+            if (end == v || *end != '\0' || !std::isfinite(o.mesh_iso)) return false;
+            o.have_mesh_opts = true;
+        }
         else if (a == "--adaptive") {
             char* end = nullptr;
             const char* v = next("--adaptive");
@@ -703,6 +791,18 @@ bool parse(int argc, char** argv, Options& o) {
         std::fprintf(stderr, "--bloom: THRESHOLD and INTENSITY are finite and >= 0\n");
         return false;
     }
+    if (o.mesh.empty() ? (o.have_mesh_bounds || o.have_mesh_opts) : !o.have_mesh_bounds) {
+        std::fprintf(stderr, "--mesh FILE.obj|FILE.ply needs --mesh-bounds x0,y0,z0,x1,y1,z1 (and they need --mesh)\n");
+        return false;
+    }
+    if (!o.mesh.empty()) {
+        const rmr_volume_desc d = mesh_lattice(o);
+        const char* bad = nullptr;
+        if (rmr_check_volume(&d, &bad) != RMR_OK) {
+            std::fprintf(stderr, "--mesh-bounds / --mesh-grid: the lattice's %s is out of range\n", bad);
+            return false;
+        }
+    }
     if (o.adaptive >= 0 && (o.min_samples < 2 || o.pass_samples < 1 || o.samples < o.min_samples)) {
         std::fprintf(stderr, "--adaptive: --min-samples >= 2, --pass-samples >= 1 and --samples >= --min-samples\n");
         return false;
@@ -756,6 +856,10 @@ int main(int argc, char** argv) {
     }
     if (!o.sampled_aov.empty() && (!o.devices.empty() || o.interactive)) {
         std::fprintf(stderr, "--sampled-aov: not with --gpus / --devices or --interactive\n");
+        return 2;
+    }
+    if (!o.mesh.empty() && (!o.devices.empty() || o.interactive)) {
+        std::fprintf(stderr, "--mesh: not with --gpus / --devices or --interactive\n");
         return 2;
     }
     Screen::setScreenSize(Vector2(1280, 720));  // Program.cpp:89
@@ -820,6 +924,7 @@ int main(int argc, char** argv) {
     int rc = Graphics::lastStatus() == RMR_OK ? 0 : 1;
     if (rc == 0 && !o.aov.empty() && !write_aovs(o)) rc = 1;
     if (rc == 0 && !o.sampled_aov.empty() && !write_sampled_aovs(o)) rc = 1;
+    if (rc == 0 && !o.mesh.empty() && !write_mesh(o)) rc = 1;
     Graphics::Shutdown();
     return rc;
 }

@@ -77,6 +77,7 @@ class Renderer:
         if rc != abi.RMR_OK:
             raise RMRError(rc, "rmr_create failed (no HIP device %d?)" % device)
         self._device = int(device)
+        self._mesh_info = None   # (n_vertices, n_quads, normals, ids) of the last extract_mesh
         self.set_image_size(width, height)
         self.reload()
         self.variant = None
@@ -441,6 +442,80 @@ class Renderer:
                 raise RMRError(-5, (self._L.rmr_last_error(self._ctx) or b"").decode(errors="replace"))
             out[name] = torch.as_tensor(_DeviceArray(ptr, (h, w, 4), self), device="cuda:%d" % self._device)
         return out
+
+    # -- SDF volume sampling and surface-nets mesh extraction (rmr.h) --
+    def sample_volume(self, origin, spacing, shape, ids=False):
+        """rmr_sample_volume: map() at the lattice's points origin + i * spacing, shape = (nx, ny, nz) points,
+        as a float32 array indexed [iz, iy, ix]; with ids=True the pair (distances, ids)."""
+        d = _volume_desc(origin, spacing, shape)
+        nx, ny, nz = d.n[0], d.n[1], d.n[2]
+        dist = np.zeros((nz, ny, nx), np.float32)
+        idv = np.zeros((nz, ny, nx), np.float32) if ids else None
+        self._chk(self._L.rmr_sample_volume(self._ctx, C.byref(d), _fp(dist), _fp(idv) if ids else None))
+        return (dist, idv) if ids else dist
+
+    def sample_volume_device(self, origin, spacing, shape, ids=False):
+        """rmr_sample_volume_device: the same as torch float32 tensors [iz, iy, ix] on the context's device,
+        written by the kernel (no copy); queued on the context's stream, no sync."""
+        import torch
+        d = _volume_desc(origin, spacing, shape)
+        nx, ny, nz = d.n[0], d.n[1], d.n[2]
+        dev = "cuda:%d" % self._device
+        dist = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev)
+        idv = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev) if ids else None
+        self._chk(self._L.rmr_sample_volume_device(self._ctx, C.byref(d), dist.data_ptr(),
+                                                   idv.data_ptr() if ids else None))
+        return (dist, idv) if ids else dist
+
+    def extract_mesh(self, origin, spacing, shape, iso=0.0, normals=True, ids=True):
+        """rmr_extract_mesh + rmr_read_mesh: the surface-nets mesh of the level iso over the lattice, a dict of
+        'vertices' (V, 3) float32, 'quads' (Q, 4) uint32, 'normals' (V, 3) float32 or None and 'ids' (V,)
+        float32 or None. quads_to_triangles() splits the quads."""
+        d = _volume_desc(origin, spacing, shape)
+        mp = abi.MeshParams(float(iso), (abi.MESH_NORMALS if normals else 0) | (abi.MESH_IDS if ids else 0))
+        info = abi.MeshInfo()
+        self._mesh_info = None
+        self._chk(self._L.rmr_extract_mesh(self._ctx, C.byref(d), C.byref(mp), C.byref(info)))
+        self._mesh_info = (int(info.n_vertices), int(info.n_quads), bool(normals), bool(ids))
+        return self.read_mesh(normals=normals, ids=ids)
+
+    def read_mesh(self, normals=True, ids=True):
+        """rmr_read_mesh: the last extraction's mesh (see extract_mesh)."""
+        nv, nq = (self._mesh_info or (0, 0))[:2]
+        v = np.zeros((nv, 3), np.float32)
+        q = np.zeros((nq, 4), np.uint32)
+        n = np.zeros((nv, 3), np.float32) if normals else None
+        i = np.zeros((nv,), np.float32) if ids else None
+        self._chk(self._L.rmr_read_mesh(self._ctx, _fp(v), _fp(n) if normals else None, _fp(i) if ids else None,
+                                        q.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return {"vertices": v, "quads": q, "normals": n, "ids": i}
+
+    def mesh_device(self):
+        """rmr_mesh_device_ptr: the mesh as torch tensors on the context's device, views of the library's memory
+        (no copy, no sync; written by work queued on the context's stream): 'vertices' (V, 3) float32, 'quads'
+        (Q, 4) int32 (the uint32 indices' bits), 'normals' and 'ids' or None. Valid until the next extraction,
+        mesh_free or reload."""
+        import torch
+        if not self._mesh_info or (self._mesh_info[0] and not self._L.rmr_mesh_device_ptr(self._ctx, abi.MESH_BUF_VERTICES)):
+            raise RMRError(-5, "no mesh (call extract_mesh)")
+        nv, nq, has_n, has_i = self._mesh_info
+        dev = "cuda:%d" % self._device
+
+        def view(which, shape, typestr):
+            ptr = self._L.rmr_mesh_device_ptr(self._ctx, which)
+            if not ptr or not shape[0]:
+                return torch.empty(shape, dtype=torch.float32 if typestr == "<f4" else torch.int32, device=dev)
+            a = _DeviceArray(ptr, shape, self)
+            a.__cuda_array_interface__["typestr"] = typestr
+            return torch.as_tensor(a, device=dev)
+        return {"vertices": view(abi.MESH_BUF_VERTICES, (nv, 3), "<f4"), "quads": view(abi.MESH_BUF_QUADS, (nq, 4), "<i4"),
+                "normals": view(abi.MESH_BUF_NORMALS, (nv, 3), "<f4") if has_n else None,
+                "ids": view(abi.MESH_BUF_IDS, (nv,), "<f4") if has_i else None}
+
+    def mesh_free(self):
+        """rmr_mesh_free: release the mesh and the extraction's working memory."""
+        self._mesh_info = None
+        self._chk(self._L.rmr_mesh_free(self._ctx))
 
     def sync(self):
         self._chk(self._L.rmr_sync(self._ctx))
@@ -955,6 +1030,79 @@ def bloom_pixels(rgba, params=None, **fields):
     if rc != abi.RMR_OK:
         raise RMRError(rc, "rmr_bloom_pixels: bad params or image")
     return out
+
+
+def _volume_desc(origin, spacing, shape):
+    d = abi.volume_desc(origin, spacing, shape)
+    bad = check_volume(d)
+    if bad:
+        raise RMRError(-1, "bad volume descriptor field '%s'" % bad)
+    return d
+
+
+def check_volume(origin, spacing=None, shape=None):
+    """rmr_check_volume (no GPU): None for a lattice in range (finite numbers, spacing > 0, 2 <= n <= 4096,
+    at most 2^30 points), else the name of the first failing field: 'origin', 'spacing', 'n' or 'points'.
+    Takes an abi.VolumeDesc or (origin, spacing, shape)."""
+    d = origin if isinstance(origin, abi.VolumeDesc) else abi.volume_desc(origin, spacing, shape)
+    bad = C.c_char_p()
+    rc = lib().rmr_check_volume(C.byref(d), C.byref(bad))
+    return None if rc == abi.RMR_OK else (bad.value or b"desc").decode()
+
+
+def surface_nets(dist, origin, spacing, iso=0.0):
+    """rmr_surface_nets (no GPU): the surface-nets mesh of a host volume dist[iz, iy, ix] (its shape gives the
+    lattice), count then fill: (vertices (V, 3) float32, quads (Q, 4) uint32)."""
+    a = np.ascontiguousarray(dist, np.float32)
+    if a.ndim != 3:
+        raise ValueError("surface_nets: a volume indexed [iz, iy, ix], got shape %r" % (a.shape,))
+    d = _volume_desc(origin, spacing, a.shape[::-1])
+    info = abi.MeshInfo()
+    rc = lib().rmr_surface_nets(_fp(a), C.byref(d), C.c_float(iso), None, 0, None, 0, C.byref(info))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_surface_nets: bad lattice or iso")
+    v = np.zeros((int(info.n_vertices), 3), np.float32)
+    q = np.zeros((int(info.n_quads), 4), np.uint32)
+    if len(v):
+        qp = (q if len(q) else np.zeros((1, 4), np.uint32)).ctypes.data_as(C.POINTER(C.c_uint32))
+        rc = lib().rmr_surface_nets(_fp(a), C.byref(d), C.c_float(iso), _fp(v), len(v), qp, len(q), C.byref(info))
+        if rc != abi.RMR_OK:
+            raise RMRError(rc, "rmr_surface_nets")
+    return v, q
+
+
+def quads_to_triangles(quads):
+    """Each quad (a, b, c, d) as the triangles (a, b, c), (a, c, d): (2 Q, 3)."""
+    return np.asarray(quads)[:, [0, 1, 2, 0, 2, 3]].reshape(-1, 3)
+
+
+def _mesh_arrays(vertices, quads, normals, ids):
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    q = np.ascontiguousarray(quads, np.uint32).reshape(-1, 4)
+    n = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    i = None if ids is None else np.ascontiguousarray(ids, np.float32).reshape(-1)
+    if (n is not None and len(n) != len(v)) or (i is not None and len(i) != len(v)):
+        raise ValueError("one normal and one id per vertex")
+    return v, q, n, i
+
+
+def encode_obj(path, vertices, quads, normals=None):
+    """rmr_encode_obj: 'v', optional 'vn', quad faces 'f a//a b//b c//c d//d' (1-based)."""
+    v, q, n, _ = _mesh_arrays(vertices, quads, normals, None)
+    rc = lib().rmr_encode_obj(os.fsencode(path), _fp(v), _fp(n) if n is not None else None, len(v),
+                              q.ctypes.data_as(C.POINTER(C.c_uint32)), len(q))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_encode_obj: %s" % path)
+
+
+def encode_ply(path, vertices, quads, normals=None, ids=None):
+    """rmr_encode_ply: binary little-endian PLY, x y z, optional nx ny nz, optional float material, faces
+    as lists of 4."""
+    v, q, n, i = _mesh_arrays(vertices, quads, normals, ids)
+    rc = lib().rmr_encode_ply(os.fsencode(path), _fp(v), _fp(n) if n is not None else None,
+                              _fp(i) if i is not None else None, len(v), q.ctypes.data_as(C.POINTER(C.c_uint32)), len(q))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_encode_ply: %s" % path)
 
 
 class _DeviceArray:
