@@ -971,6 +971,118 @@ int rmr_encode_obj(const char* path, const float* vertices, const float* normals
 int rmr_encode_ply(const char* path, const float* vertices, const float* normals, const float* ids, size_t n_vertices,
                    const uint32_t* quads, size_t n_quads);
 
+/* ---- light baking at surface points and mesh vertices --------------------------------------- */
+/* No counterpart in the reference. Additive: no other entry point changes. DESIGN.md §4.17.
+ *
+ * For n points p_i with unit normals n_i (float32 [n][3] each) and the seeds times[0 .. nspp): the light
+ * that reaches each point over the hemisphere about its normal, as the radiance a white Lambertian surface
+ * would leave there (irradiance / pi) and / or as cosine-weighted ambient occlusion. Sample k of point i
+ * is one ray; what it returns is the reference's trace() / march() bit for bit, and the samples of a point
+ * are folded in ascending k, so the result does not depend on how the work is cut into launches.
+ *
+ * The rule (csrc/rmr_bake_rule.h holds the parts the host and the kernels share). All arithmetic is
+ * float32, each operation rounded on its own except where fma() is written; `/` is the correctly rounded
+ * division; every select is a comparison.
+ *
+ * Invocation: idx = first_index + i (idx < 2^36), gx = idx & 4095, gy = idx >> 12 (< 2^24, so that gy +
+ *   time is one rounding): a 4096-wide image of points. first_index lets a caller bake a slice of a longer
+ *   list and get the bits of the whole.
+ * Reject: a point is rejected iff a coordinate of p or n is not finite or |n.n - 1| > 1e-6 (in double, each
+ *   product and sum rounded on its own; tighter than rmr_check_rays' 1e-5, so that the generated directions
+ *   are unit to float precision). Every output of a rejected point is 0, alpha included; it adds one to the
+ *   counter rmr_query_rejects reads (once per call that takes the list, whatever the flags and nspp); the
+ *   rays rmr_bake_rays_device generates for it carry gx = -1 (and gy = 0, o = d = 0, the sample's time).
+ * Direction of sample k: a fresh chain (rc = 0) with the seeds gxt = gx + times[k], gyt = gy + times[k],
+ *   started as main() starts a pixel's, with its first jitter call rand(gxt, gyt) (the value is not used);
+ *   then d = randHemisphere((p.x, p.y), (p.z, p.x), m) as the kernels' hemisphere() (csrc/rmr_trace.h;
+ *   RM1:270-304) states it: the seeds of the reference's diffuse bounce. (Without the first call the co of
+ *   randHemisphere's first rand() would be (p.x, p.y) + (gxt, gyt) * 0: the same theta for every seed, all
+ *   of a point's directions in one plane and a biased estimate. In the reference the three jitter calls of
+ *   main() always precede a bounce.) m = n, except where n.x == 0 && n.z == 0: the
+ *   reference's frame vanishes for every such n other than exactly (0, 1, 0) (a Cornell ceiling is one), so
+ *   there m = (0, 1, 0), and d.y is negated if n.y < 0.
+ * Ray: o = fma(n, bias, p) per component, direction d. The trace's own chain is again fresh: rc = 0 with the
+ *   same seeds. It is NOT continued from the direction's three rand() calls: the oracle's trace entry starts
+ *   at rc = 0 only, and the first rand() inside trace() has other `co` arguments (the first hit's
+ *   coordinates, which move with d), so the two chains differ from their first value on.
+ * Cosine: c_k = fma(n.z, d.z, fma(n.y, d.y, n.x * d.x)); c_k = c_k > 0 ? c_k : 0.
+ * Radiance (RMR_BAKE_RADIANCE): L_k = trace(o, d).rgb as rmr_trace_rays_device gives it. A sample with a
+ *   non-finite component of L_k is skipped. Over the used samples in ascending k: S = S + L_k * c_k per
+ *   channel (the product rounded, then the sum: no fma). out.rgb = (S + S) / (float)n_used, out.a =
+ *   (float)n_used; n_used == 0: rgb = 0. (The uniform hemisphere has pdf 1 / 2 pi, so this estimates
+ *   irradiance / pi: under a constant sky of radiance L it is L itself.)
+ * Occlusion (RMR_BAKE_AO): v_k = 0 iff the march of (o, d), as rmr_cast_rays states it (without normals:
+ *   the table-driven map, so every kernel class gives the same bits), is a hit with t < ao_distance, else
+ *   v_k = 1. ao = (sum c_k v_k) / (sum c_k), both sums in ascending k; a denominator of 0: ao = 1. */
+#define RMR_BAKE_RADIANCE 1
+#define RMR_BAKE_AO 2
+typedef struct rmr_bake_params {   /* 24 bytes */
+    int32_t flags;          /* RMR_BAKE_*, at least one;                      default RMR_BAKE_RADIANCE */
+    float bias;             /* finite;                                        default 0.002             */
+    float ao_distance;      /* > 0 or +inf (= the params' maxDist), not NaN;  default +inf              */
+    float origin_extent;    /* the device forms: a bound on |o coordinate| over the list (as
+                             * rmr_trace_rays_device's: finite, >= 0; any value at least the true maximum
+                             * gives the same bits; a point whose ray origin exceeds it is rejected as
+                             * well); the host forms compute it;               default 0                 */
+    uint64_t first_index;   /* first_index + n <= 2^36;                       default 0                 */
+} rmr_bake_params;
+void rmr_default_bake_params(rmr_bake_params* p);
+/* RMR_OK, or RMR_E_INVALID for a field outside the ranges above (origin_extent is not looked at) and NULL. */
+int rmr_check_bake_params(const rmr_bake_params* p);
+/* The reject rule on the host: RMR_OK iff no point is rejected; otherwise RMR_E_INVALID and *first_bad (when
+ * not NULL) is the first rejected index (RMR_OK: n). No context, no GPU. */
+int rmr_bake_check_points(const float* points, const float* normals, size_t n, size_t* first_bad);
+/* The fold on host arrays laid out [k][i] (L_rgb [nspp][n][3], c and cv [nspp][n]): out_rgba [n][4] from L_rgb
+ * and c, out_ao [n] from c and cv = c_k v_k; either output (with its inputs) may be NULL. No reject rule: every
+ * point is used. RMR_E_INVALID for nspp == 0, nspp > 2^24 or a missing input. No context, no GPU. */
+int rmr_bake_fold(const float* L_rgb, const float* c, const float* cv, size_t n, uint32_t nspp, float* out_rgba,
+                  float* out_ao);
+/* out[3 i + k] = the display's exact sRGB encode (rmr_display, rmr_srgb_thresholds) of rgb[3 i + k]: the number
+ * of thresholds <= the value (a NaN: 0). No context, no GPU. */
+int rmr_srgb8_pixels(const float* rgb, size_t n, uint8_t* out);
+/* rmr_encode_ply with "property uchar red / green / blue" (rgb8 [n_vertices][3]) after the other vertex
+ * properties; rgb8 NULL writes rmr_encode_ply's file. */
+int rmr_encode_ply_colors(const char* path, const float* vertices, const float* normals, const float* ids,
+                          const uint8_t* rgb8, size_t n_vertices, const uint32_t* quads, size_t n_quads);
+/* The bake of a host list: out_rgba [n][4] with RMR_BAKE_RADIANCE, out_ao [n] with RMR_BAKE_AO (the other may
+ * be NULL). params NULL = the defaults; origin_extent is taken from the list. Runs on the context's stream and
+ * synchronises. A bake is a render over a 1-D image of points: a tile is 64 consecutive points, a sample is k,
+ * and the per-launch plane budget (rmr_set_tuning, 64 bytes per ray) cuts the tile-samples into launches of
+ * the ray-source trace kernel (the scene-specialised one under rmr_set_jit's rule), within a point's sample
+ * set and within the point list alike; there are no launch slots. Occlusion launches hold 8 bytes per ray and
+ * rmr_set_query_grid caps their grid. State rules as rmr_trace_rays_device: RMR_E_STATE without a scene and
+ * with params.separate_channels; the accumulator, the half image, the estimate, the guides, every stage image,
+ * the sampled AOVs and the mesh are left as they are. RMR_E_INVALID for params rmr_check_bake_params refuses,
+ * nspp == 0, nspp > 2^24, first_index + n > 2^36 and ceil(n / 64) nspp >= 2^32. */
+int rmr_bake_points(rmr_ctx* ctx, const float* points, const float* normals, size_t n, const float* times,
+                    uint32_t nspp, const rmr_bake_params* params, float* out_rgba, float* out_ao);
+/* The same with device pointers (any 4-byte alignment; times stays a host array), queued on the context's
+ * stream without synchronising, as the other device forms; params->origin_extent is required (RMR_E_INVALID
+ * unless finite and >= 0). The per-point state between launches (16 bytes per point) is the library's. */
+int rmr_bake_points_device(rmr_ctx* ctx, const float* d_points, const float* d_normals, size_t n, const float* times,
+                           uint32_t nspp, const rmr_bake_params* params, float* d_out_rgba, float* d_out_ao);
+/* The generated rays as d_out[k][i] (device memory, n nspp rays), for rmr_cast_rays_device,
+ * rmr_trace_rays_device or a caller's own use; flags, ao_distance and origin_extent are not used. Needs no
+ * scene. Queued on the context's stream without synchronising. */
+int rmr_bake_rays_device(rmr_ctx* ctx, const float* d_points, const float* d_normals, size_t n, const float* times,
+                         uint32_t nspp, const rmr_bake_params* params, rmr_ray* d_out);
+/* The bake at the last extraction's vertices and normals (RMR_E_STATE without a mesh or without
+ * RMR_MESH_NORMALS), as rmr_bake_points_device with origin_extent taken from the lattice's box: its largest
+ * |coordinate| plus twice |bias|, times 1 + 2^-20, rounded up to the next float (any bound at least the true one
+ * gives the same bits).
+ * The results go to buffers that live and die with the mesh: colours [V][4] (RMR_BAKE_RADIANCE) and ao [V]
+ * (RMR_BAKE_AO); a second bake replaces what its flags name. No synchronisation.
+ * Surface-nets vertices lie off the surface by a fraction of a cell, inside a convex shape (on a unit sphere
+ * at spacing 3 / 16 by up to 0.065 of the spacing): with a bias below that every ray of such a vertex starts
+ * inside the shape, where the march ends at once. rmr_cli --mesh-bake uses 0.002 + spacing / 8. */
+int rmr_bake_mesh(rmr_ctx* ctx, const float* times, uint32_t nspp, const rmr_bake_params* params);
+/* The mesh's bake to host memory (either may be NULL); synchronises. RMR_E_STATE for what was not baked. */
+int rmr_read_mesh_bake(rmr_ctx* ctx, float* rgba, float* ao);
+#define RMR_MESH_BAKE_RGBA 0
+#define RMR_MESH_BAKE_AO 1
+/* Their device pointers (NULL: no mesh, not baked, or empty). No synchronisation. */
+void* rmr_mesh_bake_device_ptr(rmr_ctx* ctx, int which);
+
 /* ---- display ---------------------------------------------------------------------------- */
 /* Graphics::Display(centre, zoom, min, max) (Graphics.cpp:356-390 with createFQ 227-258 and
  * FullQuad.vs / FullQuad.fs), headless: draws the accumulator into a screen_w x screen_h RGBA8 image

@@ -48,6 +48,9 @@ EXPORTS = [
     "rmr_aov_resolved_device_ptr", "rmr_set_aov_launch_samples", "rmr_aov_init", "rmr_aov_fold", "rmr_aov_resolve",
     "rmr_check_volume", "rmr_sample_volume", "rmr_sample_volume_device", "rmr_extract_mesh", "rmr_read_mesh",
     "rmr_mesh_device_ptr", "rmr_mesh_free", "rmr_surface_nets", "rmr_encode_obj", "rmr_encode_ply",
+    "rmr_default_bake_params", "rmr_check_bake_params", "rmr_bake_check_points", "rmr_bake_fold", "rmr_srgb8_pixels",
+    "rmr_encode_ply_colors", "rmr_bake_points", "rmr_bake_points_device", "rmr_bake_rays_device", "rmr_bake_mesh",
+    "rmr_read_mesh_bake", "rmr_mesh_bake_device_ptr",
 ]
 
 
@@ -236,6 +239,23 @@ def lib(diag=None):
                                        C.c_size_t, C.POINTER(abi.MeshInfo)]),
         "rmr_encode_obj": (C.c_int, [C.c_char_p, fp, fp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]),
         "rmr_encode_ply": (C.c_int, [C.c_char_p, fp, fp, fp, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t]),
+        "rmr_default_bake_params": (None, [C.POINTER(abi.BakeParams)]),
+        "rmr_check_bake_params": (C.c_int, [C.POINTER(abi.BakeParams)]),
+        "rmr_bake_check_points": (C.c_int, [fp, fp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "rmr_bake_fold": (C.c_int, [fp, fp, fp, C.c_size_t, C.c_uint32, fp, fp]),
+        "rmr_srgb8_pixels": (C.c_int, [fp, C.c_size_t, C.POINTER(C.c_uint8)]),
+        "rmr_encode_ply_colors": (C.c_int, [C.c_char_p, fp, fp, fp, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint32),
+                                            C.c_size_t]),
+        "rmr_bake_points": (C.c_int, [vp, fp, fp, C.c_size_t, fp, C.c_uint32, C.POINTER(abi.BakeParams), fp, fp]),
+        "rmr_bake_points_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, fp, C.c_uint32,
+                                             C.POINTER(abi.BakeParams), C.c_void_p, C.c_void_p]),
+        "rmr_bake_rays_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, fp, C.c_uint32,
+                                           C.POINTER(abi.BakeParams), C.c_void_p]),
+        "rmr_bake_mesh": (C.c_int, [vp, fp, C.c_uint32, C.POINTER(abi.BakeParams)]),
+        "rmr_read_mesh_bake": (C.c_int, [vp, fp, fp]),
+        "rmr_mesh_bake_device_ptr": (vp, [vp, C.c_int]),
+        "rmr_diag_bake_kernels": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, fp, C.c_uint32,
+                                            C.POINTER(abi.BakeParams), C.c_void_p]),
         "rmr_diag_bloom_tail": (C.c_int, [vp, C.c_int]),
         "rmr_diag_bloom_time": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, fp]),
         "rmr_diag_tonemap_fold": (C.c_int, [vp, C.c_int]),

@@ -323,6 +323,26 @@ MESH_BUF_VERTICES = 0
 MESH_BUF_NORMALS = 1
 MESH_BUF_IDS = 2
 MESH_BUF_QUADS = 3
+
+
+# light baking at surface points and mesh vertices (rmr.h rmr_bake_points)
+BAKE_RADIANCE = 1
+BAKE_AO = 2
+MESH_BAKE_RGBA = 0
+MESH_BAKE_AO = 1
+
+
+class BakeParams(C.Structure):
+    _fields_ = [("flags", C.c_int32), ("bias", C.c_float), ("ao_distance", C.c_float), ("origin_extent", C.c_float),
+                ("first_index", C.c_uint64)]
+
+
+def bake_params(radiance=True, ao=False, bias=0.002, ao_distance=float("inf"), first_index=0, origin_extent=0.0):
+    """rmr_bake_params (the defaults are rmr_default_bake_params')."""
+    return BakeParams((BAKE_RADIANCE if radiance else 0) | (BAKE_AO if ao else 0), float(bias), float(ao_distance),
+                      float(origin_extent), int(first_index))
+
+
 # variance planes of the variance-guided denoiser (rmr.h)
 VARIANCE_SEED = 0
 VARIANCE_FILTERED = 1

@@ -28,6 +28,7 @@
 #include "adaptive.hpp"
 #include "rmr_camera.hpp"
 #include "rmr_ray_check.h"
+#include "rmr_bake_rule.h"
 #include "rmr_jit.hpp"
 #include "rmr_trail_rule.h"
 #include "scene.hpp"
@@ -72,6 +73,13 @@ hipError_t launch_mesh_emit(const rmr_volume_desc& d, const float* dist, float i
                             hipStream_t s);
 hipError_t launch_mesh_attr(const KParams& P, int np, const float* vertices, uint32_t n_vertices, float* normals, float* ids,
                             hipStream_t s);
+hipError_t launch_bake_rays(const BakeList& B, uint64_t s0, uint32_t cnt, float4* rec, unsigned long long* rejects,
+                            hipStream_t s);
+hipError_t launch_bake_ray_list(const BakeList& B, rmr_ray* out, unsigned long long* rejects, hipStream_t s);
+hipError_t launch_bake_ao(const KParams& P, int np, const BakeList& B, float ao_distance, uint64_t s0, uint32_t cnt,
+                          float2* plane, unsigned long long* rejects, int grid_cap, hipStream_t s);
+hipError_t launch_bake_fold(bool ao, const void* plane, const float4* rec, float4* state, uint64_t n, uint32_t nspp,
+                            uint64_t s0, uint32_t cnt, float* out, hipStream_t s);
 }  // namespace rmr
 
 using rmr::CompiledScene;
@@ -168,6 +176,16 @@ struct rmr_ctx {
     void* d_mesh_cell = nullptr;
     void* d_mesh_scan = nullptr;
     size_t mesh_dist_cap = 0, mesh_flag_cap = 0, mesh_cell_cap = 0, mesh_scan_cap = 0;   // bytes
+    // light baking (rmr_bake_points, rmr_bake.hip): the per-point state between launches (a
+    // float4 per point, grows only, freed at rmr_reload and rmr_destroy); the host form's device copies live
+    // in d_qin / d_qout. The mesh's bake (rmr_bake_mesh): colours [V][4] and ao [V], which go with the mesh,
+    // whose lattice is kept for the origins' bound
+    void* d_bake_state = nullptr;
+    size_t bake_state_cap = 0;            // bytes
+    float* d_mesh_rgba = nullptr;
+    float* d_mesh_ao = nullptr;
+    rmr_volume_desc mesh_desc{};
+    int mesh_baked = 0;                   // RMR_BAKE_*: what rmr_bake_mesh has (queued) for the current mesh
     // which of the output stages' images below are valid: the one place that says so (stage_state.hpp)
     rmr::StageState st;
     // first-hit guides and the preview denoiser (rmr_render_guides / rmr_denoise): three guide planes and
@@ -471,16 +489,16 @@ void free_aov(rmr_ctx* c) {
 
 // Release the mesh's buffers (the caller has synced the context's stream); there is no mesh afterwards.
 void drop_mesh(rmr_ctx* c) {
-    free_all({&c->d_mesh_v, &c->d_mesh_n, &c->d_mesh_id, &c->d_mesh_q});
+    free_all({&c->d_mesh_v, &c->d_mesh_n, &c->d_mesh_id, &c->d_mesh_q, &c->d_mesh_rgba, &c->d_mesh_ao});
     c->mesh_valid = false;
-    c->mesh_flags = 0;
+    c->mesh_flags = c->mesh_baked = 0;
     c->mesh_nv = c->mesh_nq = 0;
 }
-// The same and the extraction's working memory.
+// The same, the extraction's working memory and the bakes' per-point state.
 void free_mesh(rmr_ctx* c) {
     drop_mesh(c);
-    free_all({&c->d_mesh_dist, &c->d_mesh_flag, &c->d_mesh_cell, &c->d_mesh_scan});
-    c->mesh_dist_cap = c->mesh_flag_cap = c->mesh_cell_cap = c->mesh_scan_cap = 0;
+    free_all({&c->d_mesh_dist, &c->d_mesh_flag, &c->d_mesh_cell, &c->d_mesh_scan, &c->d_bake_state});
+    c->mesh_dist_cap = c->mesh_flag_cap = c->mesh_cell_cap = c->mesh_scan_cap = c->bake_state_cap = 0;
 }
 
 // Release the half image and the tile-error map (the caller has synced the context's stream).
@@ -1033,7 +1051,12 @@ int submit_launch(rmr_ctx* c, const KParams& P, rmr_ctx::Slot* S, bool use_jit, 
 // d_rays set (rmr_trace_rays_device): the list and the result live on the device, the records are
 // packed and the planes unpacked by kernels (rmr_query.hip), `extent` bounds the origins, and nothing
 // is copied or synchronised.
-struct RayList { const rmr_ray* rays; size_t n; float* out; const rmr_ray* d_rays; float* d_out; float extent; };
+// bake set (rmr_bake_points_device): the list is a bake's tile-samples instead (rmr_bake.hip: tile t of 64
+// points, sample k, at index t nspp + k; the plan's "samples" are these), n counts them, k_bake_rays writes
+// the records and k_bake_fold reads the planes: d_out is the points' [n][4] result.
+struct BakeJob { rmr::BakeList list; const float* h_times; float4* state; };
+struct RayList { const rmr_ray* rays; size_t n; float* out; const rmr_ray* d_rays; float* d_out; float extent;
+                 BakeJob* bake = nullptr; };
 
 // words of rmr_ctx::d_query: rays the device forms rejected (rmr_query_rejects); the device forms'
 // first rejected index (not read); the same two of a host form's call
@@ -1071,13 +1094,14 @@ void pack_rays(const RayList& rl, size_t u0, std::vector<float4>& h) {
 // in the plan (one "tile" of 64 units, ceil(n / 64) "samples": the same unit order), each launch is the
 // upload of its records, the ray-source kernel and the readback of its planes, and nothing is folded.
 // A device list (rl->d_rays) has k_pack_rays in the upload's place and k_unpack_rgba in the readback's, and
-// is not synchronised.
+// is not synchronised. A bake (rl->bake) is a device list whose units are a bake's tile-samples: k_bake_rays
+// writes the records from the points and k_bake_fold folds the planes onto the points' state (rmr_bake.hip).
 // Ray-source launches run on the context's stream: no launch slots.
 int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, int x1, int y1,
                  const float* times, uint32_t first_sample, uint32_t nspp, const RayList* rl = nullptr) {
     int r;
     if ((r = launch_precheck(c))) return r;
-    if (rl) nspp = (uint32_t)((rl->n + 63) / 64);
+    if (rl) nspp = rl->bake ? (uint32_t)rl->n : (uint32_t)((rl->n + 63) / 64);
     if ((!rl && tiles.empty()) || nspp == 0) return RMR_OK;
     const bool rays = rl || c->camera.model != RMR_CAMERA_VIEW;
     if (!c->view_set) default_view(c);
@@ -1094,7 +1118,7 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
         for (int k = 0; k < 3; k++) { cam.U[k] = f[k]; cam.V[k] = f[3 + k]; cam.F[k] = f[6 + k]; }
         org_extent = rmr::camera_origin_extent(m, c->view);
     }
-    if (rl && rl->d_rays) {
+    if (rl && (rl->d_rays || rl->bake)) {
         org_extent = (double)rl->extent;
         if ((r = ensure_query(c))) return r;
     } else if (rl) {
@@ -1112,6 +1136,7 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
     const rmr::SamplePlan sp = rmr::plan_samples(plane, nspp, c->samp_budget, rays ? 0 : c->launch_streams,
                                                  rays ? sizeof(float4) + rmr::kRayRecordBytes : sizeof(float4));
     const size_t chunk = sp.per_launch;
+    if (rl && rl->bake && (r = stage_times(c, rl->bake->h_times, rl->bake->list.nspp, &rl->bake->list.times))) return r;
     if (sp.slotted && c->slots.size() != (size_t)c->launch_streams) {
         if ((r = free_slots(c)) || (r = make_slots(c))) return r;
     }
@@ -1163,7 +1188,9 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
         P.time1 = rl ? 0.0f : times[k0];   // the seed when this launch has one sample (unit_pixel)
         P.n_units = (uint64_t)n * plane;
         std::vector<float4> h_rays;   // (a list's records; the launch is synchronised below)
-        if (rl && rl->d_rays) {
+        if (rl && rl->bake) {
+            HIPCHK(c, rmr::launch_bake_rays(rl->bake->list, k0, n, c->d_rays, c->d_query + kQueryRejects, c->stream));
+        } else if (rl && rl->d_rays) {
             HIPCHK(c, rmr::launch_pack_rays(rl->d_rays, rl->n, (uint64_t)k0 * 64, (uint32_t)P.n_units, rl->extent, c->d_rays,
                                             c->d_query + kQueryRejects, c->d_query + kQueryFirstBad, c->stream));
         } else if (rl) {
@@ -1200,7 +1227,10 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
             P.refill_threshold = refill_for(c->refill_threshold, park);
         }
         if ((r = submit_launch(c, P, S, use_jit, gp.grid, rays ? c->d_rays : nullptr, !rl))) return r;
-        if (rl && rl->d_rays) {
+        if (rl && rl->bake) {
+            HIPCHK(c, rmr::launch_bake_fold(false, P.samp, c->d_rays, rl->bake->state, rl->bake->list.n, rl->bake->list.nspp,
+                                            k0, n, rl->d_out, c->stream));
+        } else if (rl && rl->d_rays) {
             const size_t u0 = (size_t)k0 * 64, cnt = std::min<size_t>((size_t)P.n_units, rl->n - u0);
             HIPCHK(c, rmr::launch_unpack_rgba(P.samp, c->d_rays, rl->d_out + 4 * u0, (uint32_t)cnt, c->stream));
         } else if (rl) {
@@ -1833,23 +1863,7 @@ int rmr_candidate_grid(const float* prims, int n, int n_large, double E, double 
     return RMR_OK;
 }
 
-// sRGB decision points of Graphics::Display's GL_FRAMEBUFFER_SRGB write: byte(c) = round(255 srgb(c))
-// for c in [0, 1] (srgb: 12.92 c below 0.0031308, else 1.055 c^(1/2.4) - 0.055), so byte(c) >= k
-// <=> srgb(c) >= (k - 1/2) / 255 <=> c >= linear((k - 1/2) / 255); out[k] is that bound rounded up to
-// a float (for a float c the comparison is then exact), out[0] = 0.
-int rmr_srgb_thresholds(float out[256]) {
-    if (!out) return RMR_E_INVALID;
-    out[0] = 0.0f;
-    for (int k = 1; k < 256; k++) {
-        const double y = (k - 0.5) / 255.0;
-        const double lin = (y <= 0.04045) ? y / 12.92 : std::pow((y + 0.055) / 1.055, 2.4);
-        float f = (float)lin;
-        if ((double)f < lin) f = std::nextafter(f, 2.0f);
-        out[k] = f;
-    }
-    return RMR_OK;
-}
-
+// (rmr_srgb_thresholds, the sRGB decision points of the display's encode, is host-only code: bake.cpp)
 namespace {
 int display_common(rmr_ctx* c, float cx, float cy, float zoom, float min_x, float min_y, float max_x, float max_y,
                    int sw, int sh, uint32_t* dev) {
@@ -2504,6 +2518,7 @@ int rmr_extract_mesh(rmr_ctx* c, const rmr_volume_desc* desc, const rmr_mesh_par
         HIPCHK(c, rmr::launch_mesh_attr(P, c->accel.map_np, c->d_mesh_v, (uint32_t)nv, c->d_mesh_n, c->d_mesh_id, c->stream));
     }
     c->mesh_valid = true;
+    c->mesh_desc = *desc;
     c->mesh_flags = mp->flags;
     c->mesh_nv = info->n_vertices = nv;
     c->mesh_nq = info->n_quads = nq;
@@ -2545,6 +2560,183 @@ int rmr_mesh_free(rmr_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_mesh(c);
     return RMR_OK;
+}
+
+// ---- light baking at surface points and mesh vertices (rmr_bake.hip, rmr_bake_rule.h) ----
+namespace {
+// The call's params (NULL: the defaults) and counts, checked.
+int bake_args(rmr_ctx* c, const char* who, size_t n, const float* times, uint32_t nspp, const rmr_bake_params* params,
+              rmr_bake_params& q) {
+    if (params) q = *params;
+    else rmr_default_bake_params(&q);
+    if (rmr_check_bake_params(&q) != RMR_OK)
+        return fail(c, RMR_E_INVALID, std::string(who) + ": params fail rmr_check_bake_params (flags, bias, ao_distance, first_index)");
+    if (nspp == 0 || nspp > (1u << 24) || !times) return fail(c, RMR_E_INVALID, std::string(who) + ": 1 <= nspp <= 2^24 seeds");
+    if ((uint64_t)n > rmr::kBakeMaxIndex - q.first_index)
+        return fail(c, RMR_E_INVALID, std::string(who) + ": first_index + n exceeds 2^36");
+    if ((((uint64_t)n + 63) / 64) * (uint64_t)nspp >= ((uint64_t)1 << 32))
+        return fail(c, RMR_E_INVALID, std::string(who) + ": ceil(n / 64) nspp must stay below 2^32 (bake slices, first_index)");
+    return RMR_OK;
+}
+
+// The bake of a device list, queued: the radiance through render_tiles' plan and launches, the occlusion by
+// launches of its own kernel under the same budget (8 bytes per ray), each followed by its fold.
+int bake_device(rmr_ctx* c, const char* who, const float* d_points, const float* d_normals, size_t n, const float* times,
+                uint32_t nspp, const rmr_bake_params& q, float* d_rgba, float* d_ao) {
+    int r;
+    if ((r = launch_precheck(c))) return r;
+    if (c->params.separate_channels != 0)
+        return fail(c, RMR_E_STATE, std::string(who) + " with separate_channels set: a bake's ray has no channel passes");
+    if (!rmr::extent_ok(q.origin_extent))
+        return fail(c, RMR_E_INVALID, std::string(who) + ": origin_extent must be finite and >= 0");
+    if (n == 0) return RMR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((r = ensure_query(c))) return r;
+    if ((r = ensure_qbuf(c, &c->d_bake_state, &c->bake_state_cap, n * sizeof(float4)))) return r;
+    BakeJob job{{d_points, d_normals, (uint64_t)n, q.first_index, nullptr, nspp, q.bias, q.origin_extent}, times,
+                (float4*)c->d_bake_state};
+    const size_t n_ts = ((n + 63) / 64) * (size_t)nspp;
+    if (q.flags & RMR_BAKE_RADIANCE) {
+        const RayList rl{nullptr, n_ts, nullptr, nullptr, d_rgba, q.origin_extent, &job};
+        if ((r = render_tiles(c, std::vector<TileXY>(), 0, 0, 0, 0, nullptr, 0, 0, &rl))) return r;
+    }
+    if (q.flags & RMR_BAKE_AO) {
+        if (!c->view_set) default_view(c);
+        KParams P;
+        if ((r = view_params(c, P, (double)q.origin_extent))) return r;   // (the bound of the radiance pass: no new boxes)
+        if ((r = stage_times(c, times, nspp, &job.list.times))) return r;
+        // a point is counted as rejected once per call: by the radiance pass where there is one
+        unsigned long long* rejects = (q.flags & RMR_BAKE_RADIANCE) ? nullptr : c->d_query + kQueryRejects;
+        // (fewer than 2^31 units per launch, as the trace's: the kernels index a launch's units with 32 bits)
+        const size_t chunk = rmr::plan_samples(64, (uint32_t)n_ts, c->samp_budget, 0, sizeof(float2)).per_launch;
+        for (size_t k0 = 0; k0 < n_ts; k0 += chunk) {
+            const uint32_t cnt = (uint32_t)std::min(chunk, n_ts - k0);
+            if ((r = ensure_samp(c, ((size_t)cnt * 64 + 1) / 2))) return r;
+            c->last_samp = c->d_samp;
+            HIPCHK(c, rmr::launch_bake_ao(P, c->accel.map_np, job.list, q.ao_distance, k0, cnt, (float2*)c->d_samp, rejects,
+                                          c->query_grid, c->stream));
+            HIPCHK(c, rmr::launch_bake_fold(true, c->d_samp, nullptr, job.state, n, nspp, k0, cnt, d_ao, c->stream));
+        }
+    }
+    return RMR_OK;
+}
+}  // namespace
+
+int rmr_bake_points_device(rmr_ctx* c, const float* d_points, const float* d_normals, size_t n, const float* times,
+                           uint32_t nspp, const rmr_bake_params* params, float* d_out_rgba, float* d_out_ao) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_bake_params q;
+    int r;
+    if ((r = bake_args(c, "rmr_bake_points_device", n, times, nspp, params, q))) return r;
+    if (n && (!d_points || !d_normals || ((q.flags & RMR_BAKE_RADIANCE) && !d_out_rgba) || ((q.flags & RMR_BAKE_AO) && !d_out_ao)))
+        return fail(c, RMR_E_INVALID, "rmr_bake_points_device: null buffer");
+    return bake_device(c, "rmr_bake_points_device", d_points, d_normals, n, times, nspp, q, d_out_rgba, d_out_ao);
+}
+
+int rmr_bake_points(rmr_ctx* c, const float* points, const float* normals, size_t n, const float* times, uint32_t nspp,
+                    const rmr_bake_params* params, float* out_rgba, float* out_ao) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_bake_params q;
+    int r;
+    if ((r = bake_args(c, "rmr_bake_points", n, times, nspp, params, q))) return r;
+    const bool rad = (q.flags & RMR_BAKE_RADIANCE) != 0, ao = (q.flags & RMR_BAKE_AO) != 0;
+    if (n && (!points || !normals || (rad && !out_rgba) || (ao && !out_ao))) return fail(c, RMR_E_INVALID, "rmr_bake_points: null buffer");
+    // the origins' bound, over the points the rule uses
+    float ext = 0.0f;
+    for (size_t i = 0; i < n; i++) {
+        if (!rmr::bake_point_ok(points + 3 * i, normals + 3 * i)) continue;
+        float o[3];
+        rmr::bake_origin(points + 3 * i, normals + 3 * i, q.bias, o);
+        for (int k = 0; k < 3; k++) ext = std::max(ext, std::fabs(o[k]));
+    }
+    q.origin_extent = ext;
+    if (!rmr::extent_ok(ext)) return fail(c, RMR_E_INVALID, "rmr_bake_points: a ray origin (p + bias n) is not finite");
+    if ((r = launch_precheck(c))) return r;
+    if (n == 0) return bake_device(c, "rmr_bake_points", nullptr, nullptr, 0, times, nspp, q, nullptr, nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((r = ensure_qbuf(c, &c->d_qin, &c->qin_cap, n * 6 * sizeof(float)))) return r;
+    if ((r = ensure_qbuf(c, &c->d_qout, &c->qout_cap, n * 5 * sizeof(float)))) return r;
+    float* d_p = (float*)c->d_qin;
+    float* d_n = d_p + 3 * n;
+    float* d_rgba = (float*)c->d_qout;
+    float* d_ao = d_rgba + 4 * n;
+    HIPCHK(c, hipMemcpyAsync(d_p, points, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_n, normals, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((r = bake_device(c, "rmr_bake_points", d_p, d_n, n, times, nspp, q, d_rgba, d_ao))) return r;
+    if (rad) HIPCHK(c, hipMemcpyAsync(out_rgba, d_rgba, n * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (ao) HIPCHK(c, hipMemcpyAsync(out_ao, d_ao, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+int rmr_bake_rays_device(rmr_ctx* c, const float* d_points, const float* d_normals, size_t n, const float* times,
+                         uint32_t nspp, const rmr_bake_params* params, rmr_ray* d_out) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_bake_params q;
+    int r;
+    if ((r = bake_args(c, "rmr_bake_rays_device", n, times, nspp, params, q))) return r;
+    if (n && (!d_points || !d_normals || !d_out)) return fail(c, RMR_E_INVALID, "rmr_bake_rays_device: null buffer");
+    if (n == 0) return RMR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((r = ensure_query(c))) return r;
+    rmr::BakeList B{d_points, d_normals, (uint64_t)n, q.first_index, nullptr, nspp, q.bias, INFINITY};
+    if ((r = stage_times(c, times, nspp, &B.times))) return r;
+    HIPCHK(c, rmr::launch_bake_ray_list(B, d_out, c->d_query + kQueryRejects, c->stream));
+    return RMR_OK;
+}
+
+int rmr_bake_mesh(rmr_ctx* c, const float* times, uint32_t nspp, const rmr_bake_params* params) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!c->mesh_valid) return fail(c, RMR_E_STATE, "no mesh (call rmr_extract_mesh)");
+    if (!(c->mesh_flags & RMR_MESH_NORMALS)) return fail(c, RMR_E_STATE, "rmr_bake_mesh: the mesh has no normals (RMR_MESH_NORMALS)");
+    rmr_bake_params q;
+    int r;
+    const size_t nv = (size_t)c->mesh_nv;
+    if ((r = bake_args(c, "rmr_bake_mesh", nv, times, nspp, params, q))) return r;
+    // every vertex lies in the lattice's box; |n| is 1 to the reject rule's 1e-6
+    double ext = 0.0;
+    for (int a = 0; a < 3; a++) {
+        const double lo = (double)c->mesh_desc.origin[a];
+        const double hi = lo + (double)(c->mesh_desc.n[a] - 1) * (double)c->mesh_desc.spacing;
+        ext = std::max(ext, std::max(std::fabs(lo), std::fabs(hi)));
+    }
+    ext = (ext + 2.0 * std::fabs((double)q.bias)) * (1.0 + 0x1p-20);
+    q.origin_extent = std::nextafter((float)ext, INFINITY);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (nv && (q.flags & RMR_BAKE_RADIANCE) && !c->d_mesh_rgba &&
+        (r = alloc_all(c, {{&c->d_mesh_rgba, nv * 4 * sizeof(float)}}, "rmr_bake_mesh: cannot allocate the colours")))
+        return r;
+    if (nv && (q.flags & RMR_BAKE_AO) && !c->d_mesh_ao &&
+        (r = alloc_all(c, {{&c->d_mesh_ao, nv * sizeof(float)}}, "rmr_bake_mesh: cannot allocate the occlusion")))
+        return r;
+    if ((r = bake_device(c, "rmr_bake_mesh", c->d_mesh_v, c->d_mesh_n, nv, times, nspp, q, c->d_mesh_rgba, c->d_mesh_ao))) return r;
+    c->mesh_baked |= q.flags;
+    return RMR_OK;
+}
+
+int rmr_read_mesh_bake(rmr_ctx* c, float* rgba, float* ao) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!c->mesh_valid) return fail(c, RMR_E_STATE, "no mesh (call rmr_extract_mesh)");
+    if ((rgba && !(c->mesh_baked & RMR_BAKE_RADIANCE)) || (ao && !(c->mesh_baked & RMR_BAKE_AO)))
+        return fail(c, RMR_E_STATE, "rmr_read_mesh_bake: not baked (rmr_bake_mesh and its flags)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nv = (size_t)c->mesh_nv;
+    if (nv && rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->d_mesh_rgba, nv * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (nv && ao) HIPCHK(c, hipMemcpyAsync(ao, c->d_mesh_ao, nv * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+void* rmr_mesh_bake_device_ptr(rmr_ctx* c, int which) {
+    if (!c || !c->mesh_valid) return nullptr;
+    if (which == RMR_MESH_BAKE_RGBA && (c->mesh_baked & RMR_BAKE_RADIANCE)) return c->d_mesh_rgba;
+    if (which == RMR_MESH_BAKE_AO && (c->mesh_baked & RMR_BAKE_AO)) return c->d_mesh_ao;
+    return nullptr;
 }
 
 // ---- first-hit guides and the preview denoiser (rmr_guides.hip, rmr_denoise.hip) ------------------
@@ -3379,6 +3571,33 @@ int rmr_diag_bloom_time(rmr_ctx* c, int which, int levels, int n, float* ms) {
         if (which == 3) return hipMemcpyAsync(c->d_bl, c->d_accum, px * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
         return bloom_queue(c, c->d_accum, q, which);
     });
+}
+
+// Diagnostic library only (not in include/rmr.h; tools/bake_time.py): the radiance bake's own kernels alone,
+// k_bake_rays and k_bake_fold of every launch of rmr_bake_points_device's plan without the trace between them
+// (the fold reads whatever the planes hold). Queued on the context's stream, no synchronisation.
+int rmr_diag_bake_kernels(rmr_ctx* c, const float* d_points, const float* d_normals, size_t n, const float* times,
+                          uint32_t nspp, const rmr_bake_params* params, float* d_out_rgba) {
+    if (!c || !d_points || !d_normals || !d_out_rgba || n == 0) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_bake_params q;
+    int r;
+    if ((r = bake_args(c, "rmr_diag_bake_kernels", n, times, nspp, params, q))) return r;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((r = ensure_query(c))) return r;
+    if ((r = ensure_qbuf(c, &c->d_bake_state, &c->bake_state_cap, n * sizeof(float4)))) return r;
+    rmr::BakeList B{d_points, d_normals, (uint64_t)n, q.first_index, nullptr, nspp, q.bias, q.origin_extent};
+    if ((r = stage_times(c, times, nspp, &B.times))) return r;
+    const size_t n_ts = ((n + 63) / 64) * (size_t)nspp;
+    const size_t chunk = rmr::plan_samples(64, (uint32_t)n_ts, c->samp_budget, 0, sizeof(float4) + rmr::kRayRecordBytes).per_launch;
+    for (size_t k0 = 0; k0 < n_ts; k0 += chunk) {
+        const uint32_t cnt = (uint32_t)std::min(chunk, n_ts - k0);
+        if ((r = ensure_samp(c, (size_t)cnt * 64)) || (r = ensure_rays(c, (size_t)cnt * 64))) return r;
+        c->last_samp = c->d_samp;
+        HIPCHK(c, rmr::launch_bake_rays(B, k0, cnt, c->d_rays, nullptr, c->stream));
+        HIPCHK(c, rmr::launch_bake_fold(false, c->d_samp, c->d_rays, (float4*)c->d_bake_state, n, nspp, k0, cnt, d_out_rgba, c->stream));
+    }
+    return RMR_OK;
 }
 
 // Diagnostic library only (not in include/rmr.h; tools/tonemap_time.py): whether k_lum_hist folds equal

@@ -71,6 +71,9 @@ struct Options {
     double mesh_bounds[6] = {0, 0, 0, 0, 0, 0};   // --mesh-bounds x0,y0,z0,x1,y1,z1
     int mesh_grid = 128;            // --mesh-grid N: cells along the longest side
     float mesh_iso = 0.0f;          // --mesh-iso V
+    int mesh_bake = 0;              // --mesh-bake N[:AO_DISTANCE]: seeds of the vertex bake (0: none)
+    bool mesh_bake_ao = false;
+    float mesh_bake_ao_distance = 0.0f;
     double adaptive = -1.0;         // --adaptive T: the tile-error threshold, < 0 = uniform sampling
     int min_samples = 16, pass_samples = 16;   // --min-samples / --pass-samples (rmr_adaptive_params)
     bool have_camera = false;
@@ -409,7 +412,9 @@ rmr_volume_desc mesh_lattice(const Options& o) {
 }
 
 // --mesh FILE: rmr_extract_mesh over that lattice with normals and material ids, written as OBJ (v, vn, f) or
-// binary PLY (x y z nx ny nz material)
+// binary PLY (x y z nx ny nz material). --mesh-bake N: rmr_bake_mesh with the render's seed schedule, the
+// PLY's vertex colours being the display's sRGB bytes of the baked radiance; with :AO_DISTANCE the radiance
+// times the occlusion within that distance (the product rounded to float32).
 bool write_mesh(const Options& o) {
     rmr_ctx* c = Graphics::context();
     auto fail = [&](const std::string& what) {
@@ -423,7 +428,30 @@ bool write_mesh(const Options& o) {
     std::vector<float> v(3 * (size_t)info.n_vertices), n(3 * (size_t)info.n_vertices), ids((size_t)info.n_vertices);
     std::vector<uint32_t> q(4 * (size_t)info.n_quads);
     if (rmr_read_mesh(c, v.data(), n.data(), ids.data(), q.data()) != RMR_OK) return fail("rmr_read_mesh");
-    const int rc = o.mesh_ply ? rmr_encode_ply(o.mesh.c_str(), v.data(), n.data(), ids.data(), (size_t)info.n_vertices, q.data(), (size_t)info.n_quads)
+    std::vector<uint8_t> rgb8;
+    if (o.mesh_bake > 0) {
+        const size_t nv = (size_t)info.n_vertices;
+        std::vector<float> times((size_t)o.mesh_bake), rgba(4 * nv), ao(nv), rgb(3 * nv);
+        for (int s = 0; s < o.mesh_bake; s++) times[(size_t)s] = seed_time(o.frame, (unsigned)s);
+        rmr_bake_params bp;
+        rmr_default_bake_params(&bp);
+        // surface-nets vertices lie off the surface by a fraction of a cell (inside a convex shape): lift the rays'
+        // origins past that, or every ray of such a vertex starts inside the shape
+        bp.bias = 0.002f + 0.125f * d.spacing;
+        if (o.mesh_bake_ao) {
+            bp.flags |= RMR_BAKE_AO;
+            bp.ao_distance = o.mesh_bake_ao_distance;
+        }
+        if (rmr_bake_mesh(c, times.data(), (uint32_t)o.mesh_bake, &bp) != RMR_OK) return fail("rmr_bake_mesh");
+        if (rmr_read_mesh_bake(c, rgba.data(), o.mesh_bake_ao ? ao.data() : nullptr) != RMR_OK) return fail("rmr_read_mesh_bake");
+        for (size_t i = 0; i < nv; i++)
+            for (int k = 0; k < 3; k++) rgb[3 * i + (size_t)k] = o.mesh_bake_ao ? rgba[4 * i + (size_t)k] * ao[i] : rgba[4 * i + (size_t)k];
+        rgb8.resize(3 * nv);
+        if (rmr_srgb8_pixels(rgb.data(), nv, rgb8.data()) != RMR_OK) return fail("rmr_srgb8_pixels");
+    }
+    const int rc = o.mesh_bake > 0 ? rmr_encode_ply_colors(o.mesh.c_str(), v.data(), n.data(), ids.data(), rgb8.data(),
+                                                           (size_t)info.n_vertices, q.data(), (size_t)info.n_quads)
+                   : o.mesh_ply ? rmr_encode_ply(o.mesh.c_str(), v.data(), n.data(), ids.data(), (size_t)info.n_vertices, q.data(), (size_t)info.n_quads)
                               : rmr_encode_obj(o.mesh.c_str(), v.data(), n.data(), (size_t)info.n_vertices, q.data(), (size_t)info.n_quads);
     if (rc != RMR_OK) {
         std::cerr << "--mesh: cannot write " << o.mesh << std::endl;
@@ -557,6 +585,10 @@ void usage() {
         "  --mesh-grid N       cells along the box's longest side (1..4095, default 128); the spacing is that\n"
         "                      side over N, the other sides are rounded up to whole cells\n"
         "  --mesh-iso V        the level that is meshed (default 0; V > 0 grows the shape)\n"
+        "  --mesh-bake N[:AO_DISTANCE]  bake N samples of light per vertex (rmr.h rmr_bake_mesh; seeds of --frame)\n"
+        "                      into the PLY's uchar red green blue (the display's sRGB encode); with AO_DISTANCE\n"
+        "                      (> 0 or inf) the colour is the radiance times the occlusion within it; the rays\n"
+        "                      start 0.002 + an eighth of the lattice spacing off the vertex; needs --mesh FILE.ply\n"
         "  --adaptive T        adaptive sampling: render until every block's tile error is <= T, at most\n"
         "                      --samples per pixel, over the whole image; prints passes, mean spp, open tiles\n"
         "                      and max error; with --aov also PREFIX_spp.pfm (R = samples) and PREFIX_error.pfm\n"
@@ -735,6 +767,20 @@ bool parse(int argc, char** argv, Options& o) {
             o.mesh_iso = std::strtof(v, &end);
             if (end == v || *end != '\0' || !std::isfinite(o.mesh_iso)) return false;
             o.have_mesh_opts = true;
+        } else if (a == "--mesh-bake") {
+            char* end = nullptr;
+            const char* v = next("--mesh-bake");
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || n < 1 || n > (1L << 24)) return false;
+            o.mesh_bake = (int)n;
+            if (*end == ':') {
+                const char* w = end + 1;
+                o.mesh_bake_ao_distance = std::strtof(w, &end);
+                if (end == w || *end != '\0' || !(o.mesh_bake_ao_distance > 0.0f)) return false;
+                o.mesh_bake_ao = true;
+            } else if (*end != '\0') {
+                return false;
+            }
         }
         else if (a == "--adaptive") {
             char* end = nullptr;
@@ -793,6 +839,10 @@ bool parse(int argc, char** argv, Options& o) {
     }
     if (o.mesh.empty() ? (o.have_mesh_bounds || o.have_mesh_opts) : !o.have_mesh_bounds) {
         std::fprintf(stderr, "--mesh FILE.obj|FILE.ply needs --mesh-bounds x0,y0,z0,x1,y1,z1 (and they need --mesh)\n");
+        return false;
+    }
+    if (o.mesh_bake > 0 && (o.mesh.empty() || !o.mesh_ply)) {
+        std::fprintf(stderr, "--mesh-bake needs --mesh FILE.ply (an OBJ has no vertex colours)\n");
         return false;
     }
     if (!o.mesh.empty()) {

@@ -517,6 +517,101 @@ class Renderer:
         self._mesh_info = None
         self._chk(self._L.rmr_mesh_free(self._ctx))
 
+    # -- light baking at surface points and mesh vertices (rmr.h) --
+    @staticmethod
+    def _bake_params(params, fields):
+        if params is not None and fields:
+            raise ValueError("params or its fields as keywords, not both (got params and %s)" % ", ".join(sorted(fields)))
+        q = abi.bake_params(**fields) if params is None else params
+        if not isinstance(q, abi.BakeParams):
+            raise ValueError("params: an abi.BakeParams (abi.bake_params(...))")
+        return q
+
+    def bake_points(self, points, normals, times, params=None, **fields):
+        """rmr_bake_points: the light at n surface points with unit normals ((n, 3) float32 each) from the
+        samples seeded `times`: a dict of 'rgba' ((n, 4) float32: irradiance / pi and the samples used) with
+        the radiance flag and 'ao' ((n,) float32) with the occlusion flag, None for what was not asked for.
+        params: an abi.BakeParams, or its fields as keywords (abi.bake_params: radiance, ao, bias,
+        ao_distance, first_index). A rejected point (rmr.h) gives zeros and counts in query_rejects()."""
+        q = self._bake_params(params, fields)
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if len(p) != len(nn):
+            raise ValueError("one normal per point")
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        rgba = np.zeros((len(p), 4), np.float32) if q.flags & abi.BAKE_RADIANCE else None
+        ao = np.zeros((len(p),), np.float32) if q.flags & abi.BAKE_AO else None
+        self._chk(self._L.rmr_bake_points(self._ctx, _fp(p), _fp(nn), len(p), _fp(t) if len(t) else None, len(t), C.byref(q),
+                                          _fp(rgba) if rgba is not None else None, _fp(ao) if ao is not None else None))
+        return {"rgba": rgba, "ao": ao}
+
+    @staticmethod
+    def _device_points(points, normals):
+        import torch
+        for a in (points, normals):
+            if not (a.is_cuda and a.dtype == torch.float32 and a.dim() == 2 and a.shape[1] == 3 and a.is_contiguous()):
+                raise ValueError("points, normals: contiguous (n, 3) float32 CUDA tensors")
+        if points.shape[0] != normals.shape[0] or points.device != normals.device:
+            raise ValueError("one normal per point, on the points' device")
+        return points.shape[0]
+
+    def bake_points_device(self, points, normals, times, origin_extent, params=None, **fields):
+        """rmr_bake_points_device: bake_points on torch CUDA tensors ((n, 3) float32 each), the results as
+        torch tensors on the same device; queued on the context's stream (set_stream), no copy to the host
+        and no sync. origin_extent: a bound on |coordinate| of every ray origin p + bias n."""
+        import torch
+        q = self._bake_params(params, fields)
+        q = abi.BakeParams(q.flags, q.bias, q.ao_distance, float(origin_extent), q.first_index)
+        n = self._device_points(points, normals)
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        rgba = torch.empty((n, 4), dtype=torch.float32, device=points.device) if q.flags & abi.BAKE_RADIANCE else None
+        ao = torch.empty((n,), dtype=torch.float32, device=points.device) if q.flags & abi.BAKE_AO else None
+        self._chk(self._L.rmr_bake_points_device(self._ctx, points.data_ptr(), normals.data_ptr(), n,
+                                                 _fp(t) if len(t) else None, len(t), C.byref(q),
+                                                 rgba.data_ptr() if rgba is not None else None,
+                                                 ao.data_ptr() if ao is not None else None))
+        return {"rgba": rgba, "ao": ao}
+
+    def bake_rays_device(self, points, normals, times, params=None, **fields):
+        """rmr_bake_rays_device: the rays the bake generates, a (len(times) * n, 10) float32 CUDA tensor (views
+        of abi.RAY_DTYPE, ray [k * n + i] = sample k of point i) for trace_rays_device / cast_rays_device; a
+        rejected point's rays carry gx = -1. Queued on the context's stream, no sync."""
+        import torch
+        q = self._bake_params(params, fields)
+        n = self._device_points(points, normals)
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        out = torch.empty((len(t) * n, 10), dtype=torch.float32, device=points.device)
+        self._chk(self._L.rmr_bake_rays_device(self._ctx, points.data_ptr(), normals.data_ptr(), n,
+                                               _fp(t) if len(t) else None, len(t), C.byref(q), out.data_ptr()))
+        return out
+
+    def bake_mesh(self, times, params=None, **fields):
+        """rmr_bake_mesh: bake at the last extraction's vertices and normals into buffers that live with the
+        mesh (read_mesh_bake, mesh_bake_device). Queued on the context's stream, no sync."""
+        q = self._bake_params(params, fields)
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        self._chk(self._L.rmr_bake_mesh(self._ctx, _fp(t) if len(t) else None, len(t), C.byref(q)))
+
+    def read_mesh_bake(self, rgba=True, ao=False):
+        """rmr_read_mesh_bake: the mesh's baked 'rgba' (V, 4) and / or 'ao' (V,) as a dict (None: not asked for)."""
+        nv = (self._mesh_info or (0,))[0]
+        c = np.zeros((nv, 4), np.float32) if rgba else None
+        a = np.zeros((nv,), np.float32) if ao else None
+        self._chk(self._L.rmr_read_mesh_bake(self._ctx, _fp(c) if rgba else None, _fp(a) if ao else None))
+        return {"rgba": c, "ao": a}
+
+    def mesh_bake_device(self):
+        """rmr_mesh_bake_device_ptr: the mesh's bake as torch tensors on the context's device, views of the
+        library's memory (no copy, no sync): 'rgba' (V, 4) and 'ao' (V,), None for what was not baked. Valid
+        until the next extraction, mesh_free or reload."""
+        import torch
+        nv = (self._mesh_info or (0,))[0]
+        out = {}
+        for name, which, shape in (("rgba", abi.MESH_BAKE_RGBA, (nv, 4)), ("ao", abi.MESH_BAKE_AO, (nv,))):
+            ptr = self._L.rmr_mesh_bake_device_ptr(self._ctx, which) if nv else None
+            out[name] = torch.as_tensor(_DeviceArray(ptr, shape, self), device="cuda:%d" % self._device) if ptr else None
+        return out
+
     def sync(self):
         self._chk(self._L.rmr_sync(self._ctx))
 
@@ -1095,14 +1190,70 @@ def encode_obj(path, vertices, quads, normals=None):
         raise RMRError(rc, "rmr_encode_obj: %s" % path)
 
 
-def encode_ply(path, vertices, quads, normals=None, ids=None):
+def encode_ply(path, vertices, quads, normals=None, ids=None, *, colors=None):
     """rmr_encode_ply: binary little-endian PLY, x y z, optional nx ny nz, optional float material, faces
-    as lists of 4."""
+    as lists of 4. colors: (V, 3) uint8 (srgb8 of a bake), written as uchar red green blue
+    (rmr_encode_ply_colors)."""
     v, q, n, i = _mesh_arrays(vertices, quads, normals, ids)
-    rc = lib().rmr_encode_ply(os.fsencode(path), _fp(v), _fp(n) if n is not None else None,
-                              _fp(i) if i is not None else None, len(v), q.ctypes.data_as(C.POINTER(C.c_uint32)), len(q))
+    qp = q.ctypes.data_as(C.POINTER(C.c_uint32))
+    if colors is None:
+        rc = lib().rmr_encode_ply(os.fsencode(path), _fp(v), _fp(n) if n is not None else None,
+                                  _fp(i) if i is not None else None, len(v), qp, len(q))
+    else:
+        c = np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+        if len(c) != len(v):
+            raise ValueError("one colour per vertex")
+        rc = lib().rmr_encode_ply_colors(os.fsencode(path), _fp(v), _fp(n) if n is not None else None,
+                                         _fp(i) if i is not None else None, c.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                         len(v), qp, len(q))
     if rc != abi.RMR_OK:
         raise RMRError(rc, "rmr_encode_ply: %s" % path)
+
+
+def srgb8(rgb):
+    """rmr_srgb8_pixels (no GPU): the display's exact sRGB encode of an (..., 3) float array, uint8 of the same
+    shape."""
+    a = np.ascontiguousarray(rgb, np.float32)
+    if a.ndim < 1 or a.shape[-1] != 3:
+        raise ValueError("srgb8: an (..., 3) array")
+    out = np.zeros(a.shape, np.uint8)
+    rc = lib().rmr_srgb8_pixels(_fp(a), a.size // 3, out.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_srgb8_pixels")
+    return out
+
+
+def check_bake_params(params=None, **fields):
+    """rmr_check_bake_params (no GPU): True iff the params are in range."""
+    q = abi.bake_params(**fields) if params is None else params
+    return lib().rmr_check_bake_params(C.byref(q)) == abi.RMR_OK
+
+
+def bake_check_points(points, normals):
+    """rmr_bake_check_points (no GPU): the first index the bake's reject rule refuses, or None."""
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if len(p) != len(n):
+        raise ValueError("one normal per point")
+    bad = C.c_size_t(0)
+    rc = lib().rmr_bake_check_points(_fp(p), _fp(n), len(p), C.byref(bad))
+    return None if rc == abi.RMR_OK else int(bad.value)
+
+
+def bake_fold(L_rgb, c, cv=None):
+    """rmr_bake_fold (no GPU): the bake's fold of host arrays laid out [k][i]: L_rgb (N, n, 3) or None, c (N, n),
+    cv (N, n) or None; (rgba (n, 4) or None, ao (n,) or None)."""
+    cc = np.ascontiguousarray(c, np.float32)
+    nspp, n = cc.shape
+    L = None if L_rgb is None else np.ascontiguousarray(L_rgb, np.float32).reshape(nspp, n, 3)
+    v = None if cv is None else np.ascontiguousarray(cv, np.float32).reshape(nspp, n)
+    rgba = np.zeros((n, 4), np.float32) if L is not None else None
+    ao = np.zeros((n,), np.float32) if v is not None else None
+    rc = lib().rmr_bake_fold(_fp(L) if L is not None else None, _fp(cc), _fp(v) if v is not None else None, n, nspp,
+                             _fp(rgba) if rgba is not None else None, _fp(ao) if ao is not None else None)
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_bake_fold")
+    return rgba, ao
 
 
 class _DeviceArray:
