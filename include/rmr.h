@@ -195,7 +195,9 @@ int rmr_get_counters(rmr_ctx* ctx, uint64_t out[16]);
  * claim / ray cycles, uncertified hits, lanes per full map() batch, and the lane-slot schedule's passes,
  * park steps, lost lane-iterations by cause and events per batch); zeros in every other build;
  * [31..33] the trailing steps of the lane-slot kernels (rmr_set_trail_steps), in every build: steps taken
- * (lane-level; part of [0]), passes run (wave-level), lanes evaluated in the passes (taken + refused). */
+ * (lane-level; part of [0]), passes run (wave-level), lanes evaluated in the passes (taken + refused);
+ * [12] in a lane-slot kernel built with -DRMR_TRAIL_CHECK (a diagnostic): the lanes among those evaluated
+ * at a point beyond the launch's eps bound (rmr_trail_rule.h); it must stay 0. */
 int rmr_get_counters_n(rmr_ctx* ctx, uint64_t* out, int n);
 /* Select kernel implementation (0 = persistent wavefront kernel, 1 = one launch-thread per path). */
 int rmr_set_kernel(rmr_ctx* ctx, int kernel);

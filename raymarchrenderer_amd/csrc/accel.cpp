@@ -326,6 +326,16 @@ double escape_inflation(const float eye[3], double esc_extent, float max_dist) {
     return 0.002 + std::ldexp(e + 2.0 * esc_extent + 3.0 * std::fabs((double)max_dist), -16);
 }
 
+float trail_eps_bound(const float org[3], double esc_extent, double infl, float err_extent) {
+    double e = 0.0;
+    for (int k = 0; k < 3; k++) e = std::max(e, std::fabs((double)org[k]));
+    // every corner of an inflated box has |.|_inf <= esc_extent + infl
+    const double B = (std::max(e, esc_extent + infl) + 0.01) * (1.0 + 0x1p-15);
+    const double eps = std::ldexp(B + 0.002 + (double)err_extent, -17) + 0x1p-60;
+    if (!(eps < 0x1p127)) return INFINITY;   // (a NaN or infinite coordinate included)
+    return std::nextafter((float)eps, INFINITY);
+}
+
 std::vector<float> inflate_escape_boxes(const std::vector<float>& raw, double infl) {
     std::vector<float> bx(raw.size());
     for (size_t i = 0; i < bx.size(); i++)   // outward in double, then to float

@@ -90,6 +90,10 @@ CacheFacts cache_kernel_facts(const SceneAccel& a, bool grid_built);
 // (|p| <= |eye| + E + 3 maxDist) + the rounding of the slab parameters
 double escape_inflation(const float eye[3], double esc_extent, float max_dist);
 std::vector<float> inflate_escape_boxes(const std::vector<float>& raw, double infl);
+// KParams::trail_eps_hi of a launch with the escape bound on (rmr_trail_rule.h: the derivation of B): RU(2^-17
+// (B + 0.002 + E) + 2^-60) with B = (max(|org|_inf, esc_extent + infl) + 0.01)(1 + 2^-15), E = err_extent;
+// +inf where that is not a finite float
+float trail_eps_bound(const float org[3], double esc_extent, double infl, float err_extent);
 
 // ---- launch planning ----
 

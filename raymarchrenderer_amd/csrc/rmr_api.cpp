@@ -579,6 +579,7 @@ KParams scene_params(const rmr_ctx* c) {
     P.n_prims = (int)s.prims.size();
     P.am_r2 = a.am_r2;
     P.npc_eps0 = a.npc_eps0;
+    P.trail_eps_hi = INFINITY;   // (the launch's escape bound sets it, escape_params)
     P.cert_k = a.cert_k;
     P.full_threshold = c->full_threshold;
     P.n_mats = (int)(s.variant == RMR_VARIANT_RM3 ? s.spectral.size() : s.materials.size());
@@ -935,6 +936,9 @@ int escape_params(rmr_ctx* c, KParams& P, double org_extent = -1.0) {
     }
     P.esc_boxes = c->d_esc;
     P.n_esc = (int)(a.esc_raw.size() / 6);
+    // trailing steps (rmr_trail_rule.h): eps at every point a march bounded by these boxes can evaluate; without
+    // the bound there is none, the rule refuses every lane, and the launch takes no trailing step (render_tiles)
+    P.trail_eps_hi = P.esc_on ? rmr::trail_eps_bound(org, a.esc_extent, infl, a.err_extent) : INFINITY;
     return RMR_OK;
 }
 
@@ -1223,6 +1227,7 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
             // only for a march that advances (rmr_trail_rule.h: the rule's t >= t0)
             int trail = !jk.trail ? 0 : (c->trail_steps >= 0 ? c->trail_steps : jk.trail_k);
             if (!(P.step_mult > 0.0f) || !std::isfinite(P.step_mult)) trail = 0;
+            if (!std::isfinite(P.trail_eps_hi)) trail = 0;   // no escape bound: no bound of eps either
             P.shade_threshold = park | (batch << 8) | (std::min(trail, (int)rmr::kTrailMaxSteps) << 16);
             P.refill_threshold = refill_for(c->refill_threshold, park);
         }

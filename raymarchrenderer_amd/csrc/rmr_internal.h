@@ -63,6 +63,9 @@ constexpr int kCntOverflow = 16;         // lane-slot kernels: events deposited 
 constexpr int kCntTrailSteps = 31;       //   trailing steps taken (lane-level; part of counter 0)
 constexpr int kCntTrailPasses = 32;      //   trailing passes run (wave-level)
 constexpr int kCntTrailLanes = 33;       //   lanes evaluated in those passes (taken + refused)
+// ... built with -DRMR_TRAIL_CHECK (a diagnostic; the word is free in the lane-slot kernels' other builds but
+// the wave-times one): lanes evaluated in passes at a point whose eps(p) exceeds KParams::trail_eps_hi
+constexpr int kCntTrailCheck = 12;
 // RMR_PROFILE builds (rmr_trace.h trace_main), zero otherwise:
 constexpr int kCntProfClaim = 17;        // refill: cycles in work-queue claims
 constexpr int kCntProfRays = 18;         // refill: cycles in the chunk's primary rays
@@ -115,6 +118,9 @@ struct KParams {
     float cert_k;               // certified getNormal probes: the bound of rmr_trace.h am_normal_cert
     int32_t esc_on;             // escape bound (rmr_trace.h ray_exit): sphere/box scenes
     int32_t eye_step;           // primary rays' first march step from map(eye) (rmr_trace.h eye_map)
+    // trailing steps: the launch's bound of eps(x) at every point a pass evaluates (rmr_trail_rule.h; +inf:
+    // no pass runs); in the four bytes that pad eye_step to the next pointer, so that no other field moves
+    float trail_eps_hi;
     const float* esc_boxes;     // n_esc inflated boxes (lo.xyz, hi.xyz) covering every primitive
     int32_t n_esc;
     int32_t full_threshold;     // nearest-primitive cache: bits 0-7 lanes per full map() batch; bits 8-15 R:
@@ -163,6 +169,9 @@ struct KParams {
                                 // RMR_LANE_SLOTS): finished marches per park step | slot events per batch << 8
     int32_t refill_threshold;   // idle lanes before a wave fetches new units
 };
+static_assert(__builtin_offsetof(KParams, trail_eps_hi) + 4 == __builtin_offsetof(KParams, esc_boxes) &&
+                  __builtin_offsetof(KParams, esc_boxes) == 192,
+              "trail_eps_hi fills the padding ahead of esc_boxes: no other field moves");
 
 // One pass of the a-trous preview filter (rmr_denoise.hip): in -> out (W x H float4 each, never the
 // same buffer) guided by the first-hit planes of rmr_guides.hip.

@@ -2586,7 +2586,10 @@ static_assert(RMR_QUEUE_PARTS >= 1 && RMR_QUEUE_PARTS <= 64 && RMR_QUEUE_PARTS *
 // returns — and a lane whose bound fails sits the pass out, unchanged, until the next iteration's map.
 // No lane waits for another and no state crosses iterations. A pass no lane qualifies for is not run.
 // The primitive's numbers come from the table the certified probes read (P.dprims, scene order), or from
-// a copy of it in LDS (RMR_TRAIL_LDS: scenes of at most kTrailLdsPrims primitives).
+// a copy of it in LDS (RMR_TRAIL_LDS: scenes of at most kTrailLdsPrims primitives), whose rows hold the box
+// form the pass consumes (trail_row), so that the pass has no type test and no select. The rule's eps is one
+// number for the launch (KParams::trail_eps_hi, from the escape boxes and the eye); a launch without the
+// escape bound has none and takes no trailing step.
 #ifndef RMR_TRAIL_STEPS
 #define RMR_TRAIL_STEPS 0
 #endif
@@ -2608,6 +2611,31 @@ RMR_D float trail_dist(const float4* q, V3 p, float& mid, float& len2, bool& box
     const V3 qq = vabs(p - v3(a.x, a.y, a.z)) - h;
     len2 = trail_len2(qq.x, qq.y, qq.z);
     return (trail_k(qq.x, qq.y, qq.z) + sqrt_cr_big(len2)) - rad;
+}
+// the same from a row of the LDS table, which holds the box form already (rmr_trail_rule.h trail_row:
+// c.xyz h.x | h.yz rad mid): no type test, no select
+RMR_D float trail_dist_row(const float4* q, V3 p, float& mid, float& len2) {
+    const float4 a = q[0], b = q[1];
+    mid = b.w;
+    const V3 qq = vabs(p - v3(a.x, a.y, a.z)) - v3(a.w, b.x, b.y);
+    len2 = trail_len2(qq.x, qq.y, qq.z);
+    return (trail_k(qq.x, qq.y, qq.z) + sqrt_cr_big(len2)) - b.z;
+}
+// march_update<HO, false, true, true> of a lane whose trailing step the rule accepted: the lane marches from
+// outside (dist = F), and its t is not NaN (a NaN t gives a NaN delta, which the rule refuses), so t >= maxDist
+// and !(t < maxDist) are one test and the far hit's miss is `past` itself. The same selects from the same
+// values otherwise.
+RMR_D void trail_update(const KParams& P, Lane& L, float F, float mid, int w, bool cert) {
+    const bool hit0 = F < 0.001f;
+    const bool past = !(L.t < P.max_dist);
+    const float tn = fmaf(F, P.step_mult, L.t);
+    const int cn = L.ctr + 1;
+    const bool hit = hit0 & !past;
+    const bool miss = past | (!hit0 & ((cn >= P.max_steps) | (tn > L.texit)));
+    L.t = hit0 ? L.t : (miss ? P.max_dist : tn);
+    L.mid = hit ? mid : (miss ? -1.0f : L.mid);
+    L.ctr = hit ? (cert ? -1 - w : 0) : cn;
+    L.phase = hit ? PH_HIT : (miss ? PH_MISS : L.phase);
 }
 // the primary ray's first march step with the chunk's rays (chunk_ray EYEC; lane-slot kernels only)
 #ifndef RMR_EYE_CHUNK
@@ -2762,13 +2790,26 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
 #define RMR_PRIM_DIST(k, p, mid, j) (dp_lds ? prim_dist_tab(s_dp + kTabStep * (k), p, mid, j) : prim_dist(P, k, p, mid, j))
     static_assert(!RMR_NPC_TAB_SOA || MAP::kCache, "an SoA table kernel reads dtab as the LDS copy only");
 #define RMR_DTAB (dp_lds ? (const float4*)s_dp : (const float4*)P.dprims)
-    // trailing steps: the table in LDS, in the global table's layout (the generator asks for it only for
-    // scenes it holds, rmr_jit.cpp; a larger table would be cut short here, never overrun)
+    // trailing steps: the table in LDS, each row in the box form a pass consumes (rmr_trail_rule.h trail_row;
+    // the generator asks for the table only for scenes it holds, rmr_jit.cpp; a larger table would be cut
+    // short here, never overrun)
     __shared__ float4 s_tp[TRAIL_LDS ? 2 * kTrailLdsPrims : 1];
     if constexpr (TRAIL_LDS) {
-        for (int i = (int)threadIdx.x; i < 2 * P.n_prims && i < 2 * kTrailLdsPrims; i += (int)blockDim.x)
-            s_tp[i] = ((const float4*)P.dprims)[i];
+        for (int i = (int)threadIdx.x; i < P.n_prims && i < kTrailLdsPrims; i += (int)blockDim.x) {
+            // c.xyz r.x | r.yz type|index<<8 mat_id
+            const float4 a = ((const float4*)P.dprims)[2 * i], b = ((const float4*)P.dprims)[2 * i + 1];
+            float row[8];
+            trail_row((__float_as_int(b.z) & 0xff) == RMR_PRIM_BOX, a.x, a.y, a.z, a.w, b.x, b.y, b.w, row);
+            s_tp[2 * i] = make_float4(row[0], row[1], row[2], row[3]);
+            s_tp[2 * i + 1] = make_float4(row[4], row[5], row[6], row[7]);
+        }
         __syncthreads();
+    }
+    // the rule's two launch constants (rmr_trail_rule.h), wave-uniform: SGPRs
+    float tr_ak = 0.0f, tr_ck = 0.0f;
+    if constexpr (TRAIL) {
+        tr_ak = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(trail_anchor_const(P.trail_eps_hi))));
+        tr_ck = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(trail_cert_const(P.trail_eps_hi))));
     }
     const int wv = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) & 3);   // the wave's index in its block (an SGPR)
     uint32_t chunk_base = 0;
@@ -3089,6 +3130,9 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
             // the loop's own counts (scalar registers; the wave counters were carried in VGPRs here)
             uint32_t lmaps = 0, liters = 0;
             uint32_t ltsteps = 0, ltpasses = 0, ltlanes = 0;   // (trailing steps)
+#ifdef RMR_TRAIL_CHECK
+            uint32_t ltcheck = 0;
+#endif
             // lane slots: PK more finished marches than the lanes that wait in registers for their slot
             const int TL = SLOTS ? __popcll(__ballot(is_shade(L.phase))) + PK : T;
 #ifdef RMR_PROFILE
@@ -3117,7 +3161,7 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                         bool cert;
                         float s2;
                         const V2 m = MAP::eval_t(P, p, w, cert, s2);
-                        tr_anchor = trail_anchor(s2, P.am_r2, npc_eps(P, p));
+                        tr_anchor = trail_anchor_hi(s2, P.am_r2, tr_ak, p.x, p.y, p.z);
                         tr_t0 = L.t;
                         tr_w = w;
                         march_update<HO, false, true, true>(P, L, m, w, cert);
@@ -3147,20 +3191,40 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                     // but PH_MARCH) and every pass so far accepted its step: a refused lane has not
                     // moved, so the rule would refuse it again.
                     bool q = is_active(L.phase) && !L.inside;
-                    for (int k = 0; k < KT; k++, q = q && is_active(L.phase)) {
-                        const uint64_t qm = __ballot(q);
-                        if (!qm) break;
+                    // The same as a wave mask, carried in scalar registers beside the lanes' bool: a ballot of
+                    // the bool a loop carries costs a select and a compare, a ballot of compares is their mask
+                    uint64_t qm = __builtin_amdgcn_ballot_w64(is_active(L.phase) && !L.inside);
+                    // The LDS table's row, its address formed once per iteration from tr_w on every lane,
+                    // taking part or not: tr_w is 0 or the index am_w_of took from the map's minimiser, one
+                    // of the generated primitives' own literals, so below P.n_prims <= kTrailLdsPrims.
+                    // (The global table is read by the lanes that take part alone: index 0 otherwise.)
+                    const float4* const row = (const float4*)s_tp + (TRAIL_LDS ? 2 * tr_w : 0);
+                    for (int k = 0; k < KT && qm; k++) {
                         const V3 p = vfma(L.d, L.t, L.o);
-                        float mid, len2;
-                        bool box;
-                        const float F = trail_dist((TRAIL_LDS ? (const float4*)s_tp : (const float4*)P.dprims) + 2 * (q ? tr_w : 0),
-                                                   p, mid, len2, box);
-                        const TrailStep ts = trail_rule(tr_anchor, tr_t0, L.t, trail_linf(p.x, p.y, p.z), trail_finite(p.x, p.y, p.z),
-                                                        F, len2, P.npc_eps0, P.am_dmax);
+                        float mid, len2, F;
+                        bool box = false;
+                        if constexpr (TRAIL_LDS) {
+                            F = trail_dist_row(row, p, mid, len2);
+#ifdef RMR_COUNT_FLOPS
+                            box = (__float_as_int(((const float4*)P.dprims)[2 * (q ? tr_w : 0) + 1].z) & 0xff) == RMR_PRIM_BOX;
+#endif
+                        } else {
+                            F = trail_dist((const float4*)P.dprims + 2 * (q ? tr_w : 0), p, mid, len2, box);
+                        }
+                        // trail_rule_hi, with the wave's mask of accepting lanes from the five tests' own masks
+                        const TrailTests tc = trail_tests_hi(tr_anchor, tr_t0, L.t, F, len2, tr_ck, P.am_dmax);
+                        TrailStep ts;
+                        ts.accept = trail_accept(tc);
+                        ts.cert = ts.accept & tc.probes;
                         const bool ok = q && ts.accept;
-                        const uint64_t um = __ballot(ok);
+                        const uint64_t um = qm & (__builtin_amdgcn_ballot_w64(tc.zero) | __builtin_amdgcn_ballot_w64(tc.big)) &
+                                            __builtin_amdgcn_ballot_w64(tc.below) & __builtin_amdgcn_ballot_w64(tc.nearer);
                         ltpasses++;
                         ltlanes += (uint32_t)__popcll(qm);
+#ifdef RMR_TRAIL_CHECK   // diagnostics (RMR_JIT_OPTS=-DRMR_TRAIL_CHECK): evaluated lanes whose eps(p) exceeds the launch's bound
+                        ltcheck += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(
+                            q && trail_eps(trail_linf(p.x, p.y, p.z) + 0.002f, P.npc_eps0) > P.trail_eps_hi));
+#endif
                         if (!um) break;
 #ifdef RMR_COUNT_FLOPS   // one primitive and its opU, as the cache path counts them, per type
                         {
@@ -3171,8 +3235,10 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
 #endif
                         // the step march() takes with map(p) = (F, id_w); a hit parks certified by the
                         // rule's own certificate or uncertified for the batch probes (the same bits)
-                        if (ok) march_update<HO, false, true, true>(P, L, v2(F, mid), tr_w, ts.cert);
-                        q = ok;
+                        if (ok) trail_update(P, L, F, mid, tr_w, ts.cert);
+                        // a refused lane has not moved: it sits the later passes out
+                        q = ok && is_active(L.phase);
+                        qm = um & __builtin_amdgcn_ballot_w64(is_active(L.phase));
                         lmaps += (uint32_t)__popcll(um);
                         ltsteps += (uint32_t)__popcll(um);
                     }
@@ -3190,6 +3256,9 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                 tsteps += (WCount)__builtin_amdgcn_readfirstlane(ltsteps);
                 tpasses += (WCount)__builtin_amdgcn_readfirstlane(ltpasses);
                 tlanes += (WCount)__builtin_amdgcn_readfirstlane(ltlanes);
+#ifdef RMR_TRAIL_CHECK
+                if (ltcheck && lane_now() == 0) atomicAdd(P.counters + kCntTrailCheck, (unsigned long long)ltcheck);
+#endif
             }
         }
         RMR_STAMP(c2);
