@@ -1085,6 +1085,115 @@ int rmr_read_mesh_bake(rmr_ctx* ctx, float* rgba, float* ao);
 /* Their device pointers (NULL: no mesh, not baked, or empty). No synchronisation. */
 void* rmr_mesh_bake_device_ptr(rmr_ctx* ctx, int which);
 
+/* ---- irradiance probes: SH light baking on a lattice and its lookup ----------------------------- */
+/* No counterpart in the reference. Additive: no other entry point changes. DESIGN.md §4.18.
+ *
+ * The companion of the vertex bake for what moves through a scene: radiance over the whole sphere is sampled
+ * at probe points and projected onto nine spherical-harmonic functions per colour channel; irradiance / pi for
+ * any position and normal is then looked up by trilinear interpolation over a lattice of probes. There are no
+ * visibility or back-face weights: light leaks through walls thinner than a cell.
+ *
+ * The rule (csrc/rmr_probe_rule.h holds the parts the host and the kernels share). All arithmetic is float32,
+ * each operation rounded on its own (no fma); `/` is the correctly rounded division; every select is a
+ * comparison.
+ *
+ * Probes: a probe is a point p. The list form takes n points (float32 [n][3]) and first_index; its invocation
+ *   is the bake's: idx = first_index + i (idx < 2^36), gx = idx & 4095, gy = idx >> 12. The field form takes an
+ *   lattice descriptor that rmr_check_volume accepts; probe j is lattice point j by that header's position rule and linear
+ *   index, and first_index is 0.
+ * Reject: a probe is rejected iff a coordinate of p is not finite or, in the device forms, |p coordinate| >
+ *   origin_extent. Rejects are counted once per call into the counter rmr_query_rejects reads.
+ * Buried: a probe is buried iff !(map(p).x >= clearance), map as rmr_eval_map states it (the table-driven map
+ *   class, so every kernel class gives the same bits); a NaN distance buries the probe. Buried probes are not
+ *   counted. Rejected and buried probes trace nothing; all 28 of their outputs are 0.
+ * Sample k of a used probe: a fresh chain (rc = 0) with the seeds gxt = gx + times[k], gyt = gy + times[k],
+ *   started with main()'s first jitter call rand(gxt, gyt) (the value is not used; rmr_bake_points has the
+ *   reason); then d = randHemisphere((p.x, p.y), (p.z, p.x), (0, 0, 0)): the zero-normal branch, a uniform
+ *   direction on the sphere (the reference's volume-scatter path). The ray is (o = p, d); the trace's own
+ *   chain is fresh again (rc = 0, the same seeds). L_k = trace(o, d).rgb as rmr_trace_rays_device gives it. A
+ *   sample with a non-finite component of L_k is skipped.
+ * Basis of a unit vector (x, y, z):
+ *   Y0 = 0.282095f              Y1 = 0.488603f * y          Y2 = 0.488603f * z          Y3 = 0.488603f * x
+ *   Y4 = 1.092548f * (x * y)    Y5 = 1.092548f * (y * z)    Y6 = 0.315392f * ((3.0f * (z * z)) - 1.0f)
+ *   Y7 = 1.092548f * (x * z)    Y8 = 0.546274f * ((x * x) - (y * y))
+ * Fold: over the used samples in ascending k, for m = 0..8 and channel c: S[m][c] = S[m][c] + (L_k[c] *
+ *   Y_m(d_k)), the product rounded, then the sum. n_used counts the used samples (float32, exact up to 2^24).
+ *   sh[m][c] = (S[m][c] * 12.566371f) / n_used; n_used == 0: everything 0. A probe's output is 28 floats:
+ *   sh[9][3], then n_used. A probe is valid iff n_used > 0. Each coefficient meets its samples in ascending k,
+ *   so the result does not depend on how the work is cut into launches or mapped to threads.
+ * Lookup: a lattice desc, its field sh[n][28], a point q and a unit normal nrm; a query is rejected as
+ *   rmr_bake_check_points rejects a point (result (0, 0, 0, 0), counted). Per axis a: f_a = (q_a - origin_a) /
+ *   spacing; c_a = floor(f_a) clamped to [0, n_a - 2] (as a float, then converted); w_a = f_a - (float)c_a
+ *   clamped to [0, 1]: a point outside the box takes the boundary's value. The cell's eight corners in the
+ *   order dx + 2 dy + 4 dz: u_a = d_a ? w_a : 1 - w_a; g = (u_x * u_y) * u_z, or 0 if that probe is not valid;
+ *   W = the sum of g in corner order; B[m][c] = the sum of g * sh[m][c] in corner order (each product rounded,
+ *   then each sum). With Y_m = Y_m(nrm), per channel: t0 = B0 * Y0; t1 = (((B1 * Y1) + (B2 * Y2)) + (B3 * Y3))
+ *   * 0.6666667f; t2 = (((((B4 * Y4) + (B5 * Y5)) + (B6 * Y6)) + (B7 * Y7)) + (B8 * Y8)) * 0.25f; e = (t0 +
+ *   t1) + t2; v = e / W; out.rgb = W > 0 ? (v > 0 ? v : 0) : 0 and out.a = W. (1, 2/3 and 1/4 are the
+ *   clamped-cosine lobe's band factors over pi: the output has rmr_bake_points' unit, irradiance / pi; under a
+ *   constant radiance L it is L.) */
+typedef struct rmr_probe_params {   /* 16 bytes */
+    float clearance;        /* finite, >= 0;                                   default 0 */
+    float origin_extent;    /* the device list forms: a bound on |p coordinate| (finite, >= 0; a probe beyond
+                             * it is rejected); the host and field forms compute it;  default 0 */
+    uint64_t first_index;   /* first_index + n <= 2^36; the field form: 0;      default 0 */
+} rmr_probe_params;
+void rmr_default_probe_params(rmr_probe_params* p);
+/* RMR_OK, or RMR_E_INVALID for a field outside the ranges above (origin_extent is not looked at) and NULL. */
+int rmr_check_probe_params(const rmr_probe_params* p);
+/* out[i][0 .. 9) = Y_0 .. Y_8 of dirs[i] (float32 [n][3]; not normalised, not checked). No context, no GPU. */
+int rmr_sh_basis(const float* dirs, size_t n, float* out);
+/* The fold and resolve on host arrays laid out [k][i] (L_rgb and dirs [nspp][n][3]): out [n][28]. No reject or
+ * buried rule: every probe is used. RMR_E_INVALID for nspp == 0, nspp > 2^24 or a missing array. No context,
+ * no GPU. */
+int rmr_probe_fold(const float* L_rgb, const float* dirs, size_t n, uint32_t nspp, float* out);
+/* The lookup on the host: out_rgba [n][4] over the field sh [points of desc][28]. Every query's result is
+ * written; RMR_OK iff no query is rejected, otherwise RMR_E_INVALID and *first_bad (when not NULL) is the first
+ * rejected index (RMR_OK: n). RMR_E_INVALID, nothing written, for a descriptor rmr_check_volume rejects or a
+ * missing array. No context, no GPU. */
+int rmr_probe_irradiance_host(const rmr_volume_desc* desc, const float* sh, const float* points, const float* normals,
+                              size_t n, float* out_rgba, size_t* first_bad);
+/* The generated rays as d_out[k][i] (device memory, n nspp rays), for rmr_trace_rays_device or a caller's own
+ * use. A rejected or buried probe's rays: gx = -1, the sample's time, everything else 0 (rmr_bake_rays_device's
+ * convention). origin_extent is not used (no bound). Needs a scene (the buried test): RMR_E_STATE without one.
+ * Queued on the context's stream without synchronising. */
+int rmr_probe_rays_device(rmr_ctx* ctx, const float* d_points, size_t n, const float* times, uint32_t nspp,
+                          const rmr_probe_params* params, rmr_ray* d_out);
+/* The bake of a host list: out_sh [n][28]. params NULL = the defaults; origin_extent is taken from the list.
+ * Runs on the context's stream and synchronises. State rules, error codes, limits and the cut into launches
+ * are rmr_bake_points': RMR_E_STATE without a scene and with params.separate_channels; RMR_E_INVALID for params
+ * rmr_check_probe_params refuses, nspp == 0, nspp > 2^24, first_index + n > 2^36 and ceil(n / 64) nspp >= 2^32.
+ * The accumulator, the half image, the estimate, the guides, every stage image, the sampled AOVs, the mesh and
+ * its bake are left as they are (by every function of this section). */
+int rmr_bake_probes(rmr_ctx* ctx, const float* points, size_t n, const float* times, uint32_t nspp,
+                    const rmr_probe_params* params, float* out_sh);
+/* The same with device pointers (times stays a host array), queued on the context's stream without
+ * synchronising; params->origin_extent is required (RMR_E_INVALID unless finite and >= 0). The per-probe state
+ * between launches (144 bytes per probe: a float4 per coefficient) is the library's. */
+int rmr_bake_probes_device(rmr_ctx* ctx, const float* d_points, size_t n, const float* times, uint32_t nspp,
+                           const rmr_probe_params* params, float* d_out_sh);
+/* The field, owned by the context: one lattice and its [points][28] floats in device memory. It is freed by
+ * rmr_probe_field_free, rmr_reload and rmr_destroy; before a field exists the readers and the lookup return
+ * RMR_E_STATE (rmr_probe_field_device_ptr: NULL).
+ * rmr_bake_probe_field bakes the lattice's points (as rmr_bake_probes_device over them with first_index 0; the
+ * extent is the lattice box's largest |coordinate| times 1 + 2^-20, rounded up; params->first_index must be 0)
+ * and replaces the field; no synchronisation. RMR_E_INVALID, naming the field, for a descriptor
+ * rmr_check_volume rejects. */
+int rmr_bake_probe_field(rmr_ctx* ctx, const rmr_volume_desc* desc, const float* times, uint32_t nspp,
+                         const rmr_probe_params* params);
+/* Loads a saved or synthetic field (sh: host memory, [points of desc][28]); replaces the field; synchronises.
+ * Needs no scene. */
+int rmr_write_probe_field(rmr_ctx* ctx, const rmr_volume_desc* desc, const float* sh);
+/* The field's lattice and / or floats to host memory (either may be NULL); synchronises. */
+int rmr_read_probe_field(rmr_ctx* ctx, rmr_volume_desc* desc_out, float* sh);
+void* rmr_probe_field_device_ptr(rmr_ctx* ctx);
+int rmr_probe_field_free(rmr_ctx* ctx);
+/* The lookup over the context's field: out_rgba [n][4] for n points and unit normals (float32 [n][3] each). The
+ * host form copies, runs on the context's stream and synchronises; the device form is queued without
+ * synchronising. Rejected queries are counted (rmr_query_rejects). Needs no scene. */
+int rmr_probe_irradiance(rmr_ctx* ctx, const float* points, const float* normals, size_t n, float* out_rgba);
+int rmr_probe_irradiance_device(rmr_ctx* ctx, const float* d_points, const float* d_normals, size_t n, float* d_out_rgba);
+
 /* ---- display ---------------------------------------------------------------------------- */
 /* Graphics::Display(centre, zoom, min, max) (Graphics.cpp:356-390 with createFQ 227-258 and
  * FullQuad.vs / FullQuad.fs), headless: draws the accumulator into a screen_w x screen_h RGBA8 image

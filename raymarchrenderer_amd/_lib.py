@@ -51,6 +51,10 @@ EXPORTS = [
     "rmr_default_bake_params", "rmr_check_bake_params", "rmr_bake_check_points", "rmr_bake_fold", "rmr_srgb8_pixels",
     "rmr_encode_ply_colors", "rmr_bake_points", "rmr_bake_points_device", "rmr_bake_rays_device", "rmr_bake_mesh",
     "rmr_read_mesh_bake", "rmr_mesh_bake_device_ptr",
+    "rmr_default_probe_params", "rmr_check_probe_params", "rmr_sh_basis", "rmr_probe_fold", "rmr_probe_irradiance_host",
+    "rmr_probe_rays_device", "rmr_bake_probes", "rmr_bake_probes_device", "rmr_bake_probe_field", "rmr_write_probe_field",
+    "rmr_read_probe_field", "rmr_probe_field_device_ptr", "rmr_probe_field_free", "rmr_probe_irradiance",
+    "rmr_probe_irradiance_device",
 ]
 
 
@@ -254,6 +258,23 @@ def lib(diag=None):
         "rmr_bake_mesh": (C.c_int, [vp, fp, C.c_uint32, C.POINTER(abi.BakeParams)]),
         "rmr_read_mesh_bake": (C.c_int, [vp, fp, fp]),
         "rmr_mesh_bake_device_ptr": (vp, [vp, C.c_int]),
+        "rmr_default_probe_params": (None, [C.POINTER(abi.ProbeParams)]),
+        "rmr_check_probe_params": (C.c_int, [C.POINTER(abi.ProbeParams)]),
+        "rmr_sh_basis": (C.c_int, [fp, C.c_size_t, fp]),
+        "rmr_probe_fold": (C.c_int, [fp, fp, C.c_size_t, C.c_uint32, fp]),
+        "rmr_probe_irradiance_host": (C.c_int, [C.POINTER(abi.VolumeDesc), fp, fp, fp, C.c_size_t, fp, C.POINTER(C.c_size_t)]),
+        "rmr_probe_rays_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, fp, C.c_uint32, C.POINTER(abi.ProbeParams), C.c_void_p]),
+        "rmr_bake_probes": (C.c_int, [vp, fp, C.c_size_t, fp, C.c_uint32, C.POINTER(abi.ProbeParams), fp]),
+        "rmr_bake_probes_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, fp, C.c_uint32, C.POINTER(abi.ProbeParams),
+                                             C.c_void_p]),
+        "rmr_bake_probe_field": (C.c_int, [vp, C.POINTER(abi.VolumeDesc), fp, C.c_uint32, C.POINTER(abi.ProbeParams)]),
+        "rmr_write_probe_field": (C.c_int, [vp, C.POINTER(abi.VolumeDesc), fp]),
+        "rmr_read_probe_field": (C.c_int, [vp, C.POINTER(abi.VolumeDesc), fp]),
+        "rmr_probe_field_device_ptr": (vp, [vp]),
+        "rmr_probe_field_free": (C.c_int, [vp]),
+        "rmr_probe_irradiance": (C.c_int, [vp, fp, fp, C.c_size_t, fp]),
+        "rmr_probe_irradiance_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+        "rmr_diag_probe_fold": (C.c_int, [vp, C.c_int]),
         "rmr_diag_bake_kernels": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, fp, C.c_uint32,
                                             C.POINTER(abi.BakeParams), C.c_void_p]),
         "rmr_diag_bloom_tail": (C.c_int, [vp, C.c_int]),

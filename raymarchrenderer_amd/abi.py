@@ -343,6 +343,19 @@ def bake_params(radiance=True, ao=False, bias=0.002, ao_distance=float("inf"), f
                       float(origin_extent), int(first_index))
 
 
+# irradiance probes (rmr.h rmr_bake_probes)
+PROBE_FLOATS = 28
+
+
+class ProbeParams(C.Structure):
+    _fields_ = [("clearance", C.c_float), ("origin_extent", C.c_float), ("first_index", C.c_uint64)]
+
+
+def probe_params(clearance=0.0, first_index=0, origin_extent=0.0):
+    """rmr_probe_params (the defaults are rmr_default_probe_params')."""
+    return ProbeParams(float(clearance), float(origin_extent), int(first_index))
+
+
 # variance planes of the variance-guided denoiser (rmr.h)
 VARIANCE_SEED = 0
 VARIANCE_FILTERED = 1

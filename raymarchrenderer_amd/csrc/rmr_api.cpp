@@ -29,6 +29,7 @@
 #include "rmr_camera.hpp"
 #include "rmr_ray_check.h"
 #include "rmr_bake_rule.h"
+#include "rmr_probe_rule.h"
 #include "rmr_jit.hpp"
 #include "rmr_trail_rule.h"
 #include "scene.hpp"
@@ -80,6 +81,14 @@ hipError_t launch_bake_ao(const KParams& P, int np, const BakeList& B, float ao_
                           float2* plane, unsigned long long* rejects, int grid_cap, hipStream_t s);
 hipError_t launch_bake_fold(bool ao, const void* plane, const float4* rec, float4* state, uint64_t n, uint32_t nspp,
                             uint64_t s0, uint32_t cnt, float* out, hipStream_t s);
+hipError_t launch_probe_rays(const KParams& P, int np, const ProbeList& B, uint64_t s0, uint32_t cnt, float4* rec,
+                             unsigned long long* rejects, hipStream_t s);
+hipError_t launch_probe_ray_list(const KParams& P, int np, const ProbeList& B, rmr_ray* out, unsigned long long* rejects,
+                                 hipStream_t s);
+hipError_t launch_probe_fold(int mapping, const float4* samp, const float4* rec, float4* state, uint64_t n, uint32_t nspp,
+                             uint64_t s0, uint32_t cnt, float* out, hipStream_t s);
+hipError_t launch_probe_lookup(const rmr_volume_desc& d, const float* sh, const float* points, const float* normals,
+                               uint64_t n, float* out, unsigned long long* rejects, hipStream_t s);
 }  // namespace rmr
 
 using rmr::CompiledScene;
@@ -186,6 +195,15 @@ struct rmr_ctx {
     float* d_mesh_ao = nullptr;
     rmr_volume_desc mesh_desc{};
     int mesh_baked = 0;                   // RMR_BAKE_*: what rmr_bake_mesh has (queued) for the current mesh
+    // irradiance probes (rmr_bake_probes, rmr_probe.hip): the per-probe state between launches
+    // (a float4 per coefficient, grows only) and the field: one lattice and its [points][28] floats. Both are
+    // freed by rmr_probe_field_free, rmr_reload and rmr_destroy
+    void* d_probe_state = nullptr;
+    size_t probe_state_cap = 0;           // bytes
+    float* d_probe_field = nullptr;
+    rmr_volume_desc probe_desc{};
+    bool probe_valid = false;
+    int probe_fold_mapping = 0;           // rmr_probe.hip launch_probe_fold (the diagnostic library's switch)
     // which of the output stages' images below are valid: the one place that says so (stage_state.hpp)
     rmr::StageState st;
     // first-hit guides and the preview denoiser (rmr_render_guides / rmr_denoise): three guide planes and
@@ -499,6 +517,13 @@ void free_mesh(rmr_ctx* c) {
     drop_mesh(c);
     free_all({&c->d_mesh_dist, &c->d_mesh_flag, &c->d_mesh_cell, &c->d_mesh_scan, &c->d_bake_state});
     c->mesh_dist_cap = c->mesh_flag_cap = c->mesh_cell_cap = c->mesh_scan_cap = c->bake_state_cap = 0;
+}
+
+// Release the probe field and the probe bakes' state (the caller has synced the context's stream).
+void free_probes(rmr_ctx* c) {
+    free_all({&c->d_probe_field, &c->d_probe_state});
+    c->probe_state_cap = 0;
+    c->probe_valid = false;
 }
 
 // Release the half image and the tile-error map (the caller has synced the context's stream).
@@ -1058,7 +1083,9 @@ int submit_launch(rmr_ctx* c, const KParams& P, rmr_ctx::Slot* S, bool use_jit, 
 // bake set (rmr_bake_points_device): the list is a bake's tile-samples instead (rmr_bake.hip: tile t of 64
 // points, sample k, at index t nspp + k; the plan's "samples" are these), n counts them, k_bake_rays writes
 // the records and k_bake_fold reads the planes: d_out is the points' [n][4] result.
-struct BakeJob { rmr::BakeList list; const float* h_times; float4* state; };
+// probe set (rmr_bake_probes_device): the units are probes' tile-samples, k_probe_rays and k_probe_fold take the
+// two kernels' places (rmr_probe.hip), list states n and nspp, and d_out is the probes' [n][28] result.
+struct BakeJob { rmr::BakeList list; const float* h_times; float4* state; rmr::ProbeList* probe = nullptr; };
 struct RayList { const rmr_ray* rays; size_t n; float* out; const rmr_ray* d_rays; float* d_out; float extent;
                  BakeJob* bake = nullptr; };
 
@@ -1141,6 +1168,7 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
                                                  rays ? sizeof(float4) + rmr::kRayRecordBytes : sizeof(float4));
     const size_t chunk = sp.per_launch;
     if (rl && rl->bake && (r = stage_times(c, rl->bake->h_times, rl->bake->list.nspp, &rl->bake->list.times))) return r;
+    if (rl && rl->bake && rl->bake->probe) rl->bake->probe->times = rl->bake->list.times;
     if (sp.slotted && c->slots.size() != (size_t)c->launch_streams) {
         if ((r = free_slots(c)) || (r = make_slots(c))) return r;
     }
@@ -1192,7 +1220,10 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
         P.time1 = rl ? 0.0f : times[k0];   // the seed when this launch has one sample (unit_pixel)
         P.n_units = (uint64_t)n * plane;
         std::vector<float4> h_rays;   // (a list's records; the launch is synchronised below)
-        if (rl && rl->bake) {
+        if (rl && rl->bake && rl->bake->probe) {
+            HIPCHK(c, rmr::launch_probe_rays(P, c->accel.map_np, *rl->bake->probe, k0, n, c->d_rays, c->d_query + kQueryRejects,
+                                             c->stream));
+        } else if (rl && rl->bake) {
             HIPCHK(c, rmr::launch_bake_rays(rl->bake->list, k0, n, c->d_rays, c->d_query + kQueryRejects, c->stream));
         } else if (rl && rl->d_rays) {
             HIPCHK(c, rmr::launch_pack_rays(rl->d_rays, rl->n, (uint64_t)k0 * 64, (uint32_t)P.n_units, rl->extent, c->d_rays,
@@ -1232,7 +1263,10 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
             P.refill_threshold = refill_for(c->refill_threshold, park);
         }
         if ((r = submit_launch(c, P, S, use_jit, gp.grid, rays ? c->d_rays : nullptr, !rl))) return r;
-        if (rl && rl->bake) {
+        if (rl && rl->bake && rl->bake->probe) {
+            HIPCHK(c, rmr::launch_probe_fold(c->probe_fold_mapping, P.samp, c->d_rays, rl->bake->state, rl->bake->list.n,
+                                             rl->bake->list.nspp, k0, n, rl->d_out, c->stream));
+        } else if (rl && rl->bake) {
             HIPCHK(c, rmr::launch_bake_fold(false, P.samp, c->d_rays, rl->bake->state, rl->bake->list.n, rl->bake->list.nspp,
                                             k0, n, rl->d_out, c->stream));
         } else if (rl && rl->d_rays) {
@@ -1435,6 +1469,7 @@ void rmr_destroy(rmr_ctx* c) {
     free_bloom(c);
     free_aov(c);
     free_mesh(c);
+    free_probes(c);
     free_estimate(c);
     if (c->d_accum && !c->accum_external) (void)hipFree(c->d_accum);
     for (auto& k : c->jit_loaded)
@@ -1573,6 +1608,7 @@ int rmr_reload(rmr_ctx* c) {
     free_bloom(c);
     free_aov(c);
     free_mesh(c);
+    free_probes(c);
     c->W = c->pend_W;
     c->H = c->pend_H;
     if (resize) {
@@ -2744,6 +2780,237 @@ void* rmr_mesh_bake_device_ptr(rmr_ctx* c, int which) {
     return nullptr;
 }
 
+// ---- irradiance probes (rmr_probe.hip, rmr_probe_rule.h) ----------------------------------
+namespace {
+// The call's params (NULL: the defaults) and counts, checked as bake_args checks a bake's.
+int probe_args(rmr_ctx* c, const char* who, size_t n, const float* times, uint32_t nspp, const rmr_probe_params* params,
+               rmr_probe_params& q) {
+    if (params) q = *params;
+    else rmr_default_probe_params(&q);
+    if (rmr_check_probe_params(&q) != RMR_OK)
+        return fail(c, RMR_E_INVALID, std::string(who) + ": params fail rmr_check_probe_params (clearance, first_index)");
+    if (nspp == 0 || nspp > (1u << 24) || !times) return fail(c, RMR_E_INVALID, std::string(who) + ": 1 <= nspp <= 2^24 seeds");
+    if ((uint64_t)n > rmr::kBakeMaxIndex - q.first_index)
+        return fail(c, RMR_E_INVALID, std::string(who) + ": first_index + n exceeds 2^36");
+    if ((((uint64_t)n + 63) / 64) * (uint64_t)nspp >= ((uint64_t)1 << 32))
+        return fail(c, RMR_E_INVALID, std::string(who) + ": ceil(n / 64) nspp must stay below 2^32 (bake slices, first_index)");
+    return RMR_OK;
+}
+
+rmr::ProbeList probe_list(const float* d_points, const rmr_volume_desc* desc, size_t n, uint32_t nspp, const rmr_probe_params& q,
+                          float extent) {
+    rmr::ProbeList B{};
+    B.points = d_points;
+    if (desc) {
+        for (int a = 0; a < 3; a++) B.origin[a] = desc->origin[a];
+        B.spacing = desc->spacing;
+        B.nx = desc->n[0];
+        B.ny = desc->n[1];
+    }
+    B.n = (uint64_t)n;
+    B.first_index = q.first_index;
+    B.nspp = nspp;
+    B.clearance = q.clearance;
+    B.extent = extent;
+    return B;
+}
+
+// The bake of a device list (d_points) or of a lattice's points (desc), queued: render_tiles' plan and launches,
+// as the light bake's radiance pass.
+int probe_bake_device(rmr_ctx* c, const char* who, const float* d_points, const rmr_volume_desc* desc, size_t n,
+                      const float* times, uint32_t nspp, const rmr_probe_params& q, float* d_out) {
+    int r;
+    if ((r = launch_precheck(c))) return r;
+    if (c->params.separate_channels != 0)
+        return fail(c, RMR_E_STATE, std::string(who) + " with separate_channels set: a probe's ray has no channel passes");
+    if (!rmr::extent_ok(q.origin_extent))
+        return fail(c, RMR_E_INVALID, std::string(who) + ": origin_extent must be finite and >= 0");
+    if (n == 0) return RMR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((r = ensure_query(c))) return r;
+    if ((r = ensure_qbuf(c, &c->d_probe_state, &c->probe_state_cap, n * rmr::kProbeSH * sizeof(float4)))) return r;
+    rmr::ProbeList B = probe_list(d_points, desc, n, nspp, q, q.origin_extent);
+    BakeJob job{{nullptr, nullptr, (uint64_t)n, q.first_index, nullptr, nspp, 0.0f, q.origin_extent}, times,
+                (float4*)c->d_probe_state, &B};
+    const size_t n_ts = ((n + 63) / 64) * (size_t)nspp;
+    const RayList rl{nullptr, n_ts, nullptr, nullptr, d_out, q.origin_extent, &job};
+    return render_tiles(c, std::vector<TileXY>(), 0, 0, 0, 0, nullptr, 0, 0, &rl);
+}
+
+// the bound on |coordinate| over a lattice's points: the box's largest, times 1 + 2^-20, rounded up
+float lattice_extent(const rmr_volume_desc& d) {
+    double ext = 0.0;
+    for (int a = 0; a < 3; a++) {
+        const double lo = (double)d.origin[a];
+        const double hi = lo + (double)(d.n[a] - 1) * (double)d.spacing;
+        ext = std::max(ext, std::max(std::fabs(lo), std::fabs(hi)));
+    }
+    return std::nextafter((float)(ext * (1.0 + 0x1p-20)), INFINITY);
+}
+
+// A new field for the lattice (the last one is gone, whatever happens from here on).
+int probe_field_alloc(rmr_ctx* c, const char* who, const rmr_volume_desc* desc) {
+    const char* bad = nullptr;
+    if (rmr_check_volume(desc, &bad) != RMR_OK)
+        return fail(c, RMR_E_INVALID, std::string(who) + ": bad volume descriptor field '" + bad + "'");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->probe_valid = false;
+    if (c->d_probe_field) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        free_all({&c->d_probe_field});
+    }
+    return alloc_all(c, {{&c->d_probe_field, volume_points(desc) * rmr::kProbeFloats * sizeof(float)}},
+                     "cannot allocate the probe field");
+}
+}  // namespace
+
+int rmr_bake_probes_device(rmr_ctx* c, const float* d_points, size_t n, const float* times, uint32_t nspp,
+                           const rmr_probe_params* params, float* d_out_sh) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_probe_params q;
+    int r;
+    if ((r = probe_args(c, "rmr_bake_probes_device", n, times, nspp, params, q))) return r;
+    if (n && (!d_points || !d_out_sh)) return fail(c, RMR_E_INVALID, "rmr_bake_probes_device: null buffer");
+    return probe_bake_device(c, "rmr_bake_probes_device", d_points, nullptr, n, times, nspp, q, d_out_sh);
+}
+
+int rmr_bake_probes(rmr_ctx* c, const float* points, size_t n, const float* times, uint32_t nspp,
+                    const rmr_probe_params* params, float* out_sh) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_probe_params q;
+    int r;
+    if ((r = probe_args(c, "rmr_bake_probes", n, times, nspp, params, q))) return r;
+    if (n && (!points || !out_sh)) return fail(c, RMR_E_INVALID, "rmr_bake_probes: null buffer");
+    // the probes' bound, over the finite ones
+    float ext = 0.0f;
+    for (size_t i = 0; i < 3 * n; i++)
+        if (std::isfinite(points[i])) ext = std::max(ext, std::fabs(points[i]));
+    q.origin_extent = ext;
+    if ((r = launch_precheck(c))) return r;
+    if (n == 0) return probe_bake_device(c, "rmr_bake_probes", nullptr, nullptr, 0, times, nspp, q, nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((r = ensure_qbuf(c, &c->d_qin, &c->qin_cap, n * 3 * sizeof(float)))) return r;
+    if ((r = ensure_qbuf(c, &c->d_qout, &c->qout_cap, n * rmr::kProbeFloats * sizeof(float)))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_qin, points, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((r = probe_bake_device(c, "rmr_bake_probes", (const float*)c->d_qin, nullptr, n, times, nspp, q, (float*)c->d_qout))) return r;
+    HIPCHK(c, hipMemcpyAsync(out_sh, c->d_qout, n * rmr::kProbeFloats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+int rmr_probe_rays_device(rmr_ctx* c, const float* d_points, size_t n, const float* times, uint32_t nspp,
+                          const rmr_probe_params* params, rmr_ray* d_out) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_probe_params q;
+    int r;
+    if ((r = probe_args(c, "rmr_probe_rays_device", n, times, nspp, params, q))) return r;
+    if (n && (!d_points || !d_out)) return fail(c, RMR_E_INVALID, "rmr_probe_rays_device: null buffer");
+    KParams P;
+    if ((r = query_begin(c, P))) return r;
+    if (n == 0) return RMR_OK;
+    rmr::ProbeList B = probe_list(d_points, nullptr, n, nspp, q, INFINITY);
+    if ((r = stage_times(c, times, nspp, &B.times))) return r;
+    HIPCHK(c, rmr::launch_probe_ray_list(P, c->accel.map_np, B, d_out, c->d_query + kQueryRejects, c->stream));
+    return RMR_OK;
+}
+
+int rmr_bake_probe_field(rmr_ctx* c, const rmr_volume_desc* desc, const float* times, uint32_t nspp,
+                         const rmr_probe_params* params) {
+    if (!c || !desc) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    const char* bad = nullptr;
+    if (rmr_check_volume(desc, &bad) != RMR_OK)
+        return fail(c, RMR_E_INVALID, std::string("rmr_bake_probe_field: bad volume descriptor field '") + bad + "'");
+    rmr_probe_params q;
+    int r;
+    const size_t n = volume_points(desc);
+    if ((r = probe_args(c, "rmr_bake_probe_field", n, times, nspp, params, q))) return r;
+    if (q.first_index != 0) return fail(c, RMR_E_INVALID, "rmr_bake_probe_field: first_index must be 0");
+    q.origin_extent = lattice_extent(*desc);
+    if ((r = launch_precheck(c))) return r;
+    if (c->params.separate_channels != 0)
+        return fail(c, RMR_E_STATE, "rmr_bake_probe_field with separate_channels set: a probe's ray has no channel passes");
+    if (!rmr::extent_ok(q.origin_extent)) return fail(c, RMR_E_INVALID, "rmr_bake_probe_field: the lattice's box is not finite");
+    if ((r = probe_field_alloc(c, "rmr_bake_probe_field", desc))) return r;
+    if ((r = probe_bake_device(c, "rmr_bake_probe_field", nullptr, desc, n, times, nspp, q, c->d_probe_field))) return r;
+    c->probe_desc = *desc;
+    c->probe_valid = true;
+    return RMR_OK;
+}
+
+int rmr_write_probe_field(rmr_ctx* c, const rmr_volume_desc* desc, const float* sh) {
+    if (!c || !desc || !sh) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    int r;
+    if ((r = probe_field_alloc(c, "rmr_write_probe_field", desc))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_probe_field, sh, volume_points(desc) * rmr::kProbeFloats * sizeof(float),
+                             hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->probe_desc = *desc;
+    c->probe_valid = true;
+    return RMR_OK;
+}
+
+int rmr_read_probe_field(rmr_ctx* c, rmr_volume_desc* desc_out, float* sh) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!c->probe_valid) return fail(c, RMR_E_STATE, "no probe field (call rmr_bake_probe_field / rmr_write_probe_field)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (desc_out) *desc_out = c->probe_desc;
+    if (sh)
+        HIPCHK(c, hipMemcpyAsync(sh, c->d_probe_field, volume_points(&c->probe_desc) * rmr::kProbeFloats * sizeof(float),
+                                 hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+void* rmr_probe_field_device_ptr(rmr_ctx* c) { return c && c->probe_valid ? c->d_probe_field : nullptr; }
+
+int rmr_probe_field_free(rmr_ctx* c) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_probes(c);
+    return RMR_OK;
+}
+
+int rmr_probe_irradiance_device(rmr_ctx* c, const float* d_points, const float* d_normals, size_t n, float* d_out_rgba) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (n && (!d_points || !d_normals || !d_out_rgba)) return fail(c, RMR_E_INVALID, "rmr_probe_irradiance_device: null buffer");
+    if (!c->probe_valid) return fail(c, RMR_E_STATE, "no probe field (call rmr_bake_probe_field / rmr_write_probe_field)");
+    HIPCHK(c, hipSetDevice(c->device));
+    int r;
+    if ((r = ensure_query(c))) return r;
+    HIPCHK(c, rmr::launch_probe_lookup(c->probe_desc, c->d_probe_field, d_points, d_normals, (uint64_t)n, d_out_rgba,
+                                       c->d_query + kQueryRejects, c->stream));
+    return RMR_OK;
+}
+
+int rmr_probe_irradiance(rmr_ctx* c, const float* points, const float* normals, size_t n, float* out_rgba) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (n && (!points || !normals || !out_rgba)) return fail(c, RMR_E_INVALID, "rmr_probe_irradiance: null buffer");
+    if (!c->probe_valid) return fail(c, RMR_E_STATE, "no probe field (call rmr_bake_probe_field / rmr_write_probe_field)");
+    if (n == 0) return RMR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int r;
+    if ((r = ensure_qbuf(c, &c->d_qin, &c->qin_cap, n * 6 * sizeof(float)))) return r;
+    if ((r = ensure_qbuf(c, &c->d_qout, &c->qout_cap, n * 4 * sizeof(float)))) return r;
+    float* d_p = (float*)c->d_qin;
+    float* d_n = d_p + 3 * n;
+    HIPCHK(c, hipMemcpyAsync(d_p, points, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_n, normals, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((r = rmr_probe_irradiance_device(c, d_p, d_n, n, (float*)c->d_qout))) return r;
+    HIPCHK(c, hipMemcpyAsync(out_rgba, c->d_qout, n * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
 // ---- first-hit guides and the preview denoiser (rmr_guides.hip, rmr_denoise.hip) ------------------
 namespace {
 // The five W x H float4 buffers, at first use. The guide planes start as zeros (a read before a
@@ -3610,6 +3877,14 @@ int rmr_diag_bake_kernels(rmr_ctx* c, const float* d_points, const float* d_norm
 int rmr_diag_tonemap_fold(rmr_ctx* c, int on) {
     if (!c) return RMR_E_INVALID;
     c->tm_fold = on != 0;
+    return RMR_OK;
+}
+
+// Diagnostic library only (not in include/rmr.h; tools/probe_time.py): the probe fold's mapping, 0 the build's
+// default, 1 one thread per (probe, basis function), 2 one thread per probe. The results are the same.
+int rmr_diag_probe_fold(rmr_ctx* c, int mapping) {
+    if (!c || mapping < 0 || mapping > 2) return RMR_E_INVALID;
+    c->probe_fold_mapping = mapping;
     return RMR_OK;
 }
 

@@ -74,6 +74,11 @@ struct Options {
     int mesh_bake = 0;              // --mesh-bake N[:AO_DISTANCE]: seeds of the vertex bake (0: none)
     bool mesh_bake_ao = false;
     float mesh_bake_ao_distance = 0.0f;
+    std::string probes;             // --probes FILE: the irradiance probe field (rmr.h rmr_bake_probe_field)
+    bool have_probe_bounds = false, have_probe_opts = false;
+    double probe_bounds[6] = {0, 0, 0, 0, 0, 0};  // --probe-bounds x0,y0,z0,x1,y1,z1
+    int probe_grid = 8;             // --probe-grid N: cells along the longest side
+    int probe_samples = 256;        // --probe-samples K: seeds per probe
     double adaptive = -1.0;         // --adaptive T: the tile-error threshold, < 0 = uniform sampling
     int min_samples = 16, pass_samples = 16;   // --min-samples / --pass-samples (rmr_adaptive_params)
     bool have_camera = false;
@@ -394,21 +399,59 @@ bool write_sampled_aovs(const Options& o) {
 
 // The lattice of --mesh-bounds and --mesh-grid: the spacing is the longest side over N, the longest side has
 // N cells and the other sides are rounded up to whole cells; the origin is the bounds' lower corner.
-rmr_volume_desc mesh_lattice(const Options& o) {
+rmr_volume_desc box_lattice(const double bounds[6], int grid) {
     rmr_volume_desc d;
     double longest = 0.0;
     int which = 0;
     for (int a = 0; a < 3; a++) {
-        const double side = o.mesh_bounds[3 + a] - o.mesh_bounds[a];
+        const double side = bounds[3 + a] - bounds[a];
         if (side > longest) { longest = side; which = a; }
-        d.origin[a] = (float)o.mesh_bounds[a];
+        d.origin[a] = (float)bounds[a];
     }
-    d.spacing = (float)(longest / (double)o.mesh_grid);
+    d.spacing = (float)(longest / (double)grid);
     for (int a = 0; a < 3; a++) {
-        const double cells = std::ceil((o.mesh_bounds[3 + a] - o.mesh_bounds[a]) / (double)d.spacing);
-        d.n[a] = a == which ? o.mesh_grid + 1 : (int)std::fmin(std::fmax(cells, 1.0), 1e6) + 1;
+        const double cells = std::ceil((bounds[3 + a] - bounds[a]) / (double)d.spacing);
+        d.n[a] = a == which ? grid + 1 : (int)std::fmin(std::fmax(cells, 1.0), 1e6) + 1;
     }
     return d;
+}
+rmr_volume_desc mesh_lattice(const Options& o) { return box_lattice(o.mesh_bounds, o.mesh_grid); }
+// --probe-bounds and --probe-grid state their lattice the same way
+rmr_volume_desc probe_lattice(const Options& o) { return box_lattice(o.probe_bounds, o.probe_grid); }
+
+// --probes FILE: rmr_bake_probe_field over that lattice with --probe-samples seeds of the render's schedule,
+// written as the line "RMRPROBES 1 nx ny nz ox oy oz spacing" (floats as %.9g) and the points' 28 little-endian
+// float32 each (raymarchrenderer_amd.load_probes reads it).
+bool write_probes(const Options& o) {
+    rmr_ctx* c = Graphics::context();
+    auto fail = [&](const std::string& what) {
+        std::cerr << "--probes: " << what << ": " << rmr_last_error(c) << std::endl;
+        return false;
+    };
+    const rmr_volume_desc d = probe_lattice(o);
+    std::vector<float> times((size_t)o.probe_samples);
+    for (int s = 0; s < o.probe_samples; s++) times[(size_t)s] = seed_time(o.frame, (unsigned)s);
+    if (rmr_bake_probe_field(c, &d, times.data(), (uint32_t)o.probe_samples, nullptr) != RMR_OK) return fail("rmr_bake_probe_field");
+    std::vector<float> sh((size_t)d.n[0] * (size_t)d.n[1] * (size_t)d.n[2] * 28);
+    if (rmr_read_probe_field(c, nullptr, sh.data()) != RMR_OK) return fail("rmr_read_probe_field");
+    const uint16_t one = 1;
+    unsigned char first;
+    std::memcpy(&first, &one, 1);
+    std::FILE* f = first == 1 ? std::fopen(o.probes.c_str(), "wb") : nullptr;   // (the floats are written as they lie in memory)
+    bool ok = f != nullptr;
+    if (f) {
+        std::fprintf(f, "RMRPROBES 1 %d %d %d %.9g %.9g %.9g %.9g\n", d.n[0], d.n[1], d.n[2], d.origin[0], d.origin[1],
+                     d.origin[2], d.spacing);
+        ok = std::fwrite(sh.data(), sizeof(float), sh.size(), f) == sh.size();
+        ok = (std::fclose(f) == 0) && ok;
+    }
+    if (!ok) {
+        std::cerr << "--probes: cannot write " << o.probes << std::endl;
+        return false;
+    }
+    if (!o.quiet) std::printf("probes: %d x %d x %d at spacing %.6g, %d samples each -> %s\n", d.n[0], d.n[1], d.n[2], d.spacing,
+                              o.probe_samples, o.probes.c_str());
+    return true;
 }
 
 // --mesh FILE: rmr_extract_mesh over that lattice with normals and material ids, written as OBJ (v, vn, f) or
@@ -589,6 +632,13 @@ void usage() {
         "                      into the PLY's uchar red green blue (the display's sRGB encode); with AO_DISTANCE\n"
         "                      (> 0 or inf) the colour is the radiance times the occlusion within it; the rays\n"
         "                      start 0.002 + an eighth of the lattice spacing off the vertex; needs --mesh FILE.ply\n"
+        "  --probes FILE       after the render: a field of irradiance probes (rmr.h rmr_bake_probe_field: nine\n"
+        "                      spherical harmonics per channel at a lattice's points) as 'RMRPROBES 1 nx ny nz ox oy\n"
+        "                      oz spacing' and 28 float32 per point; needs --probe-bounds; not with --gpus /\n"
+        "                      --devices or --interactive\n"
+        "  --probe-bounds x0,y0,z0,x1,y1,z1   the box the lattice spans\n"
+        "  --probe-grid N      cells along the box's longest side (1..4095, default 8), as --mesh-grid\n"
+        "  --probe-samples K   seeds per probe (1..2^24, default 256; seeds of --frame)\n"
         "  --adaptive T        adaptive sampling: render until every block's tile error is <= T, at most\n"
         "                      --samples per pixel, over the whole image; prints passes, mean spp, open tiles\n"
         "                      and max error; with --aov also PREFIX_spp.pfm (R = samples) and PREFIX_error.pfm\n"
@@ -767,6 +817,31 @@ bool parse(int argc, char** argv, Options& o) {
             o.mesh_iso = std::strtof(v, &end);
             if (end == v || *end != '\0' || !std::isfinite(o.mesh_iso)) return false;
             o.have_mesh_opts = true;
+        } else if (a == "--probes") {
+            o.probes = next("--probes");
+            if (o.probes.empty()) return false;
+        } else if (a == "--probe-bounds") {
+            char tail = 0;
+            double* b = o.probe_bounds;
+            if (std::sscanf(next("--probe-bounds"), "%lf,%lf,%lf,%lf,%lf,%lf%c", b, b + 1, b + 2, b + 3, b + 4, b + 5, &tail) != 6)
+                return false;
+            for (int k = 0; k < 3; k++)
+                if (!std::isfinite((float)b[k]) || !std::isfinite((float)b[3 + k]) || !(b[3 + k] > b[k])) return false;
+            o.have_probe_bounds = true;
+        } else if (a == "--probe-grid") {
+            char* end = nullptr;
+            const char* v = next("--probe-grid");
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 1 || n > 4095) return false;
+            o.probe_grid = (int)n;
+            o.have_probe_opts = true;
+        } else if (a == "--probe-samples") {
+            char* end = nullptr;
+            const char* v = next("--probe-samples");
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 1 || n > (1L << 24)) return false;
+            o.probe_samples = (int)n;
+            o.have_probe_opts = true;
         } else if (a == "--mesh-bake") {
             char* end = nullptr;
             const char* v = next("--mesh-bake");
@@ -853,6 +928,18 @@ bool parse(int argc, char** argv, Options& o) {
             return false;
         }
     }
+    if (o.probes.empty() ? (o.have_probe_bounds || o.have_probe_opts) : !o.have_probe_bounds) {
+        std::fprintf(stderr, "--probes FILE needs --probe-bounds x0,y0,z0,x1,y1,z1 (and they need --probes)\n");
+        return false;
+    }
+    if (!o.probes.empty()) {
+        const rmr_volume_desc d = probe_lattice(o);
+        const char* bad = nullptr;
+        if (rmr_check_volume(&d, &bad) != RMR_OK) {
+            std::fprintf(stderr, "--probe-bounds / --probe-grid: the lattice's %s is out of range\n", bad);
+            return false;
+        }
+    }
     if (o.adaptive >= 0 && (o.min_samples < 2 || o.pass_samples < 1 || o.samples < o.min_samples)) {
         std::fprintf(stderr, "--adaptive: --min-samples >= 2, --pass-samples >= 1 and --samples >= --min-samples\n");
         return false;
@@ -910,6 +997,10 @@ int main(int argc, char** argv) {
     }
     if (!o.mesh.empty() && (!o.devices.empty() || o.interactive)) {
         std::fprintf(stderr, "--mesh: not with --gpus / --devices or --interactive\n");
+        return 2;
+    }
+    if (!o.probes.empty() && (!o.devices.empty() || o.interactive)) {
+        std::fprintf(stderr, "--probes: not with --gpus / --devices or --interactive\n");
         return 2;
     }
     Screen::setScreenSize(Vector2(1280, 720));  // Program.cpp:89
@@ -975,6 +1066,7 @@ int main(int argc, char** argv) {
     if (rc == 0 && !o.aov.empty() && !write_aovs(o)) rc = 1;
     if (rc == 0 && !o.sampled_aov.empty() && !write_sampled_aovs(o)) rc = 1;
     if (rc == 0 && !o.mesh.empty() && !write_mesh(o)) rc = 1;
+    if (rc == 0 && !o.probes.empty() && !write_probes(o)) rc = 1;
     Graphics::Shutdown();
     return rc;
 }

@@ -612,6 +612,127 @@ class Renderer:
             out[name] = torch.as_tensor(_DeviceArray(ptr, shape, self), device="cuda:%d" % self._device) if ptr else None
         return out
 
+    # -- irradiance probes: SH light baking on a lattice and its lookup (rmr.h) --
+    @staticmethod
+    def _probe_params(params, fields):
+        if params is not None and fields:
+            raise ValueError("params or its fields as keywords, not both (got params and %s)" % ", ".join(sorted(fields)))
+        q = abi.probe_params(**fields) if params is None else params
+        if not isinstance(q, abi.ProbeParams):
+            raise ValueError("params: an abi.ProbeParams (abi.probe_params(...))")
+        return q
+
+    def bake_probes(self, points, times, params=None, **fields):
+        """rmr_bake_probes: the radiance over the whole sphere at n probe points ((n, 3) float32) from the samples
+        seeded `times`, projected onto nine spherical harmonics per channel: (n, 28) float32, sh[9][3] then the
+        samples used. params: an abi.ProbeParams, or its fields as keywords (abi.probe_params: clearance,
+        first_index). A rejected or buried probe (rmr.h) gives zeros; rejected ones count in query_rejects()."""
+        q = self._probe_params(params, fields)
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        out = np.zeros((len(p), abi.PROBE_FLOATS), np.float32)
+        self._chk(self._L.rmr_bake_probes(self._ctx, _fp(p), len(p), _fp(t) if len(t) else None, len(t), C.byref(q), _fp(out)))
+        return out
+
+    @staticmethod
+    def _device_probes(points):
+        import torch
+        if not (points.is_cuda and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 3
+                and points.is_contiguous()):
+            raise ValueError("points: a contiguous (n, 3) float32 CUDA tensor")
+        return points.shape[0]
+
+    def bake_probes_device(self, points, times, origin_extent, params=None, **fields):
+        """rmr_bake_probes_device: bake_probes on a torch CUDA tensor ((n, 3) float32), the (n, 28) result a torch
+        tensor on the same device; queued on the context's stream (set_stream), no copy to the host and no sync.
+        origin_extent: a bound on |coordinate| of every probe."""
+        import torch
+        q = self._probe_params(params, fields)
+        q = abi.ProbeParams(q.clearance, float(origin_extent), q.first_index)
+        n = self._device_probes(points)
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        out = torch.empty((n, abi.PROBE_FLOATS), dtype=torch.float32, device=points.device)
+        self._chk(self._L.rmr_bake_probes_device(self._ctx, points.data_ptr(), n, _fp(t) if len(t) else None, len(t),
+                                                 C.byref(q), out.data_ptr()))
+        return out
+
+    def probe_rays_device(self, points, times, params=None, **fields):
+        """rmr_probe_rays_device: the rays the probe bake generates, a (len(times) * n, 10) float32 CUDA tensor
+        (views of abi.RAY_DTYPE, ray [k * n + i] = sample k of probe i) for trace_rays_device; a rejected or
+        buried probe's rays carry gx = -1. Queued on the context's stream, no sync."""
+        import torch
+        q = self._probe_params(params, fields)
+        n = self._device_probes(points)
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        out = torch.empty((len(t) * n, 10), dtype=torch.float32, device=points.device)
+        self._chk(self._L.rmr_probe_rays_device(self._ctx, points.data_ptr(), n, _fp(t) if len(t) else None, len(t),
+                                                C.byref(q), out.data_ptr()))
+        return out
+
+    def bake_probe_field(self, origin, spacing=None, shape=None, *, times, params=None, **fields):
+        """rmr_bake_probe_field: bake the probes at the lattice's points (an abi.VolumeDesc or origin, spacing,
+        shape) into the context's field (read_probe_field, probe_field_device, probe_irradiance). Queued on the
+        context's stream, no sync."""
+        q = self._probe_params(params, fields)
+        d = _volume_desc(origin, spacing, shape)
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        self._chk(self._L.rmr_bake_probe_field(self._ctx, C.byref(d), _fp(t) if len(t) else None, len(t), C.byref(q)))
+
+    def write_probe_field(self, desc, sh):
+        """rmr_write_probe_field: load a saved or synthetic field, sh (points, 28) float32 over the lattice desc
+        (an abi.VolumeDesc or (origin, spacing, shape))."""
+        d = desc if isinstance(desc, abi.VolumeDesc) else abi.volume_desc(*desc)
+        a = np.ascontiguousarray(sh, np.float32)
+        if a.size != d.n[0] * d.n[1] * d.n[2] * abi.PROBE_FLOATS:
+            raise ValueError("sh: 28 floats per lattice point")
+        self._chk(self._L.rmr_write_probe_field(self._ctx, C.byref(d), _fp(a)))
+
+    def read_probe_field(self):
+        """rmr_read_probe_field: (desc, sh): the field's abi.VolumeDesc and its (points, 28) float32 array."""
+        d = abi.VolumeDesc()
+        self._chk(self._L.rmr_read_probe_field(self._ctx, C.byref(d), None))
+        sh = np.zeros((d.n[0] * d.n[1] * d.n[2], abi.PROBE_FLOATS), np.float32)
+        self._chk(self._L.rmr_read_probe_field(self._ctx, None, _fp(sh)))
+        return d, sh
+
+    def probe_field_device(self):
+        """rmr_probe_field_device_ptr: the field as a (points, 28) torch tensor on the context's device, a view of
+        the library's memory (no copy, no sync), or None before a field exists. Valid until the next field,
+        probe_field_free or reload."""
+        import torch
+        ptr = self._L.rmr_probe_field_device_ptr(self._ctx)
+        if not ptr:
+            return None
+        d = abi.VolumeDesc()
+        self._chk(self._L.rmr_read_probe_field(self._ctx, C.byref(d), None))
+        shape = (d.n[0] * d.n[1] * d.n[2], abi.PROBE_FLOATS)
+        return torch.as_tensor(_DeviceArray(ptr, shape, self), device="cuda:%d" % self._device)
+
+    def probe_field_free(self):
+        """rmr_probe_field_free: release the field and the probe bakes' working memory."""
+        self._chk(self._L.rmr_probe_field_free(self._ctx))
+
+    def probe_irradiance(self, points, normals):
+        """rmr_probe_irradiance: irradiance / pi at n points with unit normals ((n, 3) float32 each) from the
+        context's field: (n, 4) float32, rgb and the valid corners' weight. A rejected query gives zeros and
+        counts in query_rejects()."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if len(p) != len(nn):
+            raise ValueError("one normal per point")
+        out = np.zeros((len(p), 4), np.float32)
+        self._chk(self._L.rmr_probe_irradiance(self._ctx, _fp(p), _fp(nn), len(p), _fp(out)))
+        return out
+
+    def probe_irradiance_device(self, points, normals):
+        """rmr_probe_irradiance_device: probe_irradiance on torch CUDA tensors, the (n, 4) result a torch tensor on
+        the same device; queued on the context's stream, no sync."""
+        import torch
+        n = self._device_points(points, normals)
+        out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+        self._chk(self._L.rmr_probe_irradiance_device(self._ctx, points.data_ptr(), normals.data_ptr(), n, out.data_ptr()))
+        return out
+
     def sync(self):
         self._chk(self._L.rmr_sync(self._ctx))
 
@@ -1128,7 +1249,7 @@ def bloom_pixels(rgba, params=None, **fields):
 
 
 def _volume_desc(origin, spacing, shape):
-    d = abi.volume_desc(origin, spacing, shape)
+    d = origin if isinstance(origin, abi.VolumeDesc) else abi.volume_desc(origin, spacing, shape)
     bad = check_volume(d)
     if bad:
         raise RMRError(-1, "bad volume descriptor field '%s'" % bad)
@@ -1254,6 +1375,84 @@ def bake_fold(L_rgb, c, cv=None):
     if rc != abi.RMR_OK:
         raise RMRError(rc, "rmr_bake_fold")
     return rgba, ao
+
+
+def check_probe_params(params=None, **fields):
+    """rmr_check_probe_params (no GPU): True iff the params are in range."""
+    q = abi.probe_params(**fields) if params is None else params
+    return lib().rmr_check_probe_params(C.byref(q)) == abi.RMR_OK
+
+
+def sh_basis(dirs):
+    """rmr_sh_basis (no GPU): Y_0 .. Y_8 of (..., 3) float32 unit vectors, (..., 9) float32."""
+    d = np.ascontiguousarray(dirs, np.float32)
+    if d.ndim < 1 or d.shape[-1] != 3:
+        raise ValueError("sh_basis: an (..., 3) array")
+    out = np.zeros(d.shape[:-1] + (9,), np.float32)
+    rc = lib().rmr_sh_basis(_fp(d), d.size // 3, _fp(out))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_sh_basis")
+    return out
+
+
+def probe_fold(L_rgb, dirs):
+    """rmr_probe_fold (no GPU): the probes' fold and resolve of host arrays laid out [k][i], L_rgb and dirs
+    (N, n, 3) float32: (n, 28) float32."""
+    L = np.ascontiguousarray(L_rgb, np.float32)
+    d = np.ascontiguousarray(dirs, np.float32)
+    if L.ndim != 3 or L.shape[2] != 3 or d.shape != L.shape:
+        raise ValueError("probe_fold: L_rgb and dirs of one shape (N, n, 3)")
+    nspp, n = L.shape[:2]
+    out = np.zeros((n, abi.PROBE_FLOATS), np.float32)
+    rc = lib().rmr_probe_fold(_fp(L), _fp(d), n, nspp, _fp(out))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_probe_fold")
+    return out
+
+
+def probe_irradiance_host(desc, sh, points, normals):
+    """rmr_probe_irradiance_host (no GPU): the lookup over a host field, (rgba (n, 4) float32, the first
+    rejected query's index or None)."""
+    d = _volume_desc(desc, None, None) if isinstance(desc, abi.VolumeDesc) else _volume_desc(*desc)
+    a = np.ascontiguousarray(sh, np.float32)
+    if a.size != d.n[0] * d.n[1] * d.n[2] * abi.PROBE_FLOATS:
+        raise ValueError("sh: 28 floats per lattice point")
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if len(p) != len(n):
+        raise ValueError("one normal per point")
+    out = np.zeros((len(p), 4), np.float32)
+    bad = C.c_size_t(0)
+    rc = lib().rmr_probe_irradiance_host(C.byref(d), _fp(a), _fp(p), _fp(n), len(p), _fp(out), C.byref(bad))
+    return out, (None if rc == abi.RMR_OK else int(bad.value))
+
+
+def save_probes(path, desc, sh):
+    """A probe field as a file: the line 'RMRPROBES 1 nx ny nz ox oy oz spacing' (floats as %.9g), then the
+    points * 28 little-endian float32 of sh."""
+    d = _volume_desc(desc, None, None) if isinstance(desc, abi.VolumeDesc) else _volume_desc(*desc)
+    a = np.ascontiguousarray(sh, "<f4")
+    if a.size != d.n[0] * d.n[1] * d.n[2] * abi.PROBE_FLOATS:
+        raise ValueError("sh: 28 floats per lattice point")
+    head = "RMRPROBES 1 %d %d %d %s\n" % (d.n[0], d.n[1], d.n[2],
+                                        " ".join("%.9g" % v for v in (d.origin[0], d.origin[1], d.origin[2], d.spacing)))
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        f.write(a.tobytes())
+
+
+def load_probes(path):
+    """(desc, sh) of a file save_probes or rmr_cli --probes wrote: an abi.VolumeDesc and (points, 28) float32."""
+    with open(path, "rb") as f:
+        w = f.readline().decode("ascii", "replace").split()
+        if len(w) != 9 or w[:2] != ["RMRPROBES", "1"]:
+            raise ValueError("%s: not a probe file (RMRPROBES 1 ...)" % path)
+        d = _volume_desc([float(v) for v in w[5:8]], float(w[8]), [int(v) for v in w[2:5]])
+        n = d.n[0] * d.n[1] * d.n[2] * abi.PROBE_FLOATS
+        raw = f.read()
+    if len(raw) != 4 * n:
+        raise ValueError("%s: %d payload bytes, the lattice needs %d" % (path, len(raw), 4 * n))
+    return d, np.frombuffer(raw, "<f4").astype(np.float32).reshape(-1, abi.PROBE_FLOATS)
 
 
 class _DeviceArray:
