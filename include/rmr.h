@@ -189,7 +189,8 @@ int rmr_get_section_cycles(rmr_ctx* ctx, uint64_t out[4]);
  * [14] map evals in shading batches (certified getNormal probes, rmr_trace.h cert_normals; part of [0]),
  * [4..7] the section cycles above (or the RMR_JIT_AMBCOUNT fallback counts, tools/amb_rate.py). */
 int rmr_get_counters(rmr_ctx* ctx, uint64_t out[16]);
-/* The first n of the whole counter block (n <= 34). [0..15] as above; [16] events the lane-slot kernels
+/* The first n of the whole counter block (n <= 74; [34..73]: the profiling build's counts of the trailing
+ * passes by pass index, rmr_internal.h kCntProfTrail, zeros in every other build). [0..15] as above; [16] events the lane-slot kernels
  * deposited into another lane's empty slot (the overflow deposit, rmr_trace.h RMR_SLOT_OVERFLOW);
  * [17..30] the profiling build's counters, each in a slot of its own (rmr_internal.h kCntProf*: refill
  * claim / ray cycles, uncertified hits, lanes per full map() batch, and the lane-slot schedule's passes,
@@ -1276,12 +1277,21 @@ int rmr_set_tuning(rmr_ctx* ctx, int shade_threshold, int grid_per_cu, long long
  * it. Scheduling only: results do not depend on it. RMR_E_INVALID for blocks < 0. */
 int rmr_set_grid_reserve(rmr_ctx* ctx, int blocks);
 /* Trailing steps of the lane-slot kernels (rmr_trace.h RMR_TRAIL_STEPS): behind each map-loop iteration's
- * whole map, up to `steps` (0..3) further march steps that evaluate the map's nearest primitive alone,
- * wherever a distance bound proves it the whole map's result. -1 (the default): the kernel class's own
- * number. Takes effect only in kernels specialised with the steps compiled in, and only with a positive
- * stepMultiply. Scheduling only: every sample and rmr_stats::map_evals are the same for every value.
- * RMR_E_INVALID outside -1..3. */
+ * whole map, up to `steps` (0..15) further march steps that evaluate the map's nearest primitive alone,
+ * wherever a distance bound proves it the whole map's result: a fixed number of passes, without the pass
+ * rule below. -1 (the default): the kernel class's own tuning. Takes effect only in kernels specialised with
+ * the steps compiled in, and only with a positive stepMultiply. Scheduling only: every sample and
+ * rmr_stats::map_evals are the same for every value. RMR_E_INVALID outside -1..15. */
 int rmr_set_trail_steps(rmr_ctx* ctx, int steps);
+/* The trailing passes chosen per wave: after each pass a wave takes another one if and only if fewer than
+ * `k_max` (0..15) have run in this iteration, the lanes still taking part are at least `ratio_eighths` / 8
+ * (0..8; 0: no lane test) of its active lanes, and, with `park_exit` (0 or 1), its finished lanes are still
+ * fewer than the park threshold that ends the iteration. (k, 0, 0) is rmr_set_trail_steps(k). Replaces an
+ * earlier rmr_set_trail_steps and is replaced by a later one. A tuning with a ratio or the park exit runs a
+ * code object of its own, specialised with the rule compiled in at the next launch (the rule's scalar state
+ * is not free in the kernel without it); a fixed schedule runs the one every other launch runs. Scheduling
+ * only, as above. RMR_E_INVALID, with the offending argument in rmr_last_error, outside those ranges. */
+int rmr_set_trail_tuning(rmr_ctx* ctx, int k_max, int ratio_eighths, int park_exit);
 /* Test hook: per-sample radiance (before the running mean) of the integer rect, written as
  * out[k][y-y0][x-x0][4]; sample k is seeded with times[k]. The accumulator is left unchanged. */
 int rmr_trace_samples(rmr_ctx* ctx, const float* times, int x0, int y0, int x1, int y1, uint32_t nspp, float* out);

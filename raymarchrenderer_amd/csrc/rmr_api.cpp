@@ -309,7 +309,12 @@ struct rmr_ctx {
     // refill threshold follows the park threshold as the others' follows the shading threshold
     int lane_slots = -1;
     int park_threshold = 0, slot_threshold = 0;
-    int trail_steps = -1;       // trailing steps per map-loop iteration (rmr_set_trail_steps): -1 the kernel class's
+    // trailing passes per map-loop iteration (rmr_set_trail_steps, rmr_set_trail_tuning): rmr_trail_rule.h's
+    // trail_word, -1 the kernel class's
+    int trail_word = -1;
+    // ... the word asks for the pass rule (a ratio or the park exit): the launch runs the code object that has
+    // the rule compiled in (rmr_trace.h RMR_TRAIL_RULE; its own cache key), every other launch the one without
+    bool trail_rule = false;
     int jit_slots = -1;         // the request `jit` was specialised with (slots_request)
     // nearest-primitive cache: 40 lanes per full map() batch, or once waiting lanes >= cache-served ones
     // (R = 8; csg256 with the candidate grid: 15.7 -> 14.8 ms per 4 spp against R = 2)
@@ -696,6 +701,8 @@ int ensure_jit(rmr_ctx* c, bool rays = false) {
     std::string key, log;
     std::vector<std::string> opts;
     if (c->instrument & RMR_INSTR_COUNT_FLOPS) opts.push_back("-DRMR_COUNT_FLOPS");
+    const bool trail_rule = facts.trail && c->trail_rule;   // (classes without the steps: the one code object)
+    if (trail_rule) opts.push_back("-DRMR_TRAIL_RULE=1");
     if (!rmr::jit_compile(src, code, key, log, opts)) {
         c->jit_failed = true;
         return fail(c, RMR_E_HIP, "hipRTC specialisation failed: " + log.substr(0, 2000));
@@ -709,6 +716,7 @@ int ensure_jit(rmr_ctx* c, bool rays = false) {
     }
     rmr::JitKernel k;
     k.key = key;
+    k.trail_rule = trail_rule;
     // a code object that does not load (e.g. a stale disk-cache entry) marks the scene as failed, so
     // auto mode falls back to the ahead-of-time kernels instead of retrying every launch
     if (hipModuleLoadData(&k.module, code.data()) != hipSuccess) {
@@ -739,7 +747,8 @@ int ensure_jit(rmr_ctx* c, bool rays = false) {
     k.slot_t = facts.slot_t();
     k.slot_t_small = facts.slot_t_small();
     k.trail = facts.trail;
-    k.trail_k = facts.trail_k();
+    k.trail_word = facts.trail_word();
+    k.trail_word_small = facts.trail_word_small();
     c->jit_loaded.push_back(k);
     jk = k;
     ready = true;
@@ -1254,12 +1263,13 @@ int render_tiles(rmr_ctx* c, const std::vector<TileXY>& tiles, int x0, int y0, i
             const bool small = P.n_units < (uint64_t)gp.grid * (uint64_t)(jk.block / 64) * (uint64_t)jk.chunk *
                                                (uint64_t)rmr::JitFacts::kSlotSmallClaims;
             const int batch = c->slot_threshold > 0 ? c->slot_threshold : (small ? jk.slot_t_small : jk.slot_t);
-            // trailing steps (rmr_trace.h RMR_TRAIL_STEPS), bits 16-17: only where the source has them, and
-            // only for a march that advances (rmr_trail_rule.h: the rule's t >= t0)
-            int trail = !jk.trail ? 0 : (c->trail_steps >= 0 ? c->trail_steps : jk.trail_k);
+            // trailing passes (rmr_trace.h RMR_TRAIL_STEPS; rmr_trail_rule.h trail_word), bits 16-24: only where
+            // the source has them, and only for a march that advances (rmr_trail_rule.h: the rule's t >= t0)
+            int trail = !jk.trail ? 0 : (c->trail_word >= 0 ? c->trail_word : (small ? jk.trail_word_small : jk.trail_word));
             if (!(P.step_mult > 0.0f) || !std::isfinite(P.step_mult)) trail = 0;
             if (!std::isfinite(P.trail_eps_hi)) trail = 0;   // no escape bound: no bound of eps either
-            P.shade_threshold = park | (batch << 8) | (std::min(trail, (int)rmr::kTrailMaxSteps) << 16);
+            if (!jk.trail_rule) trail = rmr::trail_word(rmr::trail_word_k(trail), 0, false);   // (this code object reads no rule)
+            P.shade_threshold = park | (batch << 8) | (trail << rmr::kTrailWordShift);
             P.refill_threshold = refill_for(c->refill_threshold, park);
         }
         if ((r = submit_launch(c, P, S, use_jit, gp.grid, rays ? c->d_rays : nullptr, !rl))) return r;
@@ -2062,10 +2072,35 @@ int rmr_set_tuning(rmr_ctx* c, int shade_threshold, int grid_per_cu, long long s
     return RMR_OK;
 }
 
+// the trailing passes' code object: with the pass rule compiled in or without (ensure_jit)
+static void set_trail_rule(rmr_ctx* c, bool rule) {
+    if (rule == c->trail_rule) return;
+    c->trail_rule = rule;
+    c->jit_ready = false;   // another code object (its own cache key); the ray-source kernels have no passes
+    c->jit_failed = false;
+}
+
 int rmr_set_trail_steps(rmr_ctx* c, int steps) {
     if (!c || steps < -1 || steps > rmr::kTrailMaxSteps) return RMR_E_INVALID;
     RMR_FLUSH(c);
-    c->trail_steps = steps;
+    c->trail_word = steps < 0 ? -1 : rmr::trail_word(steps, 0, false);
+    set_trail_rule(c, false);
+    return RMR_OK;
+}
+
+int rmr_set_trail_tuning(rmr_ctx* c, int k_max, int ratio_eighths, int park_exit) {
+    if (!c) return RMR_E_INVALID;
+    if (k_max < 0 || k_max > rmr::kTrailMaxSteps)
+        return fail(c, RMR_E_INVALID, "rmr_set_trail_tuning: k_max " + std::to_string(k_max) + " outside 0.." +
+                                          std::to_string(rmr::kTrailMaxSteps));
+    if (ratio_eighths < 0 || ratio_eighths > rmr::kTrailMaxRatio)
+        return fail(c, RMR_E_INVALID, "rmr_set_trail_tuning: ratio_eighths " + std::to_string(ratio_eighths) + " outside 0.." +
+                                          std::to_string(rmr::kTrailMaxRatio));
+    if (park_exit != 0 && park_exit != 1)
+        return fail(c, RMR_E_INVALID, "rmr_set_trail_tuning: park_exit " + std::to_string(park_exit) + " is neither 0 nor 1");
+    RMR_FLUSH(c);
+    c->trail_word = rmr::trail_word(k_max, ratio_eighths, park_exit != 0);
+    set_trail_rule(c, ratio_eighths != 0 || park_exit != 0);
     return RMR_OK;
 }
 

@@ -57,7 +57,7 @@ constexpr int kQueueWordStride = 32;   // 32-bit words between two partition cou
 // The kernels' raw device counters (KParams::counters; rmr_get_counters_n): kCounterSlots 64-bit words.
 // [0..15] as rmr.h documents them (the flop-count and other diagnostic builds use 9..15 as well). From
 // 16 up every counter has a slot of its own:
-constexpr int kCounterSlots = 34;
+constexpr int kCounterSlots = 74;
 constexpr int kCntOverflow = 16;         // lane-slot kernels: events deposited into another lane's empty slot
 // lane-slot kernels with trailing steps (rmr_trace.h RMR_TRAIL_STEPS), every build:
 constexpr int kCntTrailSteps = 31;       //   trailing steps taken (lane-level; part of counter 0)
@@ -81,6 +81,13 @@ constexpr int kCntProfBatchEv = 27;      //   events in the shading batches (bat
 constexpr int kCntProfLostIdle = 28;     //   map-loop lane-iterations of idle lanes while the queue has work
 constexpr int kCntProfLostIdleExh = 29;  //   the same once the wave found the queue used up (the drain)
 constexpr int kCntProfReadyWait = 30;    //   ready rays waiting in a slot whose lane marches, summed over map-loop iterations
+// ... the trailing passes by pass index: kCntProfTrail + ((queue used up ? kCntProfTrailIdx : 0) + min(pass
+// index, kCntProfTrailIdx - 1)) * kCntProfTrailWhat + what, what = 0 passes run, 1 lanes taking part, 2 lanes
+// accepted, 3 the wave's active lanes at the pass's start, 4 its finished lanes sitting through the pass
+constexpr int kCntProfTrail = 34;
+constexpr int kCntProfTrailIdx = 4;
+constexpr int kCntProfTrailWhat = 5;
+static_assert(kCntProfTrail + 2 * kCntProfTrailIdx * kCntProfTrailWhat == kCounterSlots, "the profile build's pass counters end the block");
 
 struct KParams {
     // ---- scene tables (device pointers, read-only) ----

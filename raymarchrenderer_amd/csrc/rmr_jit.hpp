@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "rmr_trail_rule.h"
 #include "scene.hpp"
 
 // Environment switches (RMR_GRID, RMR_JIT_OPTS, RMR_JIT_BAKE, ...: A/B experiments, tools/) exist only
@@ -45,7 +46,9 @@ struct JitKernel {
     int park_t = 0, slot_t = 0; // its default thresholds (JitFacts)
     int slot_t_small = 0;       // ... the batch threshold of launches under kSlotSmallClaims claims per wave
     bool trail = false;         // the source has the trailing steps (rmr_trace.h RMR_TRAIL_STEPS)
-    int trail_k = 0;            // ... and takes this many per map-loop iteration unless told otherwise
+    bool trail_rule = false;    // ... and the pass rule (RMR_TRAIL_RULE: the code object of rmr_set_trail_tuning's rule)
+    int trail_word = 0;         // ... and runs its passes by this tuning unless told otherwise (rmr_trail_rule.h
+    int trail_word_small = 0;   //     trail_word; launches under kSlotSmallClaims claims per wave: the second)
 };
 
 // What jit_source decided about the kernel class (the launch settings follow from these, not from
@@ -59,8 +62,14 @@ struct JitFacts {
     bool slots_ok = false, slots = false;
     bool overflow = false;   // ... with the park step's overflow deposit (rmr_trace.h RMR_SLOT_OVERFLOW)
     bool trail = false;      // ... with the trailing steps compiled in (rmr_trace.h RMR_TRAIL_STEPS)
-    // trailing steps per map-loop iteration where the source has them
-    int trail_k() const { return trail ? 2 : 0; }
+    // the trailing passes' tuning where the source has them (rmr_trail_rule.h trail_word: at most k_max passes
+    // per map-loop iteration, the pass rule's ratio in eighths, its park exit),
+    // and the same for launches under kSlotSmallClaims claims per wave. Fixed schedules: the class's own code
+    // object has no pass rule (rmr_trace.h RMR_TRAIL_RULE). Three passes: same process, 1080p 64 spp, K = 2 / 3 / 4
+    // / 5 at 35.23 / 34.51 / 34.53 / 34.95 ms, and 480x270 1 spp 0.719 / 0.658 ms at K = 2 / 3
+    // (profiles/trail_adaptive_sweep.log, trail_adaptive_small.log)
+    int trail_word() const { return trail ? rmr::trail_word(3, 0, false) : 0; }
+    int trail_word_small() const { return trail ? rmr::trail_word(3, 0, false) : 0; }
     int chunk() const { return (cache || slots) ? 64 : 128; }   // rmr_trace.h RMR_CHUNK_CACHE / RMR_CHUNK_SLOTS / RMR_CHUNK
     // lane slots: finished marches per park step, slot events per shading batch (Cornell-5 1080p 64 spp:
     // flat over 8-10 / 28-40, +10% and more outside 6-12 / 24-48)

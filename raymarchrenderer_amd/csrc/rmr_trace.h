@@ -2580,7 +2580,7 @@ static_assert(RMR_QUEUE_PARTS >= 1 && RMR_QUEUE_PARTS <= 64 && RMR_QUEUE_PARTS *
 // Trailing steps (lane-slot kernels with batch probes; the hipRTC source asks for them, rmr_jit.cpp): every
 // map-loop iteration still runs the whole approximate map for every marching lane, and that map leaves its
 // minimiser w and its runner-up s2 in registers. After the iteration's march_update the wave runs up to K
-// more passes (K: bits 16-17 of KParams::shade_threshold, 0 = none) in which a lane whose one-primitive
+// more passes (K: bits 16-19 of KParams::shade_threshold, 0 = none; rmr_trail_rule.h trail_word) in which a lane whose one-primitive
 // bound holds at its new march point (rmr_trail_rule.h: the derivation and the float statements) takes
 // the next march step from primitive w alone — map(p) is (F_w(p), id_w) there, the value the whole map
 // returns — and a lane whose bound fails sits the pass out, unchanged, until the next iteration's map.
@@ -2590,8 +2590,13 @@ static_assert(RMR_QUEUE_PARTS >= 1 && RMR_QUEUE_PARTS <= 64 && RMR_QUEUE_PARTS *
 // form the pass consumes (trail_row), so that the pass has no type test and no select. The rule's eps is one
 // number for the launch (KParams::trail_eps_hi, from the escape boxes and the eye); a launch without the
 // escape bound has none and takes no trailing step.
+// RMR_TRAIL_RULE (-D, the code object of a launch tuned with rmr_set_trail_tuning's ratio or park exit): the
+// number of passes chosen per wave after each pass, up to K (the pass rule, in the map loop).
 #ifndef RMR_TRAIL_STEPS
 #define RMR_TRAIL_STEPS 0
+#endif
+#ifndef RMR_TRAIL_RULE
+#define RMR_TRAIL_RULE 0
 #endif
 #ifndef RMR_TRAIL_LDS
 #define RMR_TRAIL_LDS 0
@@ -2678,6 +2683,7 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
     constexpr bool OVF = SLOTS && RMR_SLOT_OVERFLOW;   // events of lanes with a full slot into empty slots
     constexpr bool TRAIL = BP && RMR_TRAIL_STEPS;       // one-primitive march steps behind each full map
     constexpr bool TRAIL_LDS = TRAIL && RMR_TRAIL_LDS;
+    constexpr bool TRAIL_RULE = TRAIL && RMR_TRAIL_RULE;   // ... their number chosen per wave (the pass rule)
     constexpr uint32_t CHUNK = MAP::kCache ? RMR_CHUNK_CACHE : (SLOTS ? RMR_CHUNK_SLOTS : RMR_CHUNK);
     const uint32_t n_units = (uint32_t)P.n_units;   // < 2^32 per launch (host chunking)
     // units per claim: the LDS ray buffer's CHUNK, or fewer for a small launch (the host's chunk_units)
@@ -2709,7 +2715,11 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
     // lane slots: finished marches before the park step runs, slot events before a shading batch
     // (in the shading threshold's place: bits 0-7 and 8-15)
     const int PK = T & 0xff, T2 = (T >> 8) & 0xff;
-    const int KT = TRAIL ? (T >> 16) & 3 : 0;   // trailing steps per map-loop iteration (rmr_api.cpp)
+    // trailing passes per map-loop iteration, at most (rmr_trail_rule.h trail_word; rmr_api.cpp); in the code
+    // object with the pass rule (RMR_TRAIL_RULE), the rule's ratio in eighths and its park exit
+    const int KT = TRAIL ? trail_word_k(T >> kTrailWordShift) : 0;
+    const int RT = TRAIL_RULE ? trail_word_ratio(T >> kTrailWordShift) : 0;
+    const bool PX = TRAIL_RULE && trail_word_park_exit(T >> kTrailWordShift);
     int sst = 0;             // the lane's slot: 0 empty, 1 an event awaiting shading, 2 a ray ready to march
     uint32_t nev = 0;        // slots holding an event (wave-uniform)
     // eye_map: every primary ray (a fresh unit, or a separateChannels restart) starts its march at
@@ -2751,6 +2761,9 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
     // ... by idle lanes (those of a wave whose queue is used up apart), and ready rays that wait in their
     // slot while the slot's lane marches, per map-loop iteration
     uint64_t lost_idle = 0, lost_idle_exh = 0, ready_wait = 0;
+    // the trailing passes by pass index and queue state: lane l keeps word l of the kCntProfTrail block (a
+    // wave runs far fewer than 2^26 passes of at most 64 lanes)
+    uint32_t tpass_acc = 0;
     const uint64_t c_begin = __builtin_amdgcn_s_memtime();
 #define RMR_STAMP(v) const uint64_t v = __builtin_amdgcn_s_memtime()
 #else
@@ -3199,6 +3212,23 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                     // of the generated primitives' own literals, so below P.n_prims <= kTrailLdsPrims.
                     // (The global table is read by the lanes that take part alone: index 0 otherwise.)
                     const float4* const row = (const float4*)s_tp + (TRAIL_LDS ? 2 * tr_w : 0);
+                    // The pass rule (rmr_trail_rule.h trail_word), in the code object that has it (RMR_TRAIL_RULE;
+                    // a launch with rmr_set_trail_tuning's ratio or park exit runs that one): after each pass the
+                    // wave takes another iff fewer than KT have run; with the park exit, fewer than TL lanes have
+                    // finished, the count that ends the iteration below; and 8 x the lanes still taking part
+                    // >= RT x the active lanes. A compile-time switch, not a launch-constant branch: the rule's
+                    // five scalar values, live across the map loop, cost the fixed schedule 3.5% of the launch
+                    // in a kernel that already keeps 96 scalar registers in vector lanes.
+                    // Bounded by construction: k counts up to KT <= 15 (four bits of the launch word) whatever
+                    // the masks hold, every condition is a scalar test of the wave's own masks, and nothing
+                    // here waits on another wave or on memory another wave writes. The rule only chooses how
+                    // many passes run: a pass takes a step only where the acceptance rule proves it the whole
+                    // map's step, so every pass count gives the same samples.
+                    uint64_t smr = 0, amr = 0;   // the wave's finished and active lanes, for the rule
+                    if constexpr (TRAIL_RULE) {
+                        smr = __ballot(is_shade(L.phase));
+                        amr = __ballot(is_active(L.phase));
+                    }
                     for (int k = 0; k < KT && qm; k++) {
                         const V3 p = vfma(L.d, L.t, L.o);
                         float mid, len2, F;
@@ -3221,7 +3251,17 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                                             __builtin_amdgcn_ballot_w64(tc.below) & __builtin_amdgcn_ballot_w64(tc.nearer);
                         ltpasses++;
                         ltlanes += (uint32_t)__popcll(qm);
-#ifdef RMR_TRAIL_CHECK   // diagnostics (RMR_JIT_OPTS=-DRMR_TRAIL_CHECK): evaluated lanes whose eps(p) exceeds the launch's bound
+#ifdef RMR_PROFILE   // by pass index and queue state (rmr_internal.h kCntProfTrail): lane l keeps the block's word l
+                        {
+                            // (the two ballots by every lane, ahead of the lanes' own selects)
+                            const int n_act = __popcll(__ballot(is_active(L.phase))), n_fin = __popcll(__ballot(is_shade(L.phase)));
+                            const int what = (int)(lane_now() % (uint32_t)kCntProfTrailWhat);
+                            const int n = what == 0 ? 1 : what == 1 ? __popcll(qm) : what == 2 ? __popcll(um) : what == 3 ? n_act : n_fin;
+                            const int idx = (exhausted ? kCntProfTrailIdx : 0) + (k < kCntProfTrailIdx ? k : kCntProfTrailIdx - 1);
+                            tpass_acc += (int)(lane_now() / (uint32_t)kCntProfTrailWhat) == idx ? (uint32_t)n : 0u;
+                        }
+#endif
+#ifdef RMR_TRAIL_CHECK  // diagnostics (RMR_JIT_OPTS=-DRMR_TRAIL_CHECK): evaluated lanes whose eps(p) exceeds the launch's bound
                         ltcheck += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(
                             q && trail_eps(trail_linf(p.x, p.y, p.z) + 0.002f, P.npc_eps0) > P.trail_eps_hi));
 #endif
@@ -3241,6 +3281,16 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
                         qm = um & __builtin_amdgcn_ballot_w64(is_active(L.phase));
                         lmaps += (uint32_t)__popcll(um);
                         ltsteps += (uint32_t)__popcll(um);
+                        if constexpr (TRAIL_RULE) {
+                            // the lanes whose march ended on this step: trail_update moves a lane from
+                            // PH_MARCH to PH_HIT or PH_MISS and nowhere else, so the finished and the active
+                            // lanes follow in scalar registers, without a compare
+                            const uint64_t fin = um & ~qm;
+                            smr |= fin;
+                            amr &= ~fin;
+                            if (PX && __popcll(smr) >= TL) break;
+                            if (8 * __popcll(qm) < RT * __popcll(amr)) break;
+                        }
                     }
                 }
                 const uint64_t sm = __ballot(is_shade(L.phase));
@@ -3514,6 +3564,10 @@ RMR_D void trace_main(const KParams& P, const float4* rays = nullptr) {
         atomicMax(P.counters + 13, tn);
         if (t_exh) atomicAdd(P.counters + 15, tn - t_exh);
     }
+#endif
+#ifdef RMR_PROFILE
+    if (tpass_acc && lane_now() < (uint32_t)(2 * kCntProfTrailIdx * kCntProfTrailWhat))
+        atomicAdd(P.counters + kCntProfTrail + lane_now(), (unsigned long long)tpass_acc);
 #endif
     if (lane_now() == 0) {
 #ifdef RMR_PROFILE

@@ -83,7 +83,21 @@
 namespace rmr {
 
 constexpr float kTrailProbeDelta = 0.0010001f;   // rmr_trace.h NPC_PROBE_DELTA
-constexpr int kTrailMaxSteps = 3;                // trailing steps per map-loop iteration (two bits of the launch word)
+constexpr int kTrailMaxSteps = 15;               // trailing passes per map-loop iteration (four bits of the launch word)
+constexpr int kTrailMaxRatio = 8;                // the pass rule's ratio in eighths (8: every active lane takes part)
+
+// The trailing passes' launch word, bits 16-24 of the lane-slot kernels' KParams::shade_threshold (below them
+// the park and the batch thresholds): after each pass a wave takes another one iff fewer than k_max have run,
+// (park_exit) its finished lanes are still fewer than the park threshold, and 8 x the lanes still taking
+// part >= ratio x its active lanes (ratio 0: no lane test). (k, 0, false) is the fixed schedule of k passes.
+constexpr int kTrailWordShift = 16;
+RMR_TRAIL_HD int trail_word(int k_max, int ratio, bool park_exit) { return k_max | (ratio << 4) | ((int)park_exit << 8); }
+RMR_TRAIL_HD int trail_word_k(int word) { return word & 15; }
+RMR_TRAIL_HD int trail_word_ratio(int word) { return (word >> 4) & 15; }
+RMR_TRAIL_HD bool trail_word_park_exit(int word) { return ((word >> 8) & 1) != 0; }
+RMR_TRAIL_HD bool trail_word_valid(int k_max, int ratio, int park_exit) {
+    return k_max >= 0 && k_max <= kTrailMaxSteps && ratio >= 0 && ratio <= kTrailMaxRatio && (park_exit == 0 || park_exit == 1);
+}
 
 // |p|_inf
 RMR_TRAIL_HD float trail_linf(float x, float y, float z) { return fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z))); }

@@ -200,7 +200,7 @@ void run_marches(const Scene& s, const Lean& L, uint64_t want, uint64_t seed, Le
             if (dx < 0.001f || t >= s.max_dist) break;
             const float tn = fmaf(dx, mult, t);
             if ((double)tn > texit) break;   // escaped
-            // up to three trailing steps after the iteration's own
+            // up to kTrailMaxSteps trailing steps after the iteration's own
             float tt = tn;
             for (int k = 0; k < rmr::kTrailMaxSteps; k++) {
                 float F;

@@ -4,7 +4,7 @@
 // Per scene, rays are marched as the kernel marches them (march(), stepMultiply 0.25 / 0.5 / 1.7): at every
 // march point (the anchor) the approximate fold of the generated map is run — box keys first, then the
 // spheres, each square root the correctly rounded one moved by -1 / 0 / +1 ulp at random, which is the
-// premise the map's error bound err() is stated on — and gives w and s2. From the anchor up to three
+// premise the map's error bound err() is stated on — and gives w and s2. From the anchor up to fifteen
 // trailing steps follow, each through trail_rule with primitive w alone, and further random steps of
 // the same ray up to 1.5 |s2| ahead. Origins are random points of the scene's box, the eye, and bounce
 // origins on faces, edges and corners of the boxes and on the spheres (exactly on them and 0.003 off).
@@ -350,7 +350,7 @@ Tally run_scene(const Scene& s, uint64_t want, uint64_t seed) {
             const float anchor = rmr::trail_anchor(s2, c.r2, rmr::trail_eps(rmr::trail_linf(p0[0], p0[1], p0[2]), c.eps0));
             if (dx < 0.001f || t >= s.max_dist) break;
             const float tn = fmaf(dx, mult, t);
-            // up to three trailing steps after the iteration's own
+            // up to kTrailMaxSteps trailing steps after the iteration's own
             float tt = tn;
             for (int k = 0; k < rmr::kTrailMaxSteps; k++) {
                 float F;

@@ -175,9 +175,15 @@ class Renderer:
         self._chk(self._L.rmr_set_tuning(self._ctx, st, int(grid_per_cu), int(samp_budget)))
 
     def set_trail_steps(self, steps):
-        """Trailing steps per map-loop iteration of the lane-slot kernels (rmr_set_trail_steps): 0..3, -1 the
-        kernel class's own; scheduling only."""
+        """Trailing steps per map-loop iteration of the lane-slot kernels (rmr_set_trail_steps): a fixed 0..15,
+        -1 the kernel class's own tuning; scheduling only."""
         self._chk(self._L.rmr_set_trail_steps(self._ctx, int(steps)))
+
+    def set_trail_tuning(self, k_max, ratio_eighths=0, park_exit=False):
+        """The trailing passes chosen per wave (rmr_set_trail_tuning): at most k_max (0..15) per map-loop
+        iteration, another one only while the lanes taking part are ratio_eighths / 8 (0..8) of the active
+        ones and, with park_exit, the finished lanes are fewer than the park threshold; scheduling only."""
+        self._chk(self._L.rmr_set_trail_tuning(self._ctx, int(k_max), int(ratio_eighths), int(park_exit)))
 
     def set_grid_reserve(self, blocks):
         """Workgroups the persistent trace launch leaves free (rmr_set_grid_reserve; scheduling only)."""

@@ -15,6 +15,8 @@ VARIANT = [LABEL=]SPEC[;SPEC...], SPEC one of
     trail:K | trail:K,global     lane-slot kernels: K trailing steps per map-loop iteration (RMR_JIT_TRAIL=1 and
                     rmr_set_trail_steps; K = 0: compiled in, none taken); global: the primitive table
                     read from global memory (RMR_JIT_TRAIL=2) instead of the LDS copy
+    tune:K,R,X      lane-slot kernels: the trailing passes chosen per wave (RMR_JIT_TRAIL=1 and
+                    rmr_set_trail_tuning): at most K passes, ratio R eighths, park exit X (0 or 1)
 e.g.  python tools/abrun.py --cases c2,c4 base="lib:tools/librmr_base.so" new="lib:raymarchrenderer_amd/librmr_diag.so"
       python tools/abrun.py --cases glass,default w6="opts:-DRMR_PROG_WAVES=6" w7="opts:-DRMR_PROG_WAVES=7" def=""
 
@@ -57,7 +59,7 @@ CASES = {
 
 def parse_variant(text):
     label, _, spec = text.partition("=") if ("=" in text.split(":")[0]) else ("", "", text)
-    v = {"label": label or text or "default", "lib": None, "env": {}, "cull": None, "shade": None, "trail": None}
+    v = {"label": label or text or "default", "lib": None, "env": {}, "cull": None, "shade": None, "trail": None, "tune": None}
     for item in filter(None, spec.split(";")):
         kind, _, val = item.partition(":")
         if kind == "lib":
@@ -80,13 +82,27 @@ def parse_variant(text):
             v["env"]["RMR_JIT_OVERFLOW"] = "1" if val == "on" else "0"
         elif kind == "trail":   # rmr_jit.cpp: part of the generated source; K: a launch parameter
             k, _, tab = val.partition(",")
-            if tab not in ("", "global") or not k.isdigit() or int(k) > 3:
-                raise SystemExit("trail:K or trail:K,global with K in 0..3, not %r" % item)
+            if tab not in ("", "global") or not k.isdigit() or int(k) > 15:
+                raise SystemExit("trail:K or trail:K,global with K in 0..15, not %r" % item)
             v["env"]["RMR_JIT_TRAIL"] = "2" if tab else "1"
             v["trail"] = int(k)
+        elif kind == "tune":   # a launch parameter (rmr_set_trail_tuning)
+            w = val.split(",")
+            if len(w) != 3 or not all(x.isdigit() for x in w):
+                raise SystemExit("tune:K,R,X with K in 0..15, R in 0..8, X 0 or 1, not %r" % item)
+            v["env"]["RMR_JIT_TRAIL"] = "1"
+            v["tune"] = tuple(int(x) for x in w)
         else:
             raise SystemExit("unknown variant spec %r" % item)
     return v
+
+
+def ncnt(v):
+    """Counters to read: the trailing steps' own from 31, the profiling build's pass counts from 34 (this
+    tree's library; rmr_internal.h kCntProfTrail)."""
+    if v["trail"] is None and v["tune"] is None:
+        return 32
+    return 74 if "-DRMR_PROFILE" in v["env"].get("RMR_JIT_OPTS", "") and not v["lib"] else 34
 
 
 def apply_env(v, keys, saved):
@@ -135,6 +151,8 @@ def main():
                     r.set_tuning(v["shade"], -1, 0)
                 if v["trail"] is not None:
                     r.set_trail_steps(v["trail"])
+                if v["tune"] is not None:
+                    r.set_trail_tuning(*v["tune"])
                 r.reload()
                 r.reset_stats()
                 r.render_spp(times)
@@ -142,7 +160,7 @@ def main():
                 if rnd:
                     ms[i].append(s.trace_ms)
                 if rnd == a.rounds:
-                    img[i], st[i], cnt[i] = r.read_accum(), s, r.counters(32 if v["trail"] is None else 34)
+                    img[i], st[i], cnt[i] = r.read_accum(), s, r.counters(ncnt(v))
         apply_env({"env": {}}, keys, saved)
         t0 = float(np.median(ms[0]))
         out = {"case": name, "W": W, "H": H, "spp": spp, "bounces": bounces}
@@ -158,7 +176,7 @@ def main():
                 "overflow_deposits": cnt[i][16],
                 "bitwise_equal_to_first": bool(np.array_equal(img[i].view(np.uint32), img[0].view(np.uint32))),
             }
-            if v["trail"] is not None:   # rmr_internal.h kCntTrail*: steps taken, passes, lanes evaluated in them
+            if v["trail"] is not None or v["tune"] is not None:   # rmr_internal.h kCntTrail*: steps taken, passes, lanes evaluated in them
                 c = cnt[i]
                 out[v["label"]]["trail"] = {
                     "steps": c[31], "passes": c[32], "lanes": c[33],
@@ -176,6 +194,16 @@ def main():
                                                "shade": round(c[6] / tot, 4), "cache_full_maps": round(c[9] / tot, 4),
                                                # parts of refill: work-queue claims, the chunk's primary rays
                                                "refill_claims": round(c[17] / tot, 4), "refill_rays": round(c[18] / tot, 4)}
+                if len(c) >= 74 and c[32]:   # trailing passes by pass index (the last: that index and later)
+                    rows = {}
+                    for e, tag in enumerate(("queue_has_work", "queue_used_up")):
+                        for k in range(4):
+                            n, qm, um, act, fin = c[34 + (4 * e + k) * 5:39 + (4 * e + k) * 5]
+                            if n:
+                                rows["%s_pass%d" % (tag, k)] = {
+                                    "passes": n, "lanes_taking_part": round(qm / n, 2), "lanes_accepted": round(um / n, 2),
+                                    "active_lanes": round(act / n, 2), "finished_lanes_sitting": round(fin / n, 2)}
+                    out[v["label"]]["trail_passes"] = rows
                 if c[3]:   # cache kernels: lanes per full map() batch
                     out[v["label"]]["lanes_per_full_batch"] = round(c[21] / c[3], 2)
                 if c[22]:   # lane-slot kernels: the schedule's own counts, per map-loop iteration / per batch
