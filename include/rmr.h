@@ -1091,8 +1091,9 @@ void* rmr_mesh_bake_device_ptr(rmr_ctx* ctx, int which);
  *
  * The companion of the vertex bake for what moves through a scene: radiance over the whole sphere is sampled
  * at probe points and projected onto nine spherical-harmonic functions per colour channel; irradiance / pi for
- * any position and normal is then looked up by trilinear interpolation over a lattice of probes. There are no
- * visibility or back-face weights: light leaks through walls thinner than a cell.
+ * any position and normal is then looked up by trilinear interpolation over a lattice of probes. This lookup has
+ * no visibility or back-face weights: light leaks through walls thinner than a cell (rmr_probe_irradiance_vis,
+ * below, is the lookup with them).
  *
  * The rule (csrc/rmr_probe_rule.h holds the parts the host and the kernels share). All arithmetic is float32,
  * each operation rounded on its own (no fma); `/` is the correctly rounded division; every select is a
@@ -1194,6 +1195,94 @@ int rmr_probe_field_free(rmr_ctx* ctx);
  * synchronising. Rejected queries are counted (rmr_query_rejects). Needs no scene. */
 int rmr_probe_irradiance(rmr_ctx* ctx, const float* points, const float* normals, size_t n, float* out_rgba);
 int rmr_probe_irradiance_device(rmr_ctx* ctx, const float* d_points, const float* d_normals, size_t n, float* d_out_rgba);
+
+/* -- the probes' visibility: octahedral depth moments per probe, and the lookup weighted by them -- */
+/* No counterpart in the reference. Additive: rmr_probe_irradiance, the probe bake, the field and its file are as
+ * they were; this is a second lookup over the same field. DESIGN.md §4.19.
+ *
+ * rmr_probe_irradiance blends a cell's eight probes by position alone, so light leaks through a wall thinner
+ * than a cell. Here each probe also holds a small map of how far it sees, and the lookup weighs a corner down
+ * when the point lies behind what that probe sees (a Chebyshev bound on the two moments of distance) or faces
+ * away from it.
+ *
+ * The rule (csrc/rmr_probe_vis_rule.h holds the parts the host and the kernels share). As above: float32, each
+ * operation rounded on its own (no fma), `/` and sqrt correctly rounded, every select a comparison. |x| is
+ * x < 0 ? -x : x and sgn(x) is x >= 0 ? 1 : -1.
+ *
+ * The map: 8 x 8 texels per probe, two floats (m1, m2) per texel: vis[64][2], 128 floats. Texel j = iy * 8 +
+ *   ix has the direction D_j, the octahedral decode of its centre: u = (((float)ix + 0.5) / 8) * 2 - 1, v
+ *   likewise from iy (all exact); n = (u, v, (1 - |u|) - |v|); for n.z < 0: n.x = (1 - |v|) * sgn(u) and n.y =
+ *   (1 - |u|) * sgn(v); len = sqrt(((n.x * n.x) + (n.y * n.y)) + (n.z * n.z)); D_j = (n.x / len, n.y / len,
+ *   n.z / len). The poles are +-z.
+ * Samples: sample k of probe i has the direction d_k of rmr_bake_probes (the same invocation, seeds, first
+ *   jitter call and zero-normal randHemisphere), and the distance t_k = the t of rmr_cast_rays' march for the
+ *   ray (o = p, d_k) without RMR_CAST_NORMALS (maxDist, maxSteps and stepMultiply from the context's params;
+ *   the ray is not put through rmr_check_rays). A sample whose t_k is not finite is skipped; otherwise r_k =
+ *   t_k < range ? t_k : range. range is finite and > 0.
+ * Fold, for texel j over the samples in ascending k: c = ((D.x * d.x) + (D.y * d.y)) + (D.z * d.z); if
+ *   !(c > 0) the sample does not touch the texel; otherwise c2 = c * c, c4 = c2 * c2, c8 = c4 * c4, c16 = c8 *
+ *   c8, w = c16 * c16 (c^32; no powf); A = A + w; M1 = M1 + (w * r); M2 = M2 + (w * (r * r)).
+ *   Resolve: A > 0: m1 = M1 / A and m2 = M2 / A; otherwise m1 = range and m2 = range * range (a texel nobody
+ *   sampled sees as far as the range). Each texel meets its samples in ascending k as one sequential sum, so
+ *   neither the cut into launches nor the mapping to threads changes a bit.
+ * Which probes: the list forms use rmr_probe_params and the probe bake's reject and buried rules; a rejected or
+ *   buried probe casts nothing and all 128 of its floats are 0; rejects are counted as in the probe bake. The
+ *   field form bakes for the context's field: probe j is used iff it is valid there (sh[j][27] > 0; no buried
+ *   test of its own); every other probe gets 128 zeros.
+ * Lookup: the cell, the factors g0 = (u_x * u_y) * u_z, the corner order, the SH resolve and the reject rule
+ *   are rmr_probe_irradiance's. bias is finite and >= 0. qb_a = q_a + (bias * nrm_a). Per corner with a valid
+ *   probe, at P = the lattice position of the corner's indices (origin_a + ((float)index_a * spacing)):
+ *   v = qb - P; r = sqrt(((v.x * v.x) + (v.y * v.y)) + (v.z * v.z)).
+ *   r == 0: wb = 1 and wv = 1. Otherwise:
+ *   back face: dn = ((v.x * nrm.x) + (v.y * nrm.y)) + (v.z * nrm.z); b = (-dn) / r (the cosine between the
+ *     normal and the direction from the point to the probe); h = (b + 1) * 0.5; wb = (h * h) + 0.2f.
+ *   visibility: dir = (v.x / r, v.y / r, v.z / r). Its texel under the octahedral encode: s = (|x| + |y|) +
+ *     |z|; ox = x / s; oy = y / s; for z < 0 (so z = -0 is the upper half): (ox, oy) = ((1 - |oy|) * sgn(x),
+ *     (1 - |ox|) * sgn(y)), both from the old values; per axis f = floor(((o * 0.5) + 0.5) * 8); f = f > 0 ? f
+ *     : 0; f = f < 7 ? f : 7 (a NaN gives 0); ix = (int)f from ox, iy from oy. (m1, m2) = vis[iy * 8 + ix].
+ *     r <= m1: wv = 1. Otherwise var = |m2 - (m1 * m1)|; dl = r - m1; ch = var / (var + (dl * dl)); wv = (ch *
+ *     ch) * ch; wv < 0.05f: wv = 0.05f (the floor keeps a point that every probe calls occluded from dividing
+ *     by nothing).
+ *   g = (g0 * wb) * wv, or 0 for a probe that is not valid. W, B, the SH resolve, the clamp at 0 and out.a = W
+ *   follow as in rmr_probe_irradiance. */
+/* out[j] = D_j. RMR_E_INVALID for NULL. No context, no GPU. */
+int rmr_probe_vis_dirs(float out[64][3]);
+/* The fold and resolve on host arrays laid out [k][i]: d_and_t [nspp][n][4] = (d.xyz, t); out [n][128]. No reject
+ * or buried rule: every probe is used. RMR_E_INVALID for nspp == 0, nspp > 2^24, a range that is not finite and
+ * > 0, or a missing array. No context, no GPU. */
+int rmr_probe_vis_fold(const float* d_and_t, size_t n, uint32_t nspp, float range, float* out);
+/* The lookup on the host over sh [points of desc][28] and vis [points of desc][128]; results, return value and
+ * *first_bad as rmr_probe_irradiance_host's; also RMR_E_INVALID, nothing written, for a bias that is not finite
+ * and >= 0. No context, no GPU. */
+int rmr_probe_irradiance_vis_host(const rmr_volume_desc* desc, const float* sh, const float* vis, const float* points,
+                                  const float* normals, size_t n, float bias, float* out_rgba, size_t* first_bad);
+/* The maps of a host list of probes: out_vis [n][128]. Runs on the context's stream and synchronises. State
+ * rules, error codes and limits are rmr_bake_probes', except that params.separate_channels does not matter:
+ * nothing is traced. Also RMR_E_INVALID for a range that is not finite and > 0. The samples are cut into runs
+ * of k under rmr_set_tuning's samp_budget at 16 bytes per (probe, sample); the running sums between launches
+ * (768 bytes per probe) are the library's. */
+int rmr_bake_probe_visibility(rmr_ctx* ctx, const float* points, size_t n, const float* times, uint32_t nspp,
+                              const rmr_probe_params* params, float range, float* out_vis);
+/* The same with device pointers (times stays a host array), queued on the context's stream without
+ * synchronising; params->origin_extent is required, as in rmr_bake_probes_device. */
+int rmr_bake_probe_visibility_device(rmr_ctx* ctx, const float* d_points, size_t n, const float* times, uint32_t nspp,
+                                     const rmr_probe_params* params, float range, float* d_out_vis);
+/* The maps of the context's field, stored with it ([points][128] floats and range); no synchronisation.
+ * RMR_E_STATE without a field or without a scene. rmr_bake_probe_field, rmr_write_probe_field,
+ * rmr_probe_field_free, rmr_reload and rmr_destroy drop the visibility (a new field has none). */
+int rmr_bake_probe_field_visibility(rmr_ctx* ctx, const float* times, uint32_t nspp, float range);
+/* Loads saved or synthetic maps for the context's field (vis: host memory, [points][128]); synchronises.
+ * RMR_E_STATE without a field; needs no scene. */
+int rmr_write_probe_field_visibility(rmr_ctx* ctx, const float* vis, float range);
+/* The maps and / or the range to host memory (either may be NULL); synchronises. RMR_E_STATE without them. */
+int rmr_read_probe_field_visibility(rmr_ctx* ctx, float* vis, float* range_out);
+void* rmr_probe_field_visibility_device_ptr(rmr_ctx* ctx);
+/* The weighted lookup over the context's field and its visibility; as rmr_probe_irradiance otherwise.
+ * RMR_E_STATE without a field or without its visibility; RMR_E_INVALID for a bias that is not finite and >= 0. */
+int rmr_probe_irradiance_vis(rmr_ctx* ctx, const float* points, const float* normals, size_t n, float bias,
+                             float* out_rgba);
+int rmr_probe_irradiance_vis_device(rmr_ctx* ctx, const float* d_points, const float* d_normals, size_t n, float bias,
+                                    float* d_out_rgba);
 
 /* ---- display ---------------------------------------------------------------------------- */
 /* Graphics::Display(centre, zoom, min, max) (Graphics.cpp:356-390 with createFQ 227-258 and

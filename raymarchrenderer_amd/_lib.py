@@ -55,6 +55,10 @@ EXPORTS = [
     "rmr_probe_rays_device", "rmr_bake_probes", "rmr_bake_probes_device", "rmr_bake_probe_field", "rmr_write_probe_field",
     "rmr_read_probe_field", "rmr_probe_field_device_ptr", "rmr_probe_field_free", "rmr_probe_irradiance",
     "rmr_probe_irradiance_device",
+    "rmr_probe_vis_dirs", "rmr_probe_vis_fold", "rmr_probe_irradiance_vis_host", "rmr_bake_probe_visibility",
+    "rmr_bake_probe_visibility_device", "rmr_bake_probe_field_visibility", "rmr_write_probe_field_visibility",
+    "rmr_read_probe_field_visibility", "rmr_probe_field_visibility_device_ptr", "rmr_probe_irradiance_vis",
+    "rmr_probe_irradiance_vis_device",
 ]
 
 
@@ -275,6 +279,19 @@ def lib(diag=None):
         "rmr_probe_field_free": (C.c_int, [vp]),
         "rmr_probe_irradiance": (C.c_int, [vp, fp, fp, C.c_size_t, fp]),
         "rmr_probe_irradiance_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+        "rmr_probe_vis_dirs": (C.c_int, [fp]),
+        "rmr_probe_vis_fold": (C.c_int, [fp, C.c_size_t, C.c_uint32, C.c_float, fp]),
+        "rmr_probe_irradiance_vis_host": (C.c_int, [C.POINTER(abi.VolumeDesc), fp, fp, fp, fp, C.c_size_t, C.c_float, fp,
+                                                    C.POINTER(C.c_size_t)]),
+        "rmr_bake_probe_visibility": (C.c_int, [vp, fp, C.c_size_t, fp, C.c_uint32, C.POINTER(abi.ProbeParams), C.c_float, fp]),
+        "rmr_bake_probe_visibility_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, fp, C.c_uint32, C.POINTER(abi.ProbeParams),
+                                                       C.c_float, C.c_void_p]),
+        "rmr_bake_probe_field_visibility": (C.c_int, [vp, fp, C.c_uint32, C.c_float]),
+        "rmr_write_probe_field_visibility": (C.c_int, [vp, fp, C.c_float]),
+        "rmr_read_probe_field_visibility": (C.c_int, [vp, fp, fp]),
+        "rmr_probe_field_visibility_device_ptr": (vp, [vp]),
+        "rmr_probe_irradiance_vis": (C.c_int, [vp, fp, fp, C.c_size_t, C.c_float, fp]),
+        "rmr_probe_irradiance_vis_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p]),
         "rmr_diag_probe_fold": (C.c_int, [vp, C.c_int]),
         "rmr_diag_bake_kernels": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_size_t, fp, C.c_uint32,
                                             C.POINTER(abi.BakeParams), C.c_void_p]),

@@ -345,6 +345,10 @@ def bake_params(radiance=True, ao=False, bias=0.002, ao_distance=float("inf"), f
 
 # irradiance probes (rmr.h rmr_bake_probes)
 PROBE_FLOATS = 28
+# a probe's visibility map (rmr.h rmr_bake_probe_visibility): 8 x 8 texels of (m1, m2)
+PROBE_VIS_RES = 8
+PROBE_VIS_TEXELS = 64
+PROBE_VIS_FLOATS = 128
 
 
 class ProbeParams(C.Structure):

@@ -30,6 +30,7 @@
 #include "rmr_ray_check.h"
 #include "rmr_bake_rule.h"
 #include "rmr_probe_rule.h"
+#include "rmr_probe_vis_rule.h"
 #include "rmr_jit.hpp"
 #include "rmr_trail_rule.h"
 #include "scene.hpp"
@@ -89,6 +90,13 @@ hipError_t launch_probe_fold(int mapping, const float4* samp, const float4* rec,
                              uint64_t s0, uint32_t cnt, float* out, hipStream_t s);
 hipError_t launch_probe_lookup(const rmr_volume_desc& d, const float* sh, const float* points, const float* normals,
                                uint64_t n, float* out, unsigned long long* rejects, hipStream_t s);
+hipError_t launch_probe_vis_cast(const KParams& P, int np, const ProbeList& B, const float* valid_sh, float range,
+                                 uint64_t s0, uint32_t cnt, float4* rec, unsigned long long* rejects, hipStream_t s);
+hipError_t launch_probe_vis_fold(const float4* rec, float* state, uint64_t n, uint32_t nspp, float range, uint64_t s0,
+                                 uint32_t cnt, float* out, hipStream_t s);
+hipError_t launch_probe_lookup_vis(const rmr_volume_desc& d, const float* sh, const float* vis, const float* points,
+                                   const float* normals, uint64_t n, float bias, float* out, unsigned long long* rejects,
+                                   hipStream_t s);
 }  // namespace rmr
 
 using rmr::CompiledScene;
@@ -203,6 +211,13 @@ struct rmr_ctx {
     float* d_probe_field = nullptr;
     rmr_volume_desc probe_desc{};
     bool probe_valid = false;
+    // the field's visibility (rmr_bake_probe_field_visibility, rmr_probe_vis.hip): [points][128]
+    // floats and the range, dropped with the field and by every new field; the visibility bakes' running sums
+    void* d_probe_vis_state = nullptr;
+    size_t probe_vis_state_cap = 0;       // bytes
+    float* d_probe_vis = nullptr;
+    float probe_vis_range = 0.0f;
+    bool probe_vis_valid = false;
     int probe_fold_mapping = 0;           // rmr_probe.hip launch_probe_fold (the diagnostic library's switch)
     // which of the output stages' images below are valid: the one place that says so (stage_state.hpp)
     rmr::StageState st;
@@ -526,9 +541,11 @@ void free_mesh(rmr_ctx* c) {
 
 // Release the probe field and the probe bakes' state (the caller has synced the context's stream).
 void free_probes(rmr_ctx* c) {
-    free_all({&c->d_probe_field, &c->d_probe_state});
+    free_all({&c->d_probe_field, &c->d_probe_state, &c->d_probe_vis, &c->d_probe_vis_state});
     c->probe_state_cap = 0;
+    c->probe_vis_state_cap = 0;
     c->probe_valid = false;
+    c->probe_vis_valid = false;
 }
 
 // Release the half image and the tile-error map (the caller has synced the context's stream).
@@ -2890,9 +2907,10 @@ int probe_field_alloc(rmr_ctx* c, const char* who, const rmr_volume_desc* desc) 
         return fail(c, RMR_E_INVALID, std::string(who) + ": bad volume descriptor field '" + bad + "'");
     HIPCHK(c, hipSetDevice(c->device));
     c->probe_valid = false;
-    if (c->d_probe_field) {
+    c->probe_vis_valid = false;   // (a new field has no visibility)
+    if (c->d_probe_field || c->d_probe_vis) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        free_all({&c->d_probe_field});
+        free_all({&c->d_probe_field, &c->d_probe_vis});
     }
     return alloc_all(c, {{&c->d_probe_field, volume_points(desc) * rmr::kProbeFloats * sizeof(float)}},
                      "cannot allocate the probe field");
@@ -3041,6 +3059,183 @@ int rmr_probe_irradiance(rmr_ctx* c, const float* points, const float* normals, 
     HIPCHK(c, hipMemcpyAsync(d_p, points, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_n, normals, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if ((r = rmr_probe_irradiance_device(c, d_p, d_n, n, (float*)c->d_qout))) return r;
+    HIPCHK(c, hipMemcpyAsync(out_rgba, c->d_qout, n * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+// ---- the probes' visibility (rmr_probe_vis.hip, rmr_probe_vis_rule.h) ---------------------
+namespace {
+const char* const kNoProbeVis = "no probe visibility (call rmr_bake_probe_field_visibility / rmr_write_probe_field_visibility)";
+const char* const kNoProbeField = "no probe field (call rmr_bake_probe_field / rmr_write_probe_field)";
+
+// The maps of a device list (d_points) or of the context's field (desc, with its validity valid_sh), queued: the
+// tile-samples in runs under the plane budget at 16 bytes per unit, each run a cast and a fold; the records
+// live in the sample planes' buffer.
+int probe_vis_device(rmr_ctx* c, const char* who, const float* d_points, const rmr_volume_desc* desc, const float* valid_sh,
+                     size_t n, const float* times, uint32_t nspp, const rmr_probe_params& q, float range, float* d_out) {
+    int r;
+    if ((r = launch_precheck(c))) return r;
+    if (!rmr::vis_range_ok(range)) return fail(c, RMR_E_INVALID, std::string(who) + ": range must be finite and > 0");
+    if (!rmr::extent_ok(q.origin_extent))
+        return fail(c, RMR_E_INVALID, std::string(who) + ": origin_extent must be finite and >= 0");
+    if (n == 0) return RMR_OK;
+    KParams P;
+    if ((r = query_begin(c, P))) return r;
+    if ((r = ensure_qbuf(c, &c->d_probe_vis_state, &c->probe_vis_state_cap, n * rmr::kVisStateFloats * sizeof(float)))) return r;
+    rmr::ProbeList B = probe_list(d_points, desc, n, nspp, q, q.origin_extent);
+    if ((r = stage_times(c, times, nspp, &B.times))) return r;
+    const size_t n_ts = ((n + 63) / 64) * (size_t)nspp;
+    // (fewer than 2^31 units per launch: the kernels index a launch's units with 32 bits)
+    const size_t chunk = rmr::plan_samples(64, (uint32_t)n_ts, c->samp_budget, 0, sizeof(float4)).per_launch;
+    for (size_t k0 = 0; k0 < n_ts; k0 += chunk) {
+        const uint32_t cnt = (uint32_t)std::min(chunk, n_ts - k0);
+        if ((r = ensure_samp(c, (size_t)cnt * 64))) return r;
+        c->last_samp = c->d_samp;
+        HIPCHK(c, rmr::launch_probe_vis_cast(P, c->accel.map_np, B, valid_sh, range, k0, cnt, c->d_samp,
+                                             c->d_query + kQueryRejects, c->stream));
+        HIPCHK(c, rmr::launch_probe_vis_fold(c->d_samp, (float*)c->d_probe_vis_state, n, nspp, range, k0, cnt, d_out, c->stream));
+    }
+    return RMR_OK;
+}
+}  // namespace
+
+int rmr_bake_probe_visibility_device(rmr_ctx* c, const float* d_points, size_t n, const float* times, uint32_t nspp,
+                                     const rmr_probe_params* params, float range, float* d_out_vis) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_probe_params q;
+    int r;
+    if ((r = probe_args(c, "rmr_bake_probe_visibility_device", n, times, nspp, params, q))) return r;
+    if (n && (!d_points || !d_out_vis)) return fail(c, RMR_E_INVALID, "rmr_bake_probe_visibility_device: null buffer");
+    return probe_vis_device(c, "rmr_bake_probe_visibility_device", d_points, nullptr, nullptr, n, times, nspp, q, range, d_out_vis);
+}
+
+int rmr_bake_probe_visibility(rmr_ctx* c, const float* points, size_t n, const float* times, uint32_t nspp,
+                              const rmr_probe_params* params, float range, float* out_vis) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    rmr_probe_params q;
+    int r;
+    if ((r = probe_args(c, "rmr_bake_probe_visibility", n, times, nspp, params, q))) return r;
+    if (n && (!points || !out_vis)) return fail(c, RMR_E_INVALID, "rmr_bake_probe_visibility: null buffer");
+    // the probes' bound, over the finite ones
+    float ext = 0.0f;
+    for (size_t i = 0; i < 3 * n; i++)
+        if (std::isfinite(points[i])) ext = std::max(ext, std::fabs(points[i]));
+    q.origin_extent = ext;
+    if ((r = launch_precheck(c))) return r;
+    if (n == 0) return probe_vis_device(c, "rmr_bake_probe_visibility", nullptr, nullptr, nullptr, 0, times, nspp, q, range, nullptr);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((r = ensure_qbuf(c, &c->d_qin, &c->qin_cap, n * 3 * sizeof(float)))) return r;
+    if ((r = ensure_qbuf(c, &c->d_qout, &c->qout_cap, n * rmr::kVisFloats * sizeof(float)))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_qin, points, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((r = probe_vis_device(c, "rmr_bake_probe_visibility", (const float*)c->d_qin, nullptr, nullptr, n, times, nspp, q, range,
+                              (float*)c->d_qout)))
+        return r;
+    HIPCHK(c, hipMemcpyAsync(out_vis, c->d_qout, n * rmr::kVisFloats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+namespace {
+// The field's maps, allocated at first use (the field's size is fixed while it lives).
+int probe_vis_alloc(rmr_ctx* c) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->d_probe_vis) return RMR_OK;
+    return alloc_all(c, {{&c->d_probe_vis, volume_points(&c->probe_desc) * rmr::kVisFloats * sizeof(float)}},
+                     "cannot allocate the probe field's visibility");
+}
+}  // namespace
+
+int rmr_bake_probe_field_visibility(rmr_ctx* c, const float* times, uint32_t nspp, float range) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!c->probe_valid) return fail(c, RMR_E_STATE, kNoProbeField);
+    rmr_probe_params q;
+    int r;
+    const size_t n = volume_points(&c->probe_desc);
+    if ((r = probe_args(c, "rmr_bake_probe_field_visibility", n, times, nspp, nullptr, q))) return r;
+    q.origin_extent = lattice_extent(c->probe_desc);
+    if ((r = launch_precheck(c))) return r;
+    if (!rmr::vis_range_ok(range)) return fail(c, RMR_E_INVALID, "rmr_bake_probe_field_visibility: range must be finite and > 0");
+    c->probe_vis_valid = false;
+    if ((r = probe_vis_alloc(c))) return r;
+    if ((r = probe_vis_device(c, "rmr_bake_probe_field_visibility", nullptr, &c->probe_desc, c->d_probe_field, n, times, nspp, q,
+                              range, c->d_probe_vis)))
+        return r;
+    c->probe_vis_range = range;
+    c->probe_vis_valid = true;
+    return RMR_OK;
+}
+
+int rmr_write_probe_field_visibility(rmr_ctx* c, const float* vis, float range) {
+    if (!c || !vis) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!c->probe_valid) return fail(c, RMR_E_STATE, kNoProbeField);
+    if (!rmr::vis_range_ok(range)) return fail(c, RMR_E_INVALID, "rmr_write_probe_field_visibility: range must be finite and > 0");
+    c->probe_vis_valid = false;
+    int r;
+    if ((r = probe_vis_alloc(c))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->d_probe_vis, vis, volume_points(&c->probe_desc) * rmr::kVisFloats * sizeof(float),
+                             hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->probe_vis_range = range;
+    c->probe_vis_valid = true;
+    return RMR_OK;
+}
+
+int rmr_read_probe_field_visibility(rmr_ctx* c, float* vis, float* range_out) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (!c->probe_valid) return fail(c, RMR_E_STATE, kNoProbeField);
+    if (!c->probe_vis_valid) return fail(c, RMR_E_STATE, kNoProbeVis);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (range_out) *range_out = c->probe_vis_range;
+    if (vis)
+        HIPCHK(c, hipMemcpyAsync(vis, c->d_probe_vis, volume_points(&c->probe_desc) * rmr::kVisFloats * sizeof(float),
+                                 hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RMR_OK;
+}
+
+void* rmr_probe_field_visibility_device_ptr(rmr_ctx* c) {
+    return c && c->probe_valid && c->probe_vis_valid ? c->d_probe_vis : nullptr;
+}
+
+int rmr_probe_irradiance_vis_device(rmr_ctx* c, const float* d_points, const float* d_normals, size_t n, float bias,
+                                    float* d_out_rgba) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (n && (!d_points || !d_normals || !d_out_rgba)) return fail(c, RMR_E_INVALID, "rmr_probe_irradiance_vis_device: null buffer");
+    if (!rmr::vis_bias_ok(bias)) return fail(c, RMR_E_INVALID, "rmr_probe_irradiance_vis: bias must be finite and >= 0");
+    if (!c->probe_valid) return fail(c, RMR_E_STATE, kNoProbeField);
+    if (!c->probe_vis_valid) return fail(c, RMR_E_STATE, kNoProbeVis);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r;
+    if ((r = ensure_query(c))) return r;
+    HIPCHK(c, rmr::launch_probe_lookup_vis(c->probe_desc, c->d_probe_field, c->d_probe_vis, d_points, d_normals, (uint64_t)n, bias,
+                                           d_out_rgba, c->d_query + kQueryRejects, c->stream));
+    return RMR_OK;
+}
+
+int rmr_probe_irradiance_vis(rmr_ctx* c, const float* points, const float* normals, size_t n, float bias, float* out_rgba) {
+    if (!c) return RMR_E_INVALID;
+    RMR_FLUSH(c);
+    if (n && (!points || !normals || !out_rgba)) return fail(c, RMR_E_INVALID, "rmr_probe_irradiance_vis: null buffer");
+    if (!rmr::vis_bias_ok(bias)) return fail(c, RMR_E_INVALID, "rmr_probe_irradiance_vis: bias must be finite and >= 0");
+    if (!c->probe_valid) return fail(c, RMR_E_STATE, kNoProbeField);
+    if (!c->probe_vis_valid) return fail(c, RMR_E_STATE, kNoProbeVis);
+    if (n == 0) return RMR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int r;
+    if ((r = ensure_qbuf(c, &c->d_qin, &c->qin_cap, n * 6 * sizeof(float)))) return r;
+    if ((r = ensure_qbuf(c, &c->d_qout, &c->qout_cap, n * 4 * sizeof(float)))) return r;
+    float* d_p = (float*)c->d_qin;
+    float* d_n = d_p + 3 * n;
+    HIPCHK(c, hipMemcpyAsync(d_p, points, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_n, normals, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if ((r = rmr_probe_irradiance_vis_device(c, d_p, d_n, n, bias, (float*)c->d_qout))) return r;
     HIPCHK(c, hipMemcpyAsync(out_rgba, c->d_qout, n * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RMR_OK;

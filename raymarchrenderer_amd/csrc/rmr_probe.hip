@@ -15,52 +15,13 @@
 // probes, tile t's sample k is tile-sample t nspp + k, a launch covers a run of tile-samples.
 // Same float semantics as the trace kernels: -ffp-contract=off, hemisphere() and rand_step() of rmr_trace.h.
 #include <hip/hip_runtime.h>
-#include "rmr_cast.h"
-#include "rmr_probe_rule.h"
+#include "rmr_probe_ray.h"
 
 #ifndef RMR_PROBE_FOLD_PER_PROBE
 #define RMR_PROBE_FOLD_PER_PROBE 0
 #endif
 
 namespace rmr {
-
-struct ProbeRay {
-    V3 o, d;
-    float time, gxt, gyt;
-    int32_t gx, gy;
-};
-
-enum { kProbeUsed = 0, kProbeBuried = 1, kProbeRejected = 2 };
-
-// Sample k of probe i: kProbeUsed with the ray, or why there is none.
-template <class MAP>
-RMR_D int probe_ray(const KParams& P, const ProbeList& B, uint64_t i, uint32_t k, ProbeRay& r) {
-    float p[3];
-    probe_point(B, i, p);
-    const uint64_t idx = B.first_index + i;
-    r.gx = bake_gx(idx);
-    r.gy = bake_gy(idx);
-    r.time = B.times[k];
-    r.gxt = (float)r.gx + r.time;
-    r.gyt = (float)r.gy + r.time;
-    if (!probe_point_ok(p, B.extent)) return kProbeRejected;
-    r.o = v3(p[0], p[1], p[2]);
-    if (probe_buried(MAP::eval(P, r.o).x, B.clearance)) return kProbeBuried;
-    Lane L;
-    L.gxt = r.gxt;
-    L.gyt = r.gyt;
-    L.rc = 0.0f;   // a fresh chain, started as main() starts a pixel's (rmr_bake.hip bake_ray has the reason)
-    (void)lrand(L, v2(L.gxt, L.gyt));
-    r.d = hemisphere(L, v2(p[0], p[1]), v2(p[2], p[0]), v3(0.0f, 0.0f, 0.0f));   // zero normal: the whole sphere
-    return kProbeUsed;
-}
-
-// A wave's rejected probes, counted once per probe (at its sample 0): one add per wave that saw one.
-RMR_D void note_probe_rejects(bool rejected, unsigned long long* rejects) {
-    const uint64_t rj = __ballot(rejected);
-    if (rejects && rejected && (int)(threadIdx.x & 63u) == __ffsll((unsigned long long)rj) - 1)
-        atomicAdd(rejects, (unsigned long long)__popcll(rj));
-}
 
 // Records [0, 64 cnt) of a launch over tile-samples [s0, s0 + cnt), laid out as k_bake_rays lays them out:
 // (o, time), (d, 0), (gx + time, gy + time, mark, 0). The padding of the last tile and every rejected or buried
@@ -195,15 +156,6 @@ __global__ __launch_bounds__(256) void k_probe_lookup(rmr_volume_desc d, const f
     float* o = out + (size_t)i * 4;   // (any 4-byte alignment)
     o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = r[3];
 }
-
-#define RMR_PROBE_SWITCH(NPV, CALL)      \
-    switch (NPV) {                       \
-    case 4: CALL(4); break;              \
-    case 8: CALL(8); break;              \
-    case 0: CALL(0); break;              \
-    case -2: CALL(-2); break;            \
-    default: CALL(-1); break;            \
-    }
 
 // P: the launch parameters of the context's scene and params; np: the scene's table-driven map class.
 hipError_t launch_probe_rays(const KParams& P, int np, const ProbeList& B, uint64_t s0, uint32_t cnt, float4* rec,

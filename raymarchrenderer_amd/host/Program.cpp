@@ -79,6 +79,8 @@ struct Options {
     double probe_bounds[6] = {0, 0, 0, 0, 0, 0};  // --probe-bounds x0,y0,z0,x1,y1,z1
     int probe_grid = 8;             // --probe-grid N: cells along the longest side
     int probe_samples = 256;        // --probe-samples K: seeds per probe
+    int probe_vis = 0;              // --probe-visibility K[:RANGE]: seeds per probe of the visibility maps (0: none)
+    float probe_vis_range = 0.0f;   //   RANGE (0: 2.6f * spacing)
     double adaptive = -1.0;         // --adaptive T: the tile-error threshold, < 0 = uniform sampling
     int min_samples = 16, pass_samples = 16;   // --min-samples / --pass-samples (rmr_adaptive_params)
     bool have_camera = false;
@@ -421,7 +423,9 @@ rmr_volume_desc probe_lattice(const Options& o) { return box_lattice(o.probe_bou
 
 // --probes FILE: rmr_bake_probe_field over that lattice with --probe-samples seeds of the render's schedule,
 // written as the line "RMRPROBES 1 nx ny nz ox oy oz spacing" (floats as %.9g) and the points' 28 little-endian
-// float32 each (raymarchrenderer_amd.load_probes reads it).
+// float32 each (raymarchrenderer_amd.load_probes reads it). With --probe-visibility K[:RANGE]: the field's
+// visibility maps as well (rmr_bake_probe_field_visibility with the schedule's first K seeds), the line
+// "RMRPROBES 2 nx ny nz ox oy oz spacing 8 range" and, after the sh payload, the points' 128 float32 each.
 bool write_probes(const Options& o) {
     rmr_ctx* c = Graphics::context();
     auto fail = [&](const std::string& what) {
@@ -434,15 +438,28 @@ bool write_probes(const Options& o) {
     if (rmr_bake_probe_field(c, &d, times.data(), (uint32_t)o.probe_samples, nullptr) != RMR_OK) return fail("rmr_bake_probe_field");
     std::vector<float> sh((size_t)d.n[0] * (size_t)d.n[1] * (size_t)d.n[2] * 28);
     if (rmr_read_probe_field(c, nullptr, sh.data()) != RMR_OK) return fail("rmr_read_probe_field");
+    std::vector<float> vis;
+    const float range = o.probe_vis_range > 0.0f ? o.probe_vis_range : 2.6f * d.spacing;
+    if (o.probe_vis > 0) {
+        std::vector<float> vt((size_t)o.probe_vis);
+        for (int s = 0; s < o.probe_vis; s++) vt[(size_t)s] = seed_time(o.frame, (unsigned)s);
+        if (rmr_bake_probe_field_visibility(c, vt.data(), (uint32_t)o.probe_vis, range) != RMR_OK)
+            return fail("rmr_bake_probe_field_visibility");
+        vis.resize(sh.size() / 28 * 128);
+        if (rmr_read_probe_field_visibility(c, vis.data(), nullptr) != RMR_OK) return fail("rmr_read_probe_field_visibility");
+    }
     const uint16_t one = 1;
     unsigned char first;
     std::memcpy(&first, &one, 1);
     std::FILE* f = first == 1 ? std::fopen(o.probes.c_str(), "wb") : nullptr;   // (the floats are written as they lie in memory)
     bool ok = f != nullptr;
     if (f) {
-        std::fprintf(f, "RMRPROBES 1 %d %d %d %.9g %.9g %.9g %.9g\n", d.n[0], d.n[1], d.n[2], d.origin[0], d.origin[1],
-                     d.origin[2], d.spacing);
+        std::fprintf(f, "RMRPROBES %d %d %d %d %.9g %.9g %.9g %.9g", o.probe_vis > 0 ? 2 : 1, d.n[0], d.n[1], d.n[2], d.origin[0],
+                     d.origin[1], d.origin[2], d.spacing);
+        if (o.probe_vis > 0) std::fprintf(f, " 8 %.9g", range);
+        std::fprintf(f, "\n");
         ok = std::fwrite(sh.data(), sizeof(float), sh.size(), f) == sh.size();
+        ok = (vis.empty() || std::fwrite(vis.data(), sizeof(float), vis.size(), f) == vis.size()) && ok;
         ok = (std::fclose(f) == 0) && ok;
     }
     if (!ok) {
@@ -451,6 +468,7 @@ bool write_probes(const Options& o) {
     }
     if (!o.quiet) std::printf("probes: %d x %d x %d at spacing %.6g, %d samples each -> %s\n", d.n[0], d.n[1], d.n[2], d.spacing,
                               o.probe_samples, o.probes.c_str());
+    if (!o.quiet && o.probe_vis > 0) std::printf("probes: visibility maps from %d samples each, range %.6g\n", o.probe_vis, range);
     return true;
 }
 
@@ -639,6 +657,10 @@ void usage() {
         "  --probe-bounds x0,y0,z0,x1,y1,z1   the box the lattice spans\n"
         "  --probe-grid N      cells along the box's longest side (1..4095, default 8), as --mesh-grid\n"
         "  --probe-samples K   seeds per probe (1..2^24, default 256; seeds of --frame)\n"
+        "  --probe-visibility K[:RANGE]   with --probes: the probes' visibility maps as well (rmr.h\n"
+        "                      rmr_bake_probe_field_visibility: 8 x 8 octahedral depth moments per probe from K seeds,\n"
+        "                      1..2^24; RANGE finite and > 0, default 2.6 x spacing); the file becomes 'RMRPROBES 2 ...\n"
+        "                      spacing 8 range' with 128 more float32 per point after the sh payload\n"
         "  --adaptive T        adaptive sampling: render until every block's tile error is <= T, at most\n"
         "                      --samples per pixel, over the whole image; prints passes, mean spp, open tiles\n"
         "                      and max error; with --aov also PREFIX_spp.pfm (R = samples) and PREFIX_error.pfm\n"
@@ -841,6 +863,20 @@ bool parse(int argc, char** argv, Options& o) {
             const long n = std::strtol(v, &end, 10);
             if (end == v || *end != '\0' || n < 1 || n > (1L << 24)) return false;
             o.probe_samples = (int)n;
+            o.have_probe_opts = true;
+        } else if (a == "--probe-visibility") {
+            char* end = nullptr;
+            const char* v = next("--probe-visibility");
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || n < 1 || n > (1L << 24)) return false;
+            o.probe_vis = (int)n;
+            if (*end == ':') {
+                const char* rv = end + 1;
+                o.probe_vis_range = std::strtof(rv, &end);
+                if (end == rv || *end != '\0' || !std::isfinite(o.probe_vis_range) || !(o.probe_vis_range > 0.0f)) return false;
+            } else if (*end != '\0') {
+                return false;
+            }
             o.have_probe_opts = true;
         } else if (a == "--mesh-bake") {
             char* end = nullptr;

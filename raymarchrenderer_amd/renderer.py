@@ -718,26 +718,103 @@ class Renderer:
         """rmr_probe_field_free: release the field and the probe bakes' working memory."""
         self._chk(self._L.rmr_probe_field_free(self._ctx))
 
-    def probe_irradiance(self, points, normals):
+    def probe_irradiance(self, points, normals, visibility=False, bias=0.0):
         """rmr_probe_irradiance: irradiance / pi at n points with unit normals ((n, 3) float32 each) from the
         context's field: (n, 4) float32, rgb and the valid corners' weight. A rejected query gives zeros and
-        counts in query_rejects()."""
+        counts in query_rejects(). visibility=True: rmr_probe_irradiance_vis, each corner weighted by the field's
+        visibility maps (bake_probe_field_visibility) and a back-face term, the point moved bias along its normal;
+        it raises without baked maps."""
         p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         nn = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
         if len(p) != len(nn):
             raise ValueError("one normal per point")
         out = np.zeros((len(p), 4), np.float32)
-        self._chk(self._L.rmr_probe_irradiance(self._ctx, _fp(p), _fp(nn), len(p), _fp(out)))
+        if visibility:
+            self._chk(self._L.rmr_probe_irradiance_vis(self._ctx, _fp(p), _fp(nn), len(p), float(bias), _fp(out)))
+        else:
+            self._chk(self._L.rmr_probe_irradiance(self._ctx, _fp(p), _fp(nn), len(p), _fp(out)))
         return out
 
-    def probe_irradiance_device(self, points, normals):
+    def probe_irradiance_device(self, points, normals, visibility=False, bias=0.0):
         """rmr_probe_irradiance_device: probe_irradiance on torch CUDA tensors, the (n, 4) result a torch tensor on
         the same device; queued on the context's stream, no sync."""
         import torch
         n = self._device_points(points, normals)
         out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
-        self._chk(self._L.rmr_probe_irradiance_device(self._ctx, points.data_ptr(), normals.data_ptr(), n, out.data_ptr()))
+        if visibility:
+            self._chk(self._L.rmr_probe_irradiance_vis_device(self._ctx, points.data_ptr(), normals.data_ptr(), n, float(bias),
+                                                              out.data_ptr()))
+        else:
+            self._chk(self._L.rmr_probe_irradiance_device(self._ctx, points.data_ptr(), normals.data_ptr(), n, out.data_ptr()))
         return out
+
+    # -- the probes' visibility: octahedral depth moments per probe (rmr.h; DESIGN.md §4.19) --
+    def bake_probe_visibility(self, points, times, range, clearance=0.0, first_index=0):
+        """rmr_bake_probe_visibility: the visibility maps of n probe points ((n, 3) float32) from the samples
+        seeded `times`: (n, 64, 2) float32, the first two moments of the distance min(t, range) each of the 8 x 8
+        octahedral texels sees. A rejected or buried probe gives zeros; rejected ones count in query_rejects()."""
+        q = abi.probe_params(clearance=clearance, first_index=first_index)
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        out = np.zeros((len(p), abi.PROBE_VIS_TEXELS, 2), np.float32)
+        self._chk(self._L.rmr_bake_probe_visibility(self._ctx, _fp(p), len(p), _fp(t) if len(t) else None, len(t), C.byref(q),
+                                                    float(range), _fp(out)))
+        return out
+
+    def bake_probe_visibility_device(self, points, times, origin_extent, range, clearance=0.0, first_index=0):
+        """rmr_bake_probe_visibility_device: bake_probe_visibility on a torch CUDA tensor ((n, 3) float32), the
+        (n, 64, 2) result a torch tensor on the same device; queued on the context's stream, no sync.
+        origin_extent: a bound on |coordinate| of every probe."""
+        import torch
+        q = abi.ProbeParams(float(clearance), float(origin_extent), int(first_index))
+        n = self._device_probes(points)
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        out = torch.empty((n, abi.PROBE_VIS_TEXELS, 2), dtype=torch.float32, device=points.device)
+        self._chk(self._L.rmr_bake_probe_visibility_device(self._ctx, points.data_ptr(), n, _fp(t) if len(t) else None, len(t),
+                                                           C.byref(q), float(range), out.data_ptr()))
+        return out
+
+    def bake_probe_field_visibility(self, times, range=None):
+        """rmr_bake_probe_field_visibility: the maps of the context's field, stored with it for
+        probe_irradiance(..., visibility=True). range=None: np.float32(2.6) * spacing, about 1.5 cell diagonals.
+        Queued on the context's stream, no sync."""
+        if range is None:
+            d = abi.VolumeDesc()
+            self._chk(self._L.rmr_read_probe_field(self._ctx, C.byref(d), None))
+            range = np.float32(2.6) * np.float32(d.spacing)
+        t = np.ascontiguousarray(times, np.float32).reshape(-1)
+        self._chk(self._L.rmr_bake_probe_field_visibility(self._ctx, _fp(t) if len(t) else None, len(t), float(range)))
+
+    def _probe_field_points(self):
+        d = abi.VolumeDesc()
+        self._chk(self._L.rmr_read_probe_field(self._ctx, C.byref(d), None))
+        return d.n[0] * d.n[1] * d.n[2]
+
+    def write_probe_field_visibility(self, vis, range):
+        """rmr_write_probe_field_visibility: load saved or synthetic maps, vis (points, 64, 2) float32, for the
+        context's field."""
+        a = np.ascontiguousarray(vis, np.float32)
+        if a.size != self._probe_field_points() * abi.PROBE_VIS_FLOATS:
+            raise ValueError("vis: 128 floats per lattice point")
+        self._chk(self._L.rmr_write_probe_field_visibility(self._ctx, _fp(a), float(range)))
+
+    def read_probe_field_visibility(self):
+        """rmr_read_probe_field_visibility: (vis (points, 64, 2) float32, range)."""
+        rng = C.c_float(0.0)
+        self._chk(self._L.rmr_read_probe_field_visibility(self._ctx, None, C.byref(rng)))
+        vis = np.zeros((self._probe_field_points(), abi.PROBE_VIS_TEXELS, 2), np.float32)
+        self._chk(self._L.rmr_read_probe_field_visibility(self._ctx, _fp(vis), None))
+        return vis, np.float32(rng.value)
+
+    def probe_field_visibility_device(self):
+        """rmr_probe_field_visibility_device_ptr: the maps as a (points, 64, 2) torch tensor on the context's
+        device, a view of the library's memory (no copy, no sync), or None without them."""
+        import torch
+        ptr = self._L.rmr_probe_field_visibility_device_ptr(self._ctx)
+        if not ptr:
+            return None
+        shape = (self._probe_field_points(), abi.PROBE_VIS_TEXELS, 2)
+        return torch.as_tensor(_DeviceArray(ptr, shape, self), device="cuda:%d" % self._device)
 
     def sync(self):
         self._chk(self._L.rmr_sync(self._ctx))
@@ -1433,32 +1510,107 @@ def probe_irradiance_host(desc, sh, points, normals):
     return out, (None if rc == abi.RMR_OK else int(bad.value))
 
 
-def save_probes(path, desc, sh):
+def probe_vis_dirs():
+    """rmr_probe_vis_dirs (no GPU): the 64 texel directions of a probe's visibility map, (64, 3) float32."""
+    out = np.zeros((abi.PROBE_VIS_TEXELS, 3), np.float32)
+    rc = lib().rmr_probe_vis_dirs(_fp(out))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_probe_vis_dirs")
+    return out
+
+
+def probe_vis_fold(d_and_t, range):
+    """rmr_probe_vis_fold (no GPU): the visibility's fold and resolve of host samples laid out [k][i], d_and_t
+    (N, n, 4) float32 = (d.xyz, t): (n, 64, 2) float32."""
+    a = np.ascontiguousarray(d_and_t, np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError("probe_vis_fold: d_and_t of shape (N, n, 4)")
+    nspp, n = a.shape[:2]
+    out = np.zeros((n, abi.PROBE_VIS_TEXELS, 2), np.float32)
+    rc = lib().rmr_probe_vis_fold(_fp(a), n, nspp, float(range), _fp(out))
+    if rc != abi.RMR_OK:
+        raise RMRError(rc, "rmr_probe_vis_fold")
+    return out
+
+
+def probe_irradiance_vis_host(desc, sh, vis, points, normals, bias=0.0):
+    """rmr_probe_irradiance_vis_host (no GPU): the visibility-weighted lookup over a host field and its maps,
+    (rgba (n, 4) float32, the first rejected query's index or None)."""
+    d = _volume_desc(desc, None, None) if isinstance(desc, abi.VolumeDesc) else _volume_desc(*desc)
+    a = np.ascontiguousarray(sh, np.float32)
+    npnt = d.n[0] * d.n[1] * d.n[2]
+    if a.size != npnt * abi.PROBE_FLOATS:
+        raise ValueError("sh: 28 floats per lattice point")
+    v = np.ascontiguousarray(vis, np.float32)
+    if v.size != npnt * abi.PROBE_VIS_FLOATS:
+        raise ValueError("vis: 128 floats per lattice point")
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if len(p) != len(n):
+        raise ValueError("one normal per point")
+    if not (np.isfinite(bias) and bias >= 0):
+        raise RMRError(-1, "rmr_probe_irradiance_vis_host: bias must be finite and >= 0")
+    out = np.zeros((len(p), 4), np.float32)
+    bad = C.c_size_t(0)
+    rc = lib().rmr_probe_irradiance_vis_host(C.byref(d), _fp(a), _fp(v), _fp(p), _fp(n), len(p), float(bias), _fp(out), C.byref(bad))
+    return out, (None if rc == abi.RMR_OK else int(bad.value))
+
+
+def save_probes(path, desc, sh, vis=None, vis_range=None):
     """A probe field as a file: the line 'RMRPROBES 1 nx ny nz ox oy oz spacing' (floats as %.9g), then the
-    points * 28 little-endian float32 of sh."""
+    points * 28 little-endian float32 of sh. With vis ((points, 64, 2) float32) and vis_range: the line 'RMRPROBES
+    2 nx ny nz ox oy oz spacing 8 range', then sh, then the points * 128 little-endian float32 of vis."""
     d = _volume_desc(desc, None, None) if isinstance(desc, abi.VolumeDesc) else _volume_desc(*desc)
     a = np.ascontiguousarray(sh, "<f4")
-    if a.size != d.n[0] * d.n[1] * d.n[2] * abi.PROBE_FLOATS:
+    npnt = d.n[0] * d.n[1] * d.n[2]
+    if a.size != npnt * abi.PROBE_FLOATS:
         raise ValueError("sh: 28 floats per lattice point")
-    head = "RMRPROBES 1 %d %d %d %s\n" % (d.n[0], d.n[1], d.n[2],
-                                        " ".join("%.9g" % v for v in (d.origin[0], d.origin[1], d.origin[2], d.spacing)))
+    if (vis is None) != (vis_range is None):
+        raise ValueError("vis and vis_range go together")
+    floats = [d.origin[0], d.origin[1], d.origin[2], d.spacing]
+    tail = b""
+    if vis is not None:
+        v = np.ascontiguousarray(vis, "<f4")
+        if v.size != npnt * abi.PROBE_VIS_FLOATS:
+            raise ValueError("vis: 128 floats per lattice point")
+        rng = float(np.float32(vis_range))
+        if not (np.isfinite(rng) and rng > 0):
+            raise ValueError("vis_range: finite and > 0")
+        tail = v.tobytes()
+    head = "RMRPROBES %d %d %d %d %s" % (1 if vis is None else 2, d.n[0], d.n[1], d.n[2], " ".join("%.9g" % x for x in floats))
+    if vis is not None:
+        head += " %d %.9g" % (abi.PROBE_VIS_RES, rng)
     with open(path, "wb") as f:
-        f.write(head.encode("ascii"))
+        f.write((head + "\n").encode("ascii"))
         f.write(a.tobytes())
+        f.write(tail)
 
 
-def load_probes(path):
-    """(desc, sh) of a file save_probes or rmr_cli --probes wrote: an abi.VolumeDesc and (points, 28) float32."""
+def load_probes(path, visibility=False):
+    """(desc, sh) of a file save_probes or rmr_cli --probes wrote: an abi.VolumeDesc and (points, 28) float32.
+    visibility=True: (desc, sh, vis, range), vis (points, 64, 2) float32, or None, None for a file without it."""
     with open(path, "rb") as f:
         w = f.readline().decode("ascii", "replace").split()
-        if len(w) != 9 or w[:2] != ["RMRPROBES", "1"]:
-            raise ValueError("%s: not a probe file (RMRPROBES 1 ...)" % path)
+        v1 = len(w) == 9 and w[:2] == ["RMRPROBES", "1"]
+        v2 = len(w) == 11 and w[:2] == ["RMRPROBES", "2"] and w[9] == str(abi.PROBE_VIS_RES)
+        if not (v1 or v2):
+            raise ValueError("%s: not a probe file (RMRPROBES 1 ... or RMRPROBES 2 ... 8 range)" % path)
         d = _volume_desc([float(v) for v in w[5:8]], float(w[8]), [int(v) for v in w[2:5]])
-        n = d.n[0] * d.n[1] * d.n[2] * abi.PROBE_FLOATS
+        npnt = d.n[0] * d.n[1] * d.n[2]
+        n = npnt * abi.PROBE_FLOATS
+        nv = npnt * abi.PROBE_VIS_FLOATS if v2 else 0
         raw = f.read()
-    if len(raw) != 4 * n:
-        raise ValueError("%s: %d payload bytes, the lattice needs %d" % (path, len(raw), 4 * n))
-    return d, np.frombuffer(raw, "<f4").astype(np.float32).reshape(-1, abi.PROBE_FLOATS)
+    if len(raw) != 4 * (n + nv):
+        raise ValueError("%s: %d payload bytes, the lattice needs %d" % (path, len(raw), 4 * (n + nv)))
+    sh = np.frombuffer(raw[:4 * n], "<f4").astype(np.float32).reshape(-1, abi.PROBE_FLOATS)
+    if not visibility:
+        return d, sh
+    if not v2:
+        return d, sh, None, None
+    rng = np.float32(float(w[10]))
+    if not (np.isfinite(rng) and rng > 0):
+        raise ValueError("%s: the visibility's range must be finite and > 0" % path)
+    return d, sh, np.frombuffer(raw[4 * n:], "<f4").astype(np.float32).reshape(-1, abi.PROBE_VIS_TEXELS, 2), rng
 
 
 class _DeviceArray:
