@@ -7,6 +7,7 @@ Fixtures are data (inputs + reference outputs); the reference source itself is n
   kat_<scene>.npz   function-level known answers: map / march / getNormal / rand chain /
                     randHemisphere on fixed input sets (+ wavelengthToColor for RM3; + edge_in / edge_out for
                     trig_nodes: map with NaN and +-inf objects)
+  kat_sky.npz       skyColor(d) with an env texture bound, RM1 and RM2, on two maps of tests/env_family.py
   img_<name>.npz    low-spp renders (4 spp) and converged renders (--conv-spp) of 64x48 images
   display_ref.npz   Graphics::Display (FullQuad.vs / .fs, GL_FRAMEBUFFER_SRGB, blend) drawn screens
 MANIFEST.json records every configuration, the camera, the seed schedule and the GL driver.
@@ -152,6 +153,37 @@ def make_kat_nan(rng):
     np.savez_compressed(os.path.join(GOLDEN, "kat_nan.npz"), **out)
 
 
+def make_kat_sky():
+    """skyColor(d) of the reference with an env texture bound (RM1:78-113 = RM2:84-107), through
+    ref_run.sky_probe, on the fixture maps and directions of tests/env_family.py (the directions without the two
+    poles: GLSL leaves atan(0, 0) undefined). Returns the MANIFEST entry, with the largest difference between the
+    oracle and llvmpipe on the noise map in units of 2^-8 times the spread of the four texels the float64
+    statement (tests/env_ref.py) selects: llvmpipe filters with 8-bit weights."""
+    from oracle import oracle
+    from tests import env_family as ef
+    from tests import env_ref
+    dirs = ef.fixture_directions()
+    prm = abi.default_params(use_env_tex=1)
+    scenes = {1: os.path.join(ROOT, "scenes", "sphere1.scene"), 2: os.path.join(GS, "simple.scene")}
+    out = {"dirs": np.array(dirs)}
+    for mname in ef.FIXTURE_MAPS:
+        env = ef.maps()[mname]
+        out["map_" + mname] = np.array(env)
+        for variant, path in scenes.items():
+            out["rm%d_%s" % (variant, mname)] = ref_run.sky_probe(variant, _scene(path), dirs, env, prm)
+    np.savez_compressed(os.path.join(GOLDEN, "kat_sky.npz"), **out)
+    noise = ef.FIXTURE_MAPS[1]
+    env = ef.maps()[noise]
+    got = ef.oracle_trace(ef.direct_oracle("sphere1", env), ef.direct_rays("sphere1", dirs))
+    spread = env_ref.spread(env, dirs)
+    some = spread > 0      # (both clamps at once select one texel four times: no spread, and no filter error)
+    ratio = max(float((np.abs(got - out["rm%d_%s" % (v, noise)])[some] / (spread[some] * 2.0 ** -8)).max()) for v in scenes)
+    return {"maps": list(ef.FIXTURE_MAPS), "directions": len(dirs), "variants": [1, 2],
+            "probe": "skyColor(d) with envTex bound, GL_LINEAR, CLAMP_TO_EDGE; the poles (0, +-1, 0) left out",
+            "llvmpipe_ratio": round(ratio, 4),
+            "llvmpipe_ratio_unit": "2^-8 x spread of the four selected texels, oracle minus llvmpipe on " + noise}
+
+
 def make_image(name, path, variant, kw, conv_spp, threads):
     scene = _scene(path)
     prm = abi.default_params(**kw)
@@ -208,7 +240,7 @@ def make_display():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="", help="comma-separated fixture names (kat_<scene>, kat_nan, <image>)")
+    ap.add_argument("--only", default="", help="comma-separated fixture names (kat_<scene>, kat_nan, kat_sky, <image>)")
     ap.add_argument("--threads", type=int, default=8)
     ap.add_argument("--conv-scale", type=float, default=1.0)
     args = ap.parse_args()
@@ -250,6 +282,9 @@ def main():
         make_kat_nan(np.random.default_rng(7))
         man["kat"]["nan"] = {"scenes": [k for k, v in KATS.items() if v[1] == 1], "probe": "map/march with NaN dir"}
         print("kat nan", flush=True)
+    if not args.only or "kat_sky" in args.only.split(","):
+        man["kat"]["sky"] = make_kat_sky()
+        print("kat sky", man["kat"]["sky"]["llvmpipe_ratio"], flush=True)
     for name, (path, variant, kw, spp) in IMAGES.items():
         if args.only and name not in args.only.split(","):
             continue

@@ -172,6 +172,34 @@ void main()
     return so.reshape(n, 3)
 
 
+SKY_MAIN = r"""
+layout(std430, binding = 2) readonly buffer ProbeIn { float pin[]; };
+layout(std430, binding = 3) writeonly buffer ProbeOut { float pout[]; };
+uniform int probeCount;
+void main()
+{
+    uint gw = gl_NumWorkGroups.x * gl_WorkGroupSize.x;
+    uint i = gl_GlobalInvocationID.y * gw + gl_GlobalInvocationID.x;
+    if (i >= uint(probeCount)) return;
+    vec3 c = skyColor(vec3(pin[3 * i], pin[3 * i + 1], pin[3 * i + 2]));
+    pout[3 * i] = c.r; pout[3 * i + 1] = c.g; pout[3 * i + 2] = c.b;
+}
+"""
+
+
+def sky_probe(variant, scene, dirs, env, params, width=64):
+    """skyColor(d) of the reference with `env` ((h, w, 4) uint8) bound as envTex, for every direction:
+    (n, 3) float32. params.use_env_tex decides the branch, as in a render."""
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    n = len(d)
+    src = shader_build.build(variant, scene, probe_main=SKY_MAIN)
+    lx, ly = shader_build.LOCAL[variant]
+    lines = ["image 8 8"] + _uniform_lines(params, np.zeros(15, np.float32))
+    lines += ["ui probeCount %d" % n, "run 0 0 0 0 0 0 %d %d" % (width // lx, int(math.ceil(n / float(width) / ly)))]
+    _, so = run_job(src, lines, None, ssbo_in=d.ravel(), ssbo_out_n=3 * n, env=env)
+    return so.reshape(n, 3)
+
+
 DISPLAY_HARNESS = os.path.join(REF_OUT, "display_harness")
 
 

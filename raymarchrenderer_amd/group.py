@@ -135,6 +135,15 @@ class DeviceGroup:
         self._view = parts
         self._chk(self._L.rmr_group_set_view(self._g, *[p.ctypes.data_as(C.POINTER(C.c_float)) for p in parts]))
 
+    def set_env_map(self, rgba8):
+        """envTex for skyColor on every context of the group (rmr_group_set_env_map; Renderer.set_env_map):
+        (h, w, 4) uint8, row 0 = up. None clears."""
+        if rgba8 is None:
+            self._chk(self._L.rmr_group_set_env_map(self._g, None, 0, 0))
+            return
+        a = np.ascontiguousarray(rgba8, np.uint8)
+        self._chk(self._L.rmr_group_set_env_map(self._g, a.ctypes.data, a.shape[1], a.shape[0]))
+
     def reload(self):
         self._chk(self._L.rmr_group_reload(self._g))
 
